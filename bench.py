@@ -11,7 +11,10 @@ predecessor touched.  With N>1 every rank holds a replica of the index, classifi
 per-read results are gathered on rank 0 over RCCL inside the timed region (`--scaling weak`: per-GPU work fixed;
 `--scaling strong`: the N=1 batch is cut into N shards).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the --steps steps and
+prints the headline (value, ms_per_step, the roofline figures of the timed steps' own HIP events, stage times); --dump-outputs DIR
+also writes what the last step computed (DIR/<name>.npy).  Everything below that takes runs of its own or checks the results
+comes only with --full (the --no-* switches narrow a --full run), with extra objects:
   roofline     : k_query_level (dominant kernel).  achieved = bytes the kernel REQUESTED (device-counted) / its
                  HIP-event time, frac = achieved / 8 TB/s (<= 1 by construction).  The reference's formulation
                  counts every hash against every bin (n_h*3*bins per visited IXF); threshold-aware
@@ -150,8 +153,22 @@ def parse_args(argv=None):
     ap.add_argument("--traffic", default="live", choices=("live", "none"),
                     help="live: two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) over one step before the run")
     ap.add_argument("--dump-results", default="", help="rank 0 writes the last step's (gathered) CSR results to this .npz (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all: a fixed, seeded "
+                         "sample of the reads where the whole output is larger)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: live PMC traffic, unpruned pass, gather ceiling, read error 0.04 leg, host-fed "
+                         "rates, CPU baseline, `layouts` legs, the N > 1 strong-scaling leg, and the build line's spot check, host-fed "
+                         "build and reference builder.  Without it a run sets up, warms up, times --steps steps and prints the line; "
+                         "the --no-* switches and --traffic only narrow a --full run")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.traffic = "none"
+        args.no_unpruned = args.no_ceiling = args.no_e04 = args.no_dropin = args.no_cpu_baseline = args.no_layouts = True
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -432,6 +449,56 @@ def build_cpu_reference(n_keys, salt):
                       "bin, best of 3; one filter at a time on one core is how the reference builds (construct_ixf.cpp:80-130)"}
 
 
+DUMP_CAP_BYTES = 64 << 20     # --dump-outputs: all files of one run together
+
+
+def _seeded_sample(n, k, salt):
+    """k of range(n), sorted: the same indices for the same (n, k, salt) on every run"""
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(salt).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_search_outputs(d, read_off, user_bin, count, n_hashes):
+    """--dump-outputs of the search modes: the per-read CSR of the last timed step (what taxor_gpu_search_batch hands its caller) as
+    float64, exact for every value below 2^53.  read_index names the reads written: all of them, or a seeded sample of whole reads
+    when the CSR would exceed DUMP_CAP_BYTES (read_off is then the sample's own CSR)."""
+    os.makedirs(d, exist_ok=True)
+    read_off = np.asarray(read_off, dtype=np.int64)
+    n = read_off.size - 1
+    per = np.diff(read_off)
+    k = n
+    while True:
+        ids = _seeded_sample(n, k, 0x5EED)
+        nbytes = 8 * (3 * ids.size + 1 + 2 * int(per[ids].sum()))
+        if nbytes <= DUMP_CAP_BYTES or k == 0:
+            break
+        k = min(k - 1, int(k * DUMP_CAP_BYTES / nbytes * 0.98))
+    lens = per[ids]
+    off = np.zeros(ids.size + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    tup = np.repeat(read_off[ids] - off[:-1], lens) + np.arange(int(off[-1]), dtype=np.int64)
+    arrays = {"read_index": ids, "read_off": off, "user_bin": np.asarray(user_bin)[tup], "count": np.asarray(count)[tup],
+              "n_hashes": np.asarray(n_hashes)[ids]}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), np.asarray(a).astype(np.float64))
+    log(f"outputs of the last step: {ids.size} of {n} reads, {int(off[-1])} tuples -> {d}")
+
+
+def dump_build_outputs(d, idx, nc):
+    """--dump-outputs of --mode build: what the last build left in the index -- every IXF's seed (split into 32-bit halves, float64) and a
+    seeded sample of the fingerprint bytes of the root, the first and the last child IXF (float32)"""
+    os.makedirs(d, exist_ok=True)
+    seeds = np.array([idx.ixf_seed(i) for i in range(idx.n_ixf)], dtype=np.uint64)
+    np.save(os.path.join(d, "ixf_seed_hi.npy"), (seeds >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(d, "ixf_seed_lo.npy"), (seeds & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    for name, ixf in (("root", 0), ("child_first", 1), ("child_last", nc)):
+        data = idx.download_ixf(ixf)
+        np.save(os.path.join(d, f"fingerprints_{name}.npy"), data[_seeded_sample(data.size, 4 << 20, 0x5EED + ixf)].astype(np.float32))
+        del data
+    log(f"outputs of the last build: {idx.n_ixf} IXF seeds, fingerprint samples of IXFs 0, 1, {nc} -> {d}")
+
+
 # algorithmic bytes one key insertion moves in builder.hip (32-bit state words; DESIGN.md section 4 derives the sum):
 #   key 8 B x 4 (count, round, assign, verify) + state word: 3 adds + 2 subs (4 B read + 4 B written each), 1 load, the seed scan over
 #   1.23 slots + list entry 8 B written and read for 1.12 listed rows + log 4 + 4 + round marks: 2 B written per listed row, ~1 read
@@ -472,16 +539,19 @@ def build_mode(args):
     secs = sum(s_["seconds_total"] for s_ in sts)
     wall = sum(s_["wall_s"] for s_ in sts)
     value = ins / secs
+    if args.dump_outputs:
+        dump_build_outputs(args.dump_outputs, idx, nc)
     # spot check through the query kernel against the oracle's answer for the same keys (the full check is tests/test_gpu_build_fullsize.py)
-    sr = Searcher(idx, ratio=0.5)
-    rb = shapes[0]["bins"]
-    for c, b in ((1, 0), (nc, cb - 1)):
-        g = rb + (c - 1) * cb + b
-        keys = synth.synth_keys_host(int(off[g]), int(off[g + 1] - off[g]), salt)[::8]      # (every 8th key of the bin: a spot check)
-        own, up = sr.ixf_bulk_count(c, keys), sr.ixf_bulk_count(0, keys)
-        if own[b] != keys.size or up[c - 1] != keys.size:
-            raise SystemExit("PARITY FAILURE: a built bin does not hold its keys")
-    sr.close()
+    if args.full:
+        sr = Searcher(idx, ratio=0.5)
+        rb = shapes[0]["bins"]
+        for c, b in ((1, 0), (nc, cb - 1)):
+            g = rb + (c - 1) * cb + b
+            keys = synth.synth_keys_host(int(off[g]), int(off[g + 1] - off[g]), salt)[::8]      # (every 8th key of the bin: a spot check)
+            own, up = sr.ixf_bulk_count(c, keys), sr.ixf_bulk_count(0, keys)
+            if own[b] != keys.size or up[c - 1] != keys.size:
+                raise SystemExit("PARITY FAILURE: a built bin does not hold its keys")
+        sr.close()
     # the same from keys in HOST memory, as a binding has them (construct_ixf.cpp reads the bins' hashes from temp files): PCIe inside,
     # never `value`.  A smaller hierarchy (<= 16 children: 7 GB of keys), two builds.
     import ctypes as C
@@ -594,7 +664,7 @@ def main():
         numa_info = numa.bind_to_gpu(0 if os.environ.get("TAXOR_BENCH_SAME_GPU") == "1" else local_rank)
 
     # live PMC passes run as child processes before anything here touches the GPU
-    traffic, traffic_src, traffic_detail = None, "not collected (--traffic none, a child run, or N > 1)", {}
+    traffic, traffic_src, traffic_detail = None, "not collected (a run without --full, --traffic none, a child run, or N > 1)", {}
     if args.traffic == "live" and not args.pmc_child and world == 1:
         try:
             traffic, traffic_src, traffic_detail = live_traffic(args)
@@ -773,21 +843,24 @@ def main():
         want = n_reads if args.scaling == "strong" else n_reads * world
         assert g_nh.numel() == want, (g_nh.numel(), want)
     value = acc["all_bases"] / elapsed / 1e6
-    if args.dump_results and rank == 0:
+    if (args.dump_results or args.dump_outputs) and rank == 0:
         if dist_on:
             d_off, d_ub, d_cnt, d_nh = (x.cpu().numpy() for x in gathered["last"])
         else:
             r_ = searchers[(args.warmup + args.steps - 1) % len(searchers)].fetch()
             d_off, d_ub, d_cnt, d_nh = r_.read_off, r_.user_bin, r_.count, r_.n_hashes
-        np.savez(args.dump_results, read_off=d_off.astype(np.int64), user_bin=d_ub.astype(np.int64), count=d_cnt.astype(np.int64),
-                 n_hashes=d_nh.astype(np.int64))
+        if args.dump_results:
+            np.savez(args.dump_results, read_off=d_off.astype(np.int64), user_bin=d_ub.astype(np.int64), count=d_cnt.astype(np.int64),
+                     n_hashes=d_nh.astype(np.int64))
+        if args.dump_outputs:
+            dump_search_outputs(args.dump_outputs, d_off, d_ub, d_cnt, d_nh)
 
     # N > 1 (or the forced one-rank group): the same invocation also runs three STRONG-scaling steps -- one common batch, rank r
     # classifies its contiguous shard, the shards are gathered -- and rank 0 classifies the whole batch alone: the gathered CSR must
     # be the single-rank CSR, bit for bit.  That holds only if every rank's replica of the index is the same (the builder is
     # deterministic) and every rank's tuples arrived in rank order.
     strong_leg = None
-    if dist_on and args.mode == "syncmer" and not args.len_mix and not args.pmc_child:
+    if dist_on and args.full and args.mode == "syncmer" and not args.len_mix and not args.pmc_child:
         import hashlib
         from taxor_amd import synth as synth_s
 

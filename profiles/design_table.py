@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""DESIGN.md section 5's table from ONE bench.py line (the headline and the `layouts` legs of the same invocation).
+"""DESIGN.md section 5's table from ONE `bench.py --full` line (the headline and the `layouts` legs of the same invocation).
 usage: python profiles/design_table.py profiles/r06/bench_gtdb.json [profiles/r06/bench_build.json] [--write]
 (--write: replace the block between the <!-- BENCH-TABLE --> markers of DESIGN.md; the second file adds the builder's line)"""
 import json
@@ -14,7 +14,7 @@ c, r = j["config"], j["roofline"]
 lv = r.get("levels", [])
 gc = r.get("gather_ceiling", {})
 out = []
-out.append(f"Source: `{os.path.relpath(path, ROOT)}` — one `python bench.py` invocation ({j['steps']} steps, {j['warmup']} warm-up; the driver's own run is `BENCH_r06.json`).")
+out.append(f"Source: `{os.path.relpath(path, ROOT)}` — one `python bench.py --full` invocation ({j['steps']} steps, {j['warmup']} warm-up; the driver's own run is `BENCH_r06.json`).")
 out.append("")
 out.append("| leg (same invocation) | index | reads | Mbp/s | `frac` | other fractions | work per read |")
 out.append("|---|---|---|---|---|---|---|")

@@ -24,7 +24,7 @@ def _free_port():
 
 
 def _run(n, extra, dump):
-    common = ["bench.py", "--gpus", str(n), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--batches", "2",
+    common = ["bench.py", "--gpus", str(n), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--batches", "2", "--full",
               "--traffic", "none", "--no-cpu-baseline", "--no-unpruned", "--no-ceiling", "--sustained-reads", "8192",
               "--dump-results", str(dump)] + extra
     env = dict(os.environ, TAXOR_BENCH_BACKEND="gloo", TAXOR_BENCH_SAME_GPU="1", MASTER_ADDR="127.0.0.1")
@@ -110,7 +110,7 @@ def test_bench_line_says_what_the_workload_is_and_carries_the_layout_legs():
     """the line states the headline's strand mix and child width (config.frac_reverse, child_bins, layout_note) and measures, in the
     same invocation, strand-mixed reads (SURVEY 8(d) as written), chopper-shaped children (as wide as the root: one t_max at every
     level, taxor_build.cpp:168-187,473) and a 4096-bin root"""
-    cmd = [sys.executable, "bench.py", "--workload", "viral", "--reads", "8192", "--steps", "2", "--warmup", "1", "--batches", "2", "--traffic", "none",
+    cmd = [sys.executable, "bench.py", "--workload", "viral", "--reads", "8192", "--steps", "2", "--warmup", "1", "--batches", "2", "--full", "--traffic", "none",
            "--no-ceiling", "--no-unpruned", "--no-e04", "--no-dropin", "--no-cpu-baseline"]
     cp = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert cp.returncode == 0, cp.stderr[-3000:]
@@ -144,7 +144,7 @@ def test_bench_tracks_indexes_built_without_syncmers(mode, tmp_path):
     """bench.py --mode kmer|minimiser: the reference's default build mode gets the same line -- value, roofline
     object, unpruned pass, and the oracle re-check of the sample (bench.py exits with PARITY FAILURE otherwise)"""
     cmd = [sys.executable, "bench.py", "--mode", mode, "--reads", "4096", "--read-len", "2000", "--genomes", "8", "--genome-len", "30000",
-           "--steps", "2", "--warmup", "1", "--batches", "2", "--traffic", "none", "--no-ceiling", "--sustained-reads", "8192", "--cpu-seconds", "2"]
+           "--steps", "2", "--warmup", "1", "--batches", "2", "--full", "--traffic", "none", "--no-ceiling", "--sustained-reads", "8192", "--cpu-seconds", "2"]
     cp = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert cp.returncode == 0, cp.stderr[-3000:]
     j = json.loads([l for l in cp.stdout.splitlines() if l.startswith("{")][0])
@@ -166,7 +166,7 @@ def test_forced_single_rank_rccl_run_equals_the_plain_run(tmp_path):
     import torch
     if torch.cuda.mem_get_info(0)[0] < 160e9:
         pytest.skip("needs 160 GB of free HBM")
-    common = ["bench.py", "--gpus", "1", "--workload", "gtdb", "--steps", "8", "--warmup", "2", "--batches", "2",
+    common = ["bench.py", "--gpus", "1", "--workload", "gtdb", "--steps", "8", "--warmup", "2", "--batches", "2", "--full",
               "--traffic", "none", "--no-cpu-baseline", "--no-unpruned", "--no-ceiling", "--no-e04", "--no-layouts", "--sustained-reads", "2000000"]
     # (GPU_MAX_HW_QUEUES: conftest.py exports 8 for the test session; bench.py must choose for itself like under the driver -- 8 for the
     # plain run, 24 for a rank of a distributed one, whose torch / RCCL streams would otherwise push the searchers' streams onto shared queues)
@@ -216,7 +216,7 @@ def test_build_mode_line():
     """bench.py --mode build: one whole hierarchy build per step; the line carries insertions/s, the bytes and read-modify-writes an
     insertion costs, and the reference's own builder timed beside it"""
     cmd = [sys.executable, "bench.py", "--mode", "build", "--build-children", "6", "--build-child-bins", "64", "--build-keys-per-bin", "60000",
-           "--steps", "2", "--warmup", "1"]
+           "--steps", "2", "--warmup", "1", "--full"]
     cp = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert cp.returncode == 0, cp.stderr[-3000:]
     lines = [l for l in cp.stdout.splitlines() if l.startswith("{")]
@@ -238,3 +238,34 @@ def test_build_mode_line():
     assert j["value_host_fed"] == pi["value"] > 1e8 and 0 < pi["seconds_upload"] < pi["seconds_total"] and pi["upload_GBps"] > 1
     cb = j["cpu_baseline"]
     assert cb["kind"] == "reference" and cb["cores"] == 1 and 1e6 < cb["value"] < j["value"]
+
+
+def test_plain_run_times_the_steps_and_dumps_its_outputs(tmp_path):
+    """without --full the line is the headline alone -- --steps timed steps, ms_per_step -- and --dump-outputs writes the last step's CSR
+    as float64 .npy files; two runs with the same arguments compute the same outputs, and they are the CSR --dump-results writes"""
+    def run(tag):
+        d = tmp_path / tag
+        cmd = [sys.executable, "bench.py", "--workload", "tiny", "--steps", "3", "--warmup", "1", "--batches", "2",
+               "--dump-outputs", str(d), "--dump-results", str(tmp_path / f"{tag}.npz")]
+        cp = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert cp.returncode == 0, cp.stderr[-3000:]
+        lines = [l for l in cp.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, cp.stdout
+        return json.loads(lines[0]), d, np.load(tmp_path / f"{tag}.npz")
+
+    j, d, npz = run("a")
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert j["unit"] == "Mbp/s" and j["higher_is_better"] is True and j["dtype"] == "u8" and j["metric"].startswith("Mbp/s classified")
+    for moved in ("cpu_baseline", "layouts", "sustained", "pcie_inclusive", "value_e04", "read_error_0.04"):
+        assert moved not in j, moved
+    assert "unpruned" not in j["roofline"] and "gather_ceiling" not in j["roofline"] and j["roofline"]["traffic"] is None
+    names = ("read_index", "read_off", "user_bin", "count", "n_hashes")
+    out = {n: np.load(d / f"{n}.npy") for n in names}
+    assert all(a.dtype == np.float64 for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert np.array_equal(out["read_index"], np.arange(npz["n_hashes"].size))          # a tiny run is written whole
+    for n in ("read_off", "user_bin", "count", "n_hashes"):
+        assert np.array_equal(out[n], npz[n].astype(np.float64)), n
+    assert out["user_bin"].size > 0
+    _, d2, _ = run("b")
+    for n in names:
+        assert np.array_equal(out[n], np.load(d2 / f"{n}.npy")), n
