@@ -87,6 +87,45 @@ def ref_lib(reference_root="/root/reference"):
     return _ref
 
 
+_REF_SYNC_SO = os.path.join(_HERE, "_ref", "libtaxor_ref_syncmer.so")
+_REF_SYNC_SRC = ("ref_syncmer_driver.cpp", "ref_standin/ankerl/unordered_dense.h", "ref_standin/seqan3/alphabet/nucleotide/all.hpp")
+_ref_sync = None
+
+
+def ref_syncmer_lib(reference_root="/root/reference"):
+    """oracle/_ref/libtaxor_ref_syncmer.so: the REFERENCE's syncmer selector (src/hashing/syncmer.cpp, compiled where it lies)
+    against the stand-ins of oracle/ref_standin/, whose hash is the identity -- it returns the selected canonical k-mers, not
+    their wyhash.  Rebuilt like ref_lib() when the reference is present and the driver or a stand-in is newer; None if neither
+    the reference nor a prebuilt file is available."""
+    global _ref_sync
+    if _ref_sync is not None:
+        return _ref_sync
+    srcs = [os.path.join(_HERE, f) for f in _REF_SYNC_SRC]
+    if os.path.isdir(os.path.join(reference_root, "src")) and (
+            not os.path.exists(_REF_SYNC_SO) or any(os.path.getmtime(f) > os.path.getmtime(_REF_SYNC_SO) for f in srcs)):
+        subprocess.check_call(["make", "-C", _HERE, "-s", "-B", "_ref/libtaxor_ref_syncmer.so", f"REF={reference_root}"])
+    if not os.path.exists(_REF_SYNC_SO):
+        return None
+    L = C.CDLL(_REF_SYNC_SO)
+    L.ref_seq_to_syncmers.restype = C.c_size_t
+    L.ref_seq_to_syncmers.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    _ref_sync = L
+    return _ref_sync
+
+
+def ref_seq_to_syncmers(seq: bytes, k, s, t):
+    """the reference's selection for one read: distinct canonical k-mers in first-insertion order (uint64), or None where
+    the library is absent.  orc.seq_to_syncmers(seq, k, s, t) is wyhash of these, value for value, for k <= 31."""
+    L = ref_syncmer_lib()
+    if L is None:
+        return None
+    cap = max(len(seq), 1)
+    out = np.empty(cap, dtype=np.uint64)
+    n = L.ref_seq_to_syncmers(seq, len(seq), k, s, t, _p(out), cap)
+    assert n <= cap
+    return out[:n].copy()
+
+
 class _Ixf(C.Structure):
     _fields_ = [("bins", C.c_uint64), ("stride", C.c_uint64), ("seg_len", C.c_uint64),
                 ("seed", C.c_uint64), ("data", C.c_void_p), ("arith", C.c_uint32)]

@@ -11,8 +11,9 @@
 //   * src/main/xorfilter.hpp + hashutil.hpp  the in-repo XOR-filter prototype: NOT linked into the reference's search
 //     (which uses the un-vendored seqan3::interleaved_xor_filter) but the evidence the IXF restatement rests on --
 //     murmur64(key + seed), rotl64 by 21*i, multiply-shift reduction, 8-bit fingerprint, 32 + 1.23 n slots.
-// Everything else on the path (syncmer.cpp, hierarchical_interleaved_xor_filter.hpp, threshold.hpp, taxor_search.cpp)
-// includes the absent third-party headers and cannot be built here.
+// Everything else on the path (hierarchical_interleaved_xor_filter.hpp, threshold.hpp, taxor_search.cpp) includes the absent
+// third-party headers and cannot be built here; syncmer.cpp is built against stand-ins into a library of its own
+// (ref_syncmer_driver.cpp).
 #include <climits>
 #include <cstddef>
 #include <cstdint>

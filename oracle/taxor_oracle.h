@@ -8,12 +8,26 @@
  *
  * PINNING STATUS
  *   The reference has no tests, golden vectors or fixtures, and its search path cannot be
- *   built in this image: syncmer.cpp, hierarchical_interleaved_xor_filter.hpp, threshold.hpp and taxor_search.cpp
- *   include seqan3 / cereal / ankerl headers that are fetched by git at configure time and are absent here
+ *   built in this image: hierarchical_interleaved_xor_filter.hpp, threshold.hpp and taxor_search.cpp include
+ *   seqan3 / cereal / ankerl headers that are fetched by git at configure time and are absent here
  *   (src/seqan/CMakeLists.txt.in:7-62, src/hashing/CMakeLists.txt.in:6-15); building them against hand-written
- *   stand-ins would not be a reference build.
+ *   stand-ins would not be a reference build.  syncmer.cpp is the exception: it takes only a hash call, a set and
+ *   dna5::to_char() from those headers, and its selection logic is plain C++ (below).
  *   PINNED against the reference's own code (oracle/_ref/libtaxor_ref.so, built by `make ref` straight from the
  *   reference's files that need nothing but the standard library; tests/test_oracle_ref.py):
+ *     - orc_seq_to_syncmers's SELECTOR                 = src/hashing/syncmer.cpp itself (oracle/_ref/libtaxor_ref_syncmer.so:
+ *                                                        compiled where it lies with the reference's flags against the
+ *                                                        stand-ins of oracle/ref_standin/ -- identity hash, insertion-ordered
+ *                                                        set, dna5::to_char -- driven by oracle/ref_syncmer_driver.cpp):
+ *                                                        positions, tie rule, N reset and canonical k-mer, every admitted
+ *                                                        (k, s) and t in {1, 2, w/2, ceil(w/2), w-1, w, w+1}, for k <= 31
+ *                                                        (tests/test_syncmer_ref_cpu.py, tests/golden/ref_syncmers.npz).
+ *                                                        The wyhash, the set's iteration order and the dna5 conversion stay
+ *                                                        unpinned stand-ins.  k = 32 is a documented DIVERGENCE: the
+ *                                                        reference's kmask = (1ULL << 2*k) - 1 (syncmer.cpp:86) shifts by 64,
+ *                                                        compiles to 0 and selects only the k-mer 0; its own `taxor build`
+ *                                                        refuses syncmer indexes with k > 30 (taxor_build.cpp:124-127).  The
+ *                                                        oracle and the product keep the full-mask reading.
  *     - orc_syncmer_match_ratio / orc_threshold        = src/hixf/search/syncmer_model.hpp, every (k, error rate)
  *     - orc_nmut_kmer_ci_high, orc_containment_index_ci_low, orc_normal_cdf_inverse (and so orc_threshold_model)
  *                                                      = kmer_model.cpp, fracminhash_model.cpp, gaussian_inverse.cpp,
@@ -32,7 +46,7 @@
  *     (3) orc_minimiser_hash -- restates seqan3::views::minimiser_hash (same un-vendored fork), used for
  *         indexes built without --use-syncmer; call sites src/main/taxor_search.cpp:210-212,241-256.
  *         Window > k: which of several equal minima is kept is recalled, not read.   parity unpinned
- *   Everything else (syncmer selector, HIXF traversal/tally, classification call, TSV) is restated from code
+ *   Everything else (HIXF traversal/tally, classification call, TSV) is restated from code
  *   that IS in /root/reference and is cross-checked against a second, independent pure-Python restatement
  *   (tests/golden/make_golden.py) whose outputs are committed under tests/golden/.
  */

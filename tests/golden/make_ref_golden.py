@@ -3,7 +3,10 @@
 so that those tests hold the oracle and the product's host functions against the reference on any machine, also where the
 reference's sources are absent.  The values come from oracle/_ref/libtaxor_ref.so (`make -C oracle ref REF=<reference checkout>`,
 see oracle/ref_driver.cpp); nothing of the reference's sources is stored, only its answers.
-Run:  python tests/golden/make_ref_golden.py          (needs oracle/_ref/libtaxor_ref.so)"""
+It also writes tests/golden/ref_syncmers.npz: the reference's own syncmer selector (src/hashing/syncmer.cpp, built against the
+stand-ins of oracle/ref_standin/ into oracle/_ref/libtaxor_ref_syncmer.so; its hash is the identity, so it returns the selected
+canonical k-mers) over a stored read set at every admitted (k, s) and t in sync_ts(k, s).  Read by tests/test_syncmer_ref_cpu.py.
+Run:  python tests/golden/make_ref_golden.py          (needs both libraries; `... syncmers` writes ref_syncmers.npz alone)"""
 import ctypes as C
 import os
 import sys
@@ -48,7 +51,103 @@ def digest(*arrays):
     return h.hexdigest()
 
 
+# ---- ref_syncmers.npz ---------------------------------------------------------------------------------------------------------
+def sync_domain():
+    """every (k, s) taxor_gpu_index_create admits for a syncmer index: 2 <= k <= 32, 1 <= s <= 16, s < k, w = k-s+1 <= 32"""
+    return [(k, s) for k in range(2, 33) for s in range(1, 17) if s < k and k - s + 1 <= 32]
+
+
+def sync_ts(k, s):
+    """t in {1, 2, w//2 (the build default, taxor_build.cpp:510), ceil(w/2), w-1, w, w+1}, distinct and >= 1"""
+    w = k - s + 1
+    return sorted({t for t in (1, 2, w // 2, (w + 1) // 2, w - 1, w, w + 1) if t >= 1})
+
+
+# configurations whose full vectors are stored, so that a failure there names the read and the position
+SYNC_DIAG = ((22, 12, 5), (5, 1, 2), (9, 3, 4), (16, 8, 1), (27, 11, 17), (31, 16, 16), (32, 16, 8))
+
+
+def sync_reads():
+    """the stored read set: every length 1..33 (shorter than k, k, k+1 for every k), random reads up to a few kb, homopolymers,
+    (AT)n, TTAGGG repeats, low-complexity mixes, and reads with N, IUPAC codes, lower case and U"""
+    rng = np.random.default_rng(20261016)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    rnd = lambda n: bytes(rng.choice(acgt, size=int(n)))
+    reads = [rnd(n) for n in range(1, 34)]
+    reads += [rnd(n) for n in (63, 64, 65, 100, 257, 511, 1000, 2048, 3001, 4100)]
+    reads += [b"A" * 300, b"C" * 77, b"AT" * 200, b"TTAGGG" * 150, b"CCCTAA" * 40 + b"TTAGGG" * 40, b"ACGTTGCA" * 80,
+              b"AAAAAAAAAAAAAAAAAAAAAAAAAAAAAAAAAAAAAAAAC" * 12]
+    for _ in range(4):                                     # low-complexity mixes: random runs, homopolymers, short repeat units
+        parts, tot, n = [], 0, int(rng.integers(800, 1600))
+        while tot < n:
+            c = rng.random()
+            if c < 0.3:
+                p = rnd(rng.integers(3, 60))
+            elif c < 0.6:
+                p = bytes([int(rng.choice(acgt))]) * int(rng.integers(5, 90))
+            else:
+                p = rnd(rng.integers(2, 7)) * int(rng.integers(3, 40))
+            parts.append(p)
+            tot += len(p)
+        reads.append(b"".join(parts)[:n])
+    for frac, alphabet in ((0.01, b"N"), (0.05, b"N"), (0.02, b"NRYKMSWBDHV"), (0.03, b"acgtuUn")):
+        r = bytearray(rnd(1500))
+        for p in rng.integers(0, len(r), size=max(1, int(len(r) * frac))):
+            r[int(p)] = int(rng.choice(np.frombuffer(alphabet, np.uint8)))
+        reads.append(bytes(r))
+    reads += [b"ACGTACGTAC" + b"N" * 40 + b"ACGT" * 30, b"N" * 50, b"ACGT" * 8 + b"NN" + b"ACGT" * 8 + b"N" + b"TTAGGG" * 20]
+    return reads
+
+
+def sync_digest(values):
+    import hashlib
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(values, dtype=np.uint64).tobytes()).digest(), np.uint8)
+
+
+def wyhash_np(x):
+    """orc_wyhash_u64 over a uint64 array (lo64 ^ hi64 of x * 0x9E3779B97F4A7C15), checked against the oracle below"""
+    x = np.asarray(x, dtype=np.uint64)
+    m32, c = np.uint64(0xFFFFFFFF), np.uint64(0x9E3779B97F4A7C15)
+    s32 = np.uint64(32)
+    a_lo, a_hi, b_lo, b_hi = x & m32, x >> s32, c & m32, c >> s32
+    ll, lh, hl, hh = a_lo * b_lo, a_lo * b_hi, a_hi * b_lo, a_hi * b_hi
+    mid = (ll >> s32) + (lh & m32) + (hl & m32)
+    lo = (ll & m32) | (mid << s32)
+    hi = hh + (lh >> s32) + (hl >> s32) + (mid >> s32)
+    return lo ^ hi
+
+
+def write_syncmers():
+    if orc.ref_syncmer_lib() is None:
+        raise SystemExit("oracle/_ref/libtaxor_ref_syncmer.so is not built (make -C oracle ref REF=<reference checkout>)")
+    probe = np.random.default_rng(1).integers(0, 2**64, size=1000, dtype=np.uint64)
+    assert wyhash_np(probe).tolist() == [orc.wyhash(int(v)) for v in probe]
+    reads = sync_reads()
+    offs = np.cumsum([0] + [len(r) for r in reads]).astype(np.uint32)
+    cfg = np.array([(k, s, t) for k, s in sync_domain() for t in sync_ts(k, s)], dtype=np.uint8)
+    counts = np.zeros((len(cfg), len(reads)), np.uint16)
+    sha_kmer = np.zeros((len(cfg), 32), np.uint8)
+    sha_hash = np.zeros((len(cfg), 32), np.uint8)
+    g = {}
+    for c, (k, s, t) in enumerate(cfg.tolist()):
+        vals = [orc.ref_seq_to_syncmers(r, k, s, t) for r in reads]
+        counts[c] = [v.size for v in vals]
+        allv = np.concatenate(vals)
+        sha_kmer[c] = sync_digest(allv)
+        sha_hash[c] = sync_digest(wyhash_np(allv))
+        if (k, s, t) in SYNC_DIAG:
+            g[f"diag_{k}_{s}_{t}"] = allv
+    g.update(bases=np.frombuffer(b"".join(reads), np.uint8), offsets=offs, cfg=cfg, counts=counts, sha_kmer=sha_kmer,
+             sha_hash=sha_hash, diag=np.array(SYNC_DIAG, np.uint8))
+    path = os.path.join(HERE, "ref_syncmers.npz")
+    np.savez_compressed(path, **g)
+    print(f"{path}: {len(cfg)} configurations x {len(reads)} reads ({offs[-1]} bases), {os.path.getsize(path)} bytes")
+
+
 def main():
+    if sys.argv[1:] == ["syncmers"]:
+        return write_syncmers()
+    write_syncmers()
     R = orc.ref_lib()
     if R is None:
         raise SystemExit("oracle/_ref/libtaxor_ref.so is not built (make -C oracle ref REF=<reference checkout>)")
