@@ -106,6 +106,66 @@ void taxor_gpu_free(void *p);
 int taxor_gpu_memcpy_to_host(void *dst, const void *d_src, uint64_t bytes);
 int taxor_gpu_memcpy_from_host(void *d_dst, const void *src, uint64_t bytes);
 
+/* ---- `taxor build`: the key sets of whole reference genomes, on the device (taxor_amd/csrc/genome_keys.hip; the reference hashes
+ * each genome file on a CPU thread, src/main/compute_hashes.cpp:50-142).  An accumulator: records arrive in any number of calls,
+ * a user bin's records may span calls; _finish returns per user bin its DISTINCT keys, FracMinHash-filtered, sorted ascending:
+ *   syncmers   union over the bin's records of hashing::seq_to_syncmers(k, record, s, t) (wyhash of canonical k-mers)
+ *   minimisers union over its records of minimiser_hash(k, window_size, adjust_seed(k))
+ *   scaling>1  only keys with double(wyhash(key)) <= double(UINT64_MAX) / scaling
+ * Records are ASCII (any dna15 character; the dna4 mapping is applied on the device), at most 2^31 - 1 bases each. */
+typedef struct {
+    uint32_t kmer_size, syncmer_size, t_syncmer;
+    uint32_t use_syncmer;     /* 1 = open canonical syncmers, 0 = minimisers over window_size */
+    uint64_t window_size;     /* minimiser mode: in [k, k+511] */
+    uint32_t scaling;         /* > 1 = FracMinHash down-sampling */
+    uint32_t reserved;
+    uint64_t n_bins;          /* user bins; rec_bin values lie below it */
+} taxor_keyer_params;
+typedef struct {
+    uint64_t calls, records, bases, tiles;
+    uint64_t call_keys;       /* distinct keys summed over calls (a bin spread over calls counts in each) */
+    uint64_t keys;            /* distinct keys after _finish */
+    double seconds_device;    /* HIP-event time of packing, selection and set insertion, summed over calls */
+    double seconds_add;       /* wall time inside _add (copies and per-call compaction included) */
+    double seconds_finish;    /* wall time of _finish's gather, sort and merge */
+} taxor_keyer_stats;
+typedef struct taxor_gpu_keyer taxor_gpu_keyer;
+int taxor_gpu_keyer_create(int device, const taxor_keyer_params *params, taxor_gpu_keyer **out);
+/* records r < n_records: bases[rec_off[r] .. rec_off[r+1]) of user bin rec_bin[r] */
+int taxor_gpu_keyer_add(taxor_gpu_keyer *kr, const char *bases, const uint64_t *rec_off, const uint32_t *rec_bin, uint64_t n_records);
+/* CSR: keys of bin b at [bin_off[b], bin_off[b+1]), n_bins + 1 entries; *keys in host memory (may be NULL: not copied), *d_keys
+ * the same on the keyer's device.  Valid until _destroy; no _add after _finish. */
+int taxor_gpu_keyer_finish(taxor_gpu_keyer *kr, const uint64_t **bin_off, const uint64_t **keys, const uint64_t **d_keys);
+/* exact number of distinct keys in the union of the listed user bins (a merged bin's key count), with KeyUnion's device set */
+int taxor_gpu_keyer_union_size(taxor_gpu_keyer *kr, const uint32_t *bins, uint64_t n, uint64_t *out);
+/* a new device array holding the finished keys' ranges [first[i], first[i] + count[i]) one after the other (the technical bins'
+ * key lists in index order for taxor_gpu_index_build_hixf_ex); owned by the keyer, replaced by the next call */
+int taxor_gpu_keyer_arrange(taxor_gpu_keyer *kr, const uint64_t *first, const uint64_t *count, uint64_t n_ranges, const uint64_t **d_out);
+int taxor_gpu_keyer_stats(const taxor_gpu_keyer *kr, taxor_keyer_stats *out);
+void taxor_gpu_keyer_destroy(taxor_gpu_keyer *kr);
+/* free and total bytes of a device's memory */
+int taxor_gpu_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes);
+/* The IXF tree of a build (host only; taxor_amd/csrc/host_util.cpp, DESIGN.md "taxor build"): from the distinct key count of every
+ * user bin and t_max (0 = the candidates 64, 128, ..., 4096 and next_multiple_of_64(ceil(sqrt(n))) of taxor_build.cpp:173-187, the
+ * one with the fewest expected fingerprint bytes gathered per query hash, then the fewest index bytes).  Every user bin is one run
+ * of consecutive technical bins of one IXF (part j of parts of its sorted keys: [n*j/parts, n*(j+1)/parts)), no IXF has more than
+ * t_max bins.  IXF 0 is the root; bins in index order: all of IXF 0, then IXF 1, ... */
+typedef struct {
+    uint64_t n_ixf, n_bins_total, t_max;
+    uint32_t depth, reserved;
+    double bytes_per_hash;      /* expected fingerprint bytes gathered per query hash (3 x stride along a user bin's path, weighted
+                                   by the bins' key counts) */
+    double index_bytes;         /* fingerprint bytes, merged bins counted as the sum of their children */
+    const uint64_t *ixf_bins;   /* [n_ixf] */
+    const uint64_t *bin_first;  /* [n_ixf + 1]: IXF i's bins are [bin_first[i], bin_first[i+1]) of the arrays below */
+    const int64_t *next_ixf;    /* [n_bins_total] child IXF of a merged bin, the own IXF for a leaf */
+    const int64_t *fname_idx;   /* [n_bins_total] user bin of a leaf, -1 = merged */
+    const uint64_t *part;       /* [n_bins_total] leaf: which part of its user bin */
+    const uint64_t *parts;      /* [n_bins_total] leaf: parts of its user bin; merged: 0 */
+} taxor_layout;
+int taxor_build_layout(const uint64_t *counts, uint64_t n, uint64_t t_max, taxor_layout **out);
+void taxor_layout_free(taxor_layout *l);
+
 /* ---- taxor_gpu_search_batch split into its three phases so that a caller can keep a batch resident in HBM
  * (upload once, run many times) and overlap transfers with compute:
  *   upload : H2D of the ASCII bases + on-device dna4 mapping and 2-bit packing

@@ -114,6 +114,23 @@ class BuildStats(C.Structure):
                 ("seconds_alloc", C.c_double), ("keys_counted_in_lds", C.c_uint64)]
 
 
+class KeyerParams(C.Structure):
+    _fields_ = [("kmer_size", C.c_uint32), ("syncmer_size", C.c_uint32), ("t_syncmer", C.c_uint32), ("use_syncmer", C.c_uint32),
+                ("window_size", C.c_uint64), ("scaling", C.c_uint32), ("reserved", C.c_uint32), ("n_bins", C.c_uint64)]
+
+
+class KeyerStats(C.Structure):
+    _fields_ = [("calls", C.c_uint64), ("records", C.c_uint64), ("bases", C.c_uint64), ("tiles", C.c_uint64), ("call_keys", C.c_uint64),
+                ("keys", C.c_uint64), ("seconds_device", C.c_double), ("seconds_add", C.c_double), ("seconds_finish", C.c_double)]
+
+
+class Layout(C.Structure):
+    _fields_ = [("n_ixf", C.c_uint64), ("n_bins_total", C.c_uint64), ("t_max", C.c_uint64), ("depth", C.c_uint32), ("reserved", C.c_uint32),
+                ("bytes_per_hash", C.c_double), ("index_bytes", C.c_double), ("ixf_bins", C.POINTER(C.c_uint64)),
+                ("bin_first", C.POINTER(C.c_uint64)), ("next_ixf", C.POINTER(C.c_int64)), ("fname_idx", C.POINTER(C.c_int64)),
+                ("part", C.POINTER(C.c_uint64)), ("parts", C.POINTER(C.c_uint64))]
+
+
 SIGNATURES = {
     "taxor_gpu_last_error": (C.c_char_p, []),
     "taxor_gpu_index_create": (C.c_int, [C.POINTER(HixfView), C.c_int, C.POINTER(_P)]),
@@ -122,6 +139,16 @@ SIGNATURES = {
     "taxor_gpu_index_build_ixf_ex": (C.c_int, [_P, C.c_uint64, _P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(BuildStats)]),
     "taxor_gpu_index_build_hixf_ex": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, C.POINTER(BuildStats)]),
     "taxor_gpu_index_build_hixf_gen": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(BuildStats)]),
+    "taxor_gpu_keyer_create": (C.c_int, [C.c_int, C.POINTER(KeyerParams), C.POINTER(_P)]),
+    "taxor_gpu_keyer_add": (C.c_int, [_P, _P, _P, _P, C.c_uint64]),
+    "taxor_gpu_keyer_finish": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint64))]),
+    "taxor_gpu_keyer_union_size": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "taxor_gpu_keyer_arrange": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.POINTER(C.c_uint64))]),
+    "taxor_gpu_keyer_stats": (C.c_int, [_P, C.POINTER(KeyerStats)]),
+    "taxor_gpu_keyer_destroy": (None, [_P]),
+    "taxor_gpu_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "taxor_build_layout": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(Layout))]),
+    "taxor_layout_free": (None, [C.POINTER(Layout)]),
     "taxor_synth_key": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "taxor_gpu_synth_keys": (C.c_int, [C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint64]),
     "taxor_gpu_malloc": (C.c_int, [C.c_int, C.c_uint64, C.POINTER(_P)]),

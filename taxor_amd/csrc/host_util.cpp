@@ -3,8 +3,11 @@
 #include "../../include/taxor_gpu_tools.h"
 #include "ixf_arith.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <queue>
+#include <set>
 #include <thread>
 #include <vector>
 
@@ -294,6 +297,223 @@ int taxor_synth_reads(const char *genomes, const uint64_t *genome_off, uint64_t 
     for (auto &th : pool) th.join();
     offsets[n_reads] = n_reads * (uint64_t)read_len;
     return 0;
+}
+
+} // extern "C"
+
+// ---- the IXF tree of `taxor build` (DESIGN.md "taxor build: the layout").  The reference asks chopper (HyperLogLog counts,
+// hierarchical binning; taxor_build.cpp:428-492), which is not vendored; this is a simpler rule over EXACT counts:
+//   n <= t_max user bins: one IXF of leaves.  It gets min(t_max, next multiple of 64 of n) bins -- bins up to the row's 64-byte
+//     multiple cost a query nothing -- and a user bin larger than twice the mean is split (largest per part first) while bins are
+//     left, so the IXF's seg_len, which follows its largest bin, shrinks.
+//   n > t_max: user bins of at least total / t_max keys stay leaves (split into floor(count / (total / t_max)) parts), the rest,
+//     in descending count order, are cut into the remaining bins as contiguous groups of about equal weight; a group of one is a
+//     leaf, a larger group a merged bin whose child IXF is laid out the same way.
+// Deterministic: ties break on the user bin's index.
+namespace {
+
+struct LayIxf {
+    std::vector<int64_t> next, fname;
+    std::vector<uint64_t> part, parts;
+    std::vector<uint64_t> weight;   // keys of each bin (merged: sum of the children's)
+};
+
+struct LayBuild {
+    const uint64_t *cnt;
+    uint64_t T;
+    std::vector<LayIxf> ixfs;
+    std::vector<uint32_t> level;
+
+    static uint64_t r64(uint64_t x) { return (x + 63) / 64 * 64; }
+
+    // leaves (user bin, parts) and the greedy split of the largest per-part bins into `budget` bins, down to `thr`
+    void split(std::vector<std::pair<uint32_t, uint64_t>> &lv, uint64_t budget, double thr)
+    {
+        uint64_t used = 0;
+        for (auto &x : lv) used += x.second;
+        auto per = [&](size_t i) { return (double)cnt[lv[i].first] / (double)lv[i].second; };
+        auto less = [&](size_t a, size_t b) { return per(a) < per(b) || (per(a) == per(b) && lv[a].first > lv[b].first); };
+        std::priority_queue<size_t, std::vector<size_t>, decltype(less)> pq(less);
+        for (size_t i = 0; i < lv.size(); ++i) pq.push(i);
+        while (used < budget && !pq.empty()) {
+            const size_t i = pq.top();
+            if (per(i) <= thr || lv[i].second + 1 > cnt[lv[i].first]) break;
+            pq.pop();
+            ++lv[i].second;
+            ++used;
+            pq.push(i);
+        }
+    }
+
+    uint32_t make(std::vector<uint32_t> S, uint32_t lvl)
+    {
+        std::sort(S.begin(), S.end(), [&](uint32_t a, uint32_t b) { return cnt[a] > cnt[b] || (cnt[a] == cnt[b] && a < b); });
+        const uint32_t id = (uint32_t)ixfs.size();
+        ixfs.emplace_back();
+        level.push_back(lvl);
+        const uint64_t n = S.size();
+        double total = 0;
+        for (uint32_t u : S) total += (double)cnt[u];
+        std::vector<std::pair<uint32_t, uint64_t>> lv;
+        std::vector<std::vector<uint32_t>> groups;
+        if (n <= T) {
+            for (uint32_t u : S) lv.push_back({u, 1});
+            split(lv, std::min(T, r64(n)), 2.0 * total / (double)n);
+        } else {
+            const double target = total / (double)T;
+            uint64_t d = 0, sum_p = 0;
+            while (d < n && (double)cnt[S[d]] >= target && target > 0) {
+                const uint64_t p = std::max<uint64_t>(1, std::min<uint64_t>(cnt[S[d]], (uint64_t)((double)cnt[S[d]] / target)));
+                lv.push_back({S[d], p});
+                sum_p += p;
+                ++d;
+            }
+            while (sum_p + 1 > T) {                       // keep at least one bin for the rest
+                auto it = std::max_element(lv.begin(), lv.end(), [](const auto &a, const auto &b) { return a.second < b.second; });
+                if (it->second > 1) { --it->second; --sum_p; }
+                else { sum_p -= lv.back().second; lv.pop_back(); --d; }
+            }
+            const uint64_t M = T - sum_p;                  // bins for the S[d..n) (n - d > M: there are more of them than bins)
+            double rest = 0;
+            for (uint64_t i = d; i < n; ++i) rest += (double)cnt[S[i]];
+            uint64_t i = d;
+            for (uint64_t g = 0; g < M; ++g) {
+                const uint64_t left_groups = M - g;
+                const double want = rest / (double)left_groups;
+                std::vector<uint32_t> grp;
+                double wsum = 0;
+                // at least one member; more while the group is light and every later group still gets one
+                while (i < n && (grp.empty() || g + 1 == M || (wsum < want && n - i > left_groups - 1))) {
+                    grp.push_back(S[i]);
+                    wsum += (double)cnt[S[i]];
+                    ++i;
+                }
+                rest -= wsum;
+                if (grp.size() == 1) lv.push_back({grp[0], 1});
+                else groups.push_back(std::move(grp));
+            }
+        }
+        for (const auto &x : lv)
+            for (uint64_t j = 0; j < x.second; ++j) {
+                LayIxf &f = ixfs[id];
+                f.next.push_back(id);
+                f.fname.push_back(x.first);
+                f.part.push_back(j);
+                f.parts.push_back(x.second);
+                f.weight.push_back(cnt[x.first] * (j + 1) / x.second - cnt[x.first] * j / x.second);
+            }
+        for (const auto &grp : groups) {
+            const size_t b = ixfs[id].next.size();
+            uint64_t w = 0;
+            for (uint32_t u : grp) w += cnt[u];
+            ixfs[id].next.push_back(-1);
+            ixfs[id].fname.push_back(-1);
+            ixfs[id].part.push_back(0);
+            ixfs[id].parts.push_back(0);
+            ixfs[id].weight.push_back(w);
+            const uint32_t child = make(grp, lvl + 1);
+            ixfs[id].next[b] = child;
+        }
+        return id;
+    }
+};
+
+struct LayoutOwned {
+    taxor_layout pub{};
+    std::vector<uint64_t> ixf_bins, bin_first, part, parts;
+    std::vector<int64_t> next, fname;
+};
+
+LayoutOwned *layout_for(const uint64_t *counts, uint64_t n, uint64_t T)
+{
+    LayBuild lb;
+    lb.cnt = counts;
+    lb.T = T;
+    std::vector<uint32_t> all(n);
+    for (uint64_t i = 0; i < n; ++i) all[i] = (uint32_t)i;
+    lb.make(all, 0);
+    auto *L = new LayoutOwned();
+    const uint64_t m = lb.ixfs.size();
+    L->bin_first.push_back(0);
+    std::vector<double> stride3(m);
+    double idx_bytes = 0, total = 0;
+    uint32_t depth = 0;
+    for (uint64_t i = 0; i < m; ++i) {
+        const LayIxf &f = lb.ixfs[i];
+        L->ixf_bins.push_back(f.next.size());
+        L->bin_first.push_back(L->bin_first.back() + f.next.size());
+        L->next.insert(L->next.end(), f.next.begin(), f.next.end());
+        L->fname.insert(L->fname.end(), f.fname.begin(), f.fname.end());
+        L->part.insert(L->part.end(), f.part.begin(), f.part.end());
+        L->parts.insert(L->parts.end(), f.parts.begin(), f.parts.end());
+        stride3[i] = 3.0 * (double)LayBuild::r64(f.next.size());
+        const uint64_t mx = f.weight.empty() ? 1 : std::max<uint64_t>(1, *std::max_element(f.weight.begin(), f.weight.end()));
+        idx_bytes += (double)taxor_ixf_seg_len(mx) * stride3[i];
+        depth = std::max(depth, lb.level[i] + 1);
+    }
+    // expected bytes per query hash: a key of user bin u is looked up in every IXF on u's path (weight: u's keys)
+    std::vector<double> path(m, 0.0);
+    std::vector<int64_t> parent(m, -1);
+    for (uint64_t i = 0; i < m; ++i)
+        for (const int64_t c : lb.ixfs[i].next)
+            if (c >= 0 && (uint64_t)c != i) parent[c] = (int64_t)i;
+    for (uint64_t i = 0; i < m; ++i) path[i] = stride3[i] + (parent[i] >= 0 ? path[parent[i]] : 0.0);   // parents come first
+    double cost = 0;
+    for (uint64_t i = 0; i < m; ++i) {
+        const LayIxf &f = lb.ixfs[i];
+        for (size_t b = 0; b < f.fname.size(); ++b)
+            if (f.fname[b] >= 0 && f.part[b] == 0) {
+                cost += (double)counts[f.fname[b]] * path[i];
+                total += (double)counts[f.fname[b]];
+            }
+    }
+    L->pub.n_ixf = m;
+    L->pub.n_bins_total = L->next.size();
+    L->pub.t_max = T;
+    L->pub.depth = depth;
+    L->pub.bytes_per_hash = total > 0 ? cost / total : 0.0;
+    L->pub.index_bytes = idx_bytes;
+    L->pub.ixf_bins = L->ixf_bins.data();
+    L->pub.bin_first = L->bin_first.data();
+    L->pub.next_ixf = L->next.data();
+    L->pub.fname_idx = L->fname.data();
+    L->pub.part = L->part.data();
+    L->pub.parts = L->parts.data();
+    return L;
+}
+
+} // namespace
+
+extern "C" {
+
+int taxor_build_layout(const uint64_t *counts, uint64_t n, uint64_t t_max, taxor_layout **out)
+{
+    if (!out) return TAXOR_E_ARG;
+    *out = nullptr;
+    if (!counts || n == 0 || n >= (1ull << 31) || (t_max && t_max < 2)) return TAXOR_E_ARG;
+    std::set<uint64_t> cand;
+    if (t_max) cand.insert(t_max);
+    else {
+        for (uint64_t t = 64; t <= 4096; t *= 2) cand.insert(t);                    // taxor_build.cpp:177-178
+        cand.insert(std::max<uint64_t>(64, (uint64_t)std::ceil(std::sqrt((double)n) / 64.0) * 64));   // :182-184
+    }
+    LayoutOwned *best = nullptr;
+    for (const uint64_t T : cand) {                                              // ascending: ties keep the smaller t_max
+        LayoutOwned *L = layout_for(counts, n, T);
+        if (!best || L->pub.bytes_per_hash < best->pub.bytes_per_hash ||
+            (L->pub.bytes_per_hash == best->pub.bytes_per_hash && L->pub.index_bytes < best->pub.index_bytes)) {
+            delete best;
+            best = L;
+        } else
+            delete L;
+    }
+    *out = &best->pub;
+    return TAXOR_OK;
+}
+
+void taxor_layout_free(taxor_layout *l)
+{
+    delete reinterpret_cast<LayoutOwned *>(l);   // pub is the first member
 }
 
 } // extern "C"

@@ -17,29 +17,16 @@ namespace taxor {
 namespace {
 
 constexpr int KB = 256;
-constexpr uint64_t EMPTY = ~0ull;
+constexpr uint64_t EMPTY = KEYSET_EMPTY;
 constexpr uint32_t ENTRIES_PER_BLOCK = 4096;
 constexpr uint64_t LAUNCH_KEYS = 1ull << 24;     // keys per k_set_insert / k_set_mark launch
-
-__device__ __forceinline__ uint64_t slot_hash(uint64_t k)
-{
-    k ^= k >> 32;
-    k *= 0xD6E8FEB86659FD93ull;
-    k ^= k >> 32;
-    return k;
-}
 
 __global__ __launch_bounds__(KB) void k_set_insert(const uint64_t *__restrict__ in, uint64_t n, uint64_t *tab, uint64_t mask, unsigned long long *ctl)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * KB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * KB) {
         const uint64_t key = in[i];
         if (key == EMPTY) { ctl[1] = 1ull; continue; }            // the marker itself as a key: remembered aside
-        uint64_t s = slot_hash(key) & mask;
-        for (;;) {
-            const uint64_t old = atomicCAS((unsigned long long *)&tab[s], (unsigned long long)EMPTY, (unsigned long long)key);
-            if (old == EMPTY || old == key) break;
-            s = (s + 1) & mask;
-        }
+        (void)keyset_insert(tab, mask, key);
     }
 }
 
@@ -56,15 +43,7 @@ __global__ __launch_bounds__(KB) void k_set_mark(const uint64_t *__restrict__ in
         const uint64_t key = in[i];
         bool first;
         if (key == EMPTY) first = atomicCAS(&ctl[1], 0ull, 1ull) == 0ull;       // the marker itself as a key: one of them counts
-        else {
-            uint64_t s = slot_hash(key) & mask;
-            for (;;) {
-                const uint64_t old = atomicCAS((unsigned long long *)&tab[s], (unsigned long long)EMPTY, (unsigned long long)key);
-                if (old == EMPTY) { first = true; break; }
-                if (old == key) { first = false; break; }
-                s = (s + 1) & mask;
-            }
-        }
+        else first = keyset_insert(tab, mask, key) > 0;
         keep[i] = first ? 1 : 0;
         kept += first;
     }
@@ -181,6 +160,18 @@ hipError_t KeyUnion::unique(const uint64_t *d_in, uint64_t n, uint64_t *d_out, u
     }
     *n_out = cnt;
     return hipSuccess;
+}
+
+hipError_t keyset_count_distinct(const uint64_t *d_in, uint64_t n, uint64_t *n_out, hipStream_t st)
+{
+    *n_out = 0;
+    if (n == 0) return hipSuccess;
+    KeyUnion u;
+    uint8_t *keep = nullptr;
+    hipError_t e = hipMalloc((void **)&keep, n);
+    if (e == hipSuccess) e = u.mark(d_in, n, keep, n_out, st);
+    if (keep) (void)hipFree(keep);
+    return e;
 }
 
 } // namespace taxor

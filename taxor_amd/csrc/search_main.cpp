@@ -27,10 +27,13 @@ extern char **environ;
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <filesystem>
+#include <fstream>
 #include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
+#include <sstream>
 #include <string>
 #include <thread>
 #include <vector>
@@ -758,6 +761,7 @@ uint64_t fnv1a(const char *p, size_t n)
 }
 
 #include "pin_cmd.h"
+#include "build_cmd.h"
 
 } // namespace
 
@@ -1009,9 +1013,10 @@ int main(int argc, char **argv)
         fprintf(stderr, "%llu reads, %llu bases, %zu batches, %.3f s\n", (unsigned long long)n, (unsigned long long)nb, got.size(), dt);
         return 0;
     }
+    if (argc > 1 && strcmp(argv[1], "build") == 0) return build_command(argc, argv);   // genomes + taxonomy TSV -> .hixf (build_cmd.h)
     if (argc > 1 && strcmp(argv[1], "search") == 0) a = 2;                 // `taxor search ...` like the reference
-    else if (argc > 1 && (strcmp(argv[1], "build") == 0 || strcmp(argv[1], "profile") == 0)) {
-        fprintf(stderr, "[TAXOR ERROR] only the `search` subcommand is provided by this build\n");
+    else if (argc > 1 && strcmp(argv[1], "profile") == 0) {
+        fprintf(stderr, "[TAXOR ERROR] the `profile` subcommand is not provided by this build\n");
         return -1;
     }
     Config cfg;

@@ -1,0 +1,89 @@
+"""`taxor build`'s two library stages from Python (taxor_amd/csrc/genome_keys.hip, host_util.cpp): the device keyer -- whole genomes
+-> the distinct, FracMinHash-filtered, ascending keys of every user bin -- and the IXF layout over their counts."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+class GenomeKeyer:
+    """Accumulates records (ASCII bases, any number of add() calls; a user bin's records may span calls); finish() -> CSR.
+    Syncmer mode uses t = (k - s + 1) // 2 unless t is given (taxor_build.cpp:509-510)."""
+
+    def __init__(self, n_bins, k=22, s=12, t=None, use_syncmer=True, window=None, scaling=1, device=0):
+        if t is None:
+            t = (k - s + 1) // 2
+        prm = _lib.KeyerParams(k, s if use_syncmer else 0, t if use_syncmer else 0, 1 if use_syncmer else 0,
+                               window if window is not None else k, scaling, 0, n_bins)
+        h = C.c_void_p()
+        check(_lib.lib().taxor_gpu_keyer_create(device, C.byref(prm), C.byref(h)))
+        self._h = h
+        self.n_bins = n_bins
+        self._out = None
+
+    def add(self, bases, rec_off, rec_bin):
+        b = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, dtype=np.uint8)
+        o = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        r = np.ascontiguousarray(rec_bin, dtype=np.uint32)
+        assert o.size == r.size + 1
+        check(_lib.lib().taxor_gpu_keyer_add(self._h, _p(b) if b.size else None, _p(o), _p(r), r.size))
+
+    def finish(self):
+        """(bin_off uint64[n_bins + 1], keys uint64[bin_off[-1]]), each bin ascending"""
+        if self._out is None:
+            off = C.POINTER(C.c_uint64)()
+            keys = C.POINTER(C.c_uint64)()
+            dk = C.POINTER(C.c_uint64)()
+            check(_lib.lib().taxor_gpu_keyer_finish(self._h, C.byref(off), C.byref(keys), C.byref(dk)))
+            o = np.ctypeslib.as_array(off, shape=(self.n_bins + 1,)).copy()
+            n = int(o[-1])
+            k = np.ctypeslib.as_array(keys, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+            self._out = (o, k)
+        return self._out
+
+    def union_size(self, bins):
+        b = np.ascontiguousarray(bins, dtype=np.uint32)
+        out = C.c_uint64(0)
+        check(_lib.lib().taxor_gpu_keyer_union_size(self._h, _p(b), b.size, C.byref(out)))
+        return int(out.value)
+
+    def stats(self):
+        st = _lib.KeyerStats()
+        check(_lib.lib().taxor_gpu_keyer_stats(self._h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in _lib.KeyerStats._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().taxor_gpu_keyer_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def build_layout(counts, t_max=0):
+    """taxor_build_layout: the IXF tree for these per-user-bin distinct key counts.  Returns a dict with t_max, depth,
+    bytes_per_hash, index_bytes and ixfs: [{bins, next_ixf, fname_idx, part, parts}] (IXF 0 = root)."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    L = C.POINTER(_lib.Layout)()
+    check(_lib.lib().taxor_build_layout(_p(c), c.size, int(t_max), C.byref(L)))
+    try:
+        l = L.contents
+        first = np.ctypeslib.as_array(l.bin_first, shape=(l.n_ixf + 1,))
+        tb = int(l.n_bins_total)
+        nx = np.ctypeslib.as_array(l.next_ixf, shape=(tb,))
+        fn = np.ctypeslib.as_array(l.fname_idx, shape=(tb,))
+        part = np.ctypeslib.as_array(l.part, shape=(tb,))
+        parts = np.ctypeslib.as_array(l.parts, shape=(tb,))
+        ixfs = []
+        for i in range(int(l.n_ixf)):
+            a, b = int(first[i]), int(first[i + 1])
+            ixfs.append(dict(bins=b - a, next_ixf=nx[a:b].copy(), fname_idx=fn[a:b].copy(), part=part[a:b].copy(), parts=parts[a:b].copy()))
+        return dict(t_max=int(l.t_max), depth=int(l.depth), bytes_per_hash=float(l.bytes_per_hash), index_bytes=float(l.index_bytes), ixfs=ixfs)
+    finally:
+        _lib.lib().taxor_layout_free(L)
