@@ -177,15 +177,34 @@ def test_build_syncmers_end_to_end(tmp_path):
     assert out.read_bytes() == out2.read_bytes()
 
 
-@pytest.mark.parametrize("extra,k,w,scaling", [([], 20, 20, 1), (["--use-syncmer", "--kmer-size", "22", "--syncmer-size", "12", "--scaling", "10"], 22, 20, 10)])
-def test_build_minimisers_and_scaling(tmp_path, extra, k, w, scaling):
+BUILD_ROWS = [
+    ([], 20, 0, 0, 20, 1),
+    (["--use-syncmer", "--kmer-size", "22", "--syncmer-size", "12", "--scaling", "10"], 22, 12, 5, 20, 10),
+    (["--use-syncmer", "--kmer-size", "30", "--syncmer-size", "16"], 30, 16, 7, 20, 1),
+    (["--use-syncmer", "--kmer-size", "2", "--syncmer-size", "1"], 2, 1, 1, 20, 1),
+    (["--kmer-size", "32", "--window-size", "96"], 32, 0, 0, 96, 1),
+    (["--kmer-size", "1", "--window-size", "1"], 1, 0, 0, 1, 1),
+    # most 6-kb genomes keep zero or one key: user bins without keys go through layout, build and check_index
+    (["--use-syncmer", "--kmer-size", "22", "--syncmer-size", "12", "--scaling", "1000"], 22, 12, 5, 20, 1000),
+]
+
+
+# the first two rows keep the ids they had before the s and t columns
+BUILD_IDS = ["extra0-20-20-1", "extra1-22-20-10", "syncmer-k30-s16", "syncmer-k2-s1", "minimiser-k32-w96", "minimiser-k1-w1",
+             "syncmer-k22-s12-scaling1000"]
+
+
+@pytest.mark.parametrize("extra,k,s,t,w,scaling", BUILD_ROWS, ids=BUILD_IDS)
+def test_build_minimisers_and_scaling(tmp_path, extra, k, s, t, w, scaling):
     tsv, dirs, paths, records = write_inputs(tmp_path)
     out = tmp_path / "idx.hixf"
     build(tsv, dirs, out, "--tmax", "64", *extra)
     use_syncmer = "--use-syncmer" in extra
-    sets = oracle_sets(records, k, 12, 5, scaling, None if use_syncmer else w)
+    sets = oracle_sets(records, k, s, t, scaling, None if use_syncmer else w)
+    if scaling == 1000:
+        assert sum(x.size == 0 for x in sets) > N // 3
     hf = HixfFile(out)
-    depth, splits, merged = check_index(hf, sets, paths, records, k, 12, 5, use_syncmer, w, scaling)
+    depth, splits, merged = check_index(hf, sets, paths, records, k, s, t, use_syncmer, w, scaling)
     assert depth >= 2 and merged >= 1
     hf.close()
     out2 = tmp_path / "idx2.hixf"

@@ -28,6 +28,7 @@ def test_build_ixf_members_match(bins, max_elems):
     sizes = {0: max_elems, 1: 1, 2: max_elems // 3, bins - 1: max_elems // 2, bins // 2: 17}
     keys = {b: np.unique(rng.integers(0, 2**64 - 1, size=n, dtype=np.uint64)) for b, n in sizes.items()}
     keys[2] = np.concatenate([keys[2], np.array([0], dtype=np.uint64)])     # wyhash(poly-A k-mer) = 0 is a legal key
+    keys[bins - 1] = np.concatenate([keys[bins - 1], np.array([2**64 - 1], dtype=np.uint64)])   # so is wyhash((AT)^16) = 2^64 - 1
     seed, rounds = idx.build_ixf(0, keys, seed0=12345)
     assert rounds >= 1
     sr = Searcher(idx, ratio=0.5)
@@ -145,6 +146,17 @@ def test_hierarchical_build_on_gpu(seed):
         for b, keys in f.get("leaf_keys", {}).items():
             leaf[(i, b)] = keys
     assert leaf, "layout carries no leaf keys"
+    if seed == 2:
+        # the key 2^64 - 1 (wyhash of the k = 32 syncmer (AT)^16; the empty marker of KeyUnion's table) in two leaf bins under
+        # the same merged bin: the merged bin's union keeps it once
+        up = {int(f["next_ixf"][b]): (i, b) for i, f in enumerate(ix) for b in range(f["bins"]) if f["fname_idx"][b] == -1}
+        groups = {}
+        for (i, b) in sorted(leaf):
+            if i in up:
+                groups.setdefault(up[i], []).append((i, b))
+        pair = next(g for g in groups.values() if len(g) >= 2)[:2]
+        for ib in pair:
+            leaf[ib] = np.concatenate([leaf[ib], np.array([2**64 - 1], dtype=np.uint64)])
     # rows sized for the unions: merged bins hold whole subtrees
     def subtree_keys(i):
         ks = [k for (ii, b), k in leaf.items() if ii == i]
@@ -179,6 +191,9 @@ def test_hierarchical_build_on_gpu(seed):
             pi, pb = parent[node]
             assert h.ixf_bulk_count(pi, keys)[pb] == len(keys), (i, b, pi, pb)
             node = pi
+    if seed == 2:
+        for ib in pair:
+            assert leaf[ib][-1] == 2**64 - 1 and h.ixf_bulk_count(ib[0], leaf[ib][-1:])[ib[1]] == 1
     # (2) search parity on the GPU-built index, (3) control reads classify
     bases, offs, origin = synth.synth_reads(g, go, 200, 1500, error_rate=0.01, frac_random=0.1, seed=seed)
     sr = Searcher(idx, error_rate=0.04)

@@ -131,3 +131,17 @@ def test_k32_divergence():
     for k, s, t in ((32, 16, 8), (32, 1, 1), (32, 9, 24)):
         for r in READS[33:45]:
             assert orc.seq_to_syncmers(r, k, s, t).tolist() == mg.seq_to_syncmers(r.decode(), k, s, t), (k, s, t, len(r))
+
+
+def test_k32_palindromes_hash_to_the_empty_marker():
+    """wyhash(x) = lo64 ^ hi64 of x * 0x9E3779B97F4A7C15 is 2^64 - 1 exactly for x = 0x33..33, 0x66..66, 0x99..99, 0xCC..CC: the
+    32-mers (AT)^16, (CG)^16, (GC)^16, (TA)^16, each its own reverse complement.  2^64 - 1 is the empty-slot marker of the
+    device key sets (keyset.h), so k = 32 syncmers over (AT)n or (CG)n emit the marker as a key; the GPU tests of the keyer
+    and the builder rest on this"""
+    marker = 2**64 - 1
+    assert [orc.wyhash(int(c * 16, 16)) for c in "369C"] == [marker] * 4
+    assert orc.wyhash(marker) == marker                       # FracMinHash drops it at every scaling > 1
+    for unit in (b"AT", b"CG", b"GC", b"TA"):
+        assert orc.seq_to_syncmers(unit * 16, 32, 1, 1).tolist() == [marker], unit
+    for s in range(1, 17):
+        assert orc.seq_to_syncmers(b"AT" * 40, 32, s, 1).tolist() == [marker], s
