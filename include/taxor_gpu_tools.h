@@ -338,6 +338,54 @@ int taxor_synth_reads(const char *genomes, const uint64_t *genome_off, uint64_t 
                       uint32_t read_len, double error_rate, double frac_random, double frac_reverse,
                       uint64_t seed, int threads, char *bases, uint64_t cap, uint64_t *offsets, int32_t *origin);
 
+/* ---- `taxor profile` (src/main/taxor_profile.cpp) over a CSR read -> matches; taxor_amd/csrc/profile.hip, DESIGN.md section 10.
+ * Reads and references are numbered in byte-wise order of their names (the reference iterates std::map<std::string, ...>, and
+ * that order is observable); a read's matches stand in file order.  A read without a hit has ONE match with ref -1 (the "-"
+ * line).  A match never moves: the stages keep an alive byte per match. */
+typedef struct taxor_gpu_profile taxor_gpu_profile;
+typedef struct {
+    uint64_t n_reads, n_refs, n_matches;
+    const uint64_t *read_off;    /* [n_reads + 1] */
+    const int32_t *ref;          /* [n_matches] reference id, -1 for the "-" line */
+    const uint64_t *ref_len;     /* [n_matches] */
+    const uint64_t *hash_match;  /* [n_matches] QUERY_HASH_MATCH */
+    const uint64_t *query_len;   /* [n_reads] */
+    const uint64_t *hash_count;  /* [n_reads] QUERY_HASH_COUNT */
+} taxor_profile_csr;
+#define TAXOR_PROFILE_TRACE 1u   /* keep the per-stage and per-iteration outputs the stage tests compare */
+typedef struct {
+    uint64_t n_reads, n_refs, n_matches;
+    const int32_t *ref;          /* [n_matches] after round 3's renames */
+    const uint64_t *ref_len;     /* [n_matches] likewise */
+    const uint8_t *alive;        /* [n_matches] after the EM's erasures; a read is reported iff one of its matches is alive */
+    const uint8_t *best;         /* [n_matches] the last iteration's best matches (profile_results) */
+    const uint8_t *has_prior;    /* [n_refs] the found taxa: seen in round 3 and explained by no other reference */
+    const uint64_t *taxa_len;    /* [n_refs] ref_len of the reference's first match in round 3 */
+    const uint64_t *ref_nts;     /* [n_refs] nucleotides of the reads whose best set holds the reference, last iteration */
+    const double *log_prior;     /* [n_refs] log sequence abundance after the last update */
+    const int32_t *explained_by; /* [n_refs] the reference that explains this one, after chain resolution, or -1 */
+    const uint32_t *unique_reads, *all_reads;   /* [n_refs] round 3's unique_assign_reads / all_assigned_reads */
+    uint64_t all_nts, unclassified_nts;
+    double log_unclassified;
+    uint32_t em_steps_needed;    /* what the reference prints as "Number of EM steps needed" */
+    uint32_t em_iterations;      /* passes of the loop body */
+    uint64_t n_pairs, pair_slots;   /* occupied slots / slots of the pair table */
+    const uint64_t *pair_key;    /* [n_pairs] ref1 << 32 | ref2, in table order */
+    const uint32_t *pair_count;  /* [n_pairs] reads the two share */
+    /* with TAXOR_PROFILE_TRACE, else null: alive after each round, ref_nts of every iteration [em_iterations * n_refs] */
+    const uint8_t *alive_round1, *alive_round2, *alive_round3;
+    const uint64_t *iter_ref_nts;
+    double seconds_filter, seconds_em;
+} taxor_profile_results;
+int taxor_gpu_profile_create(int device, const taxor_profile_csr *csr, taxor_gpu_profile **out);
+/* the three rounds and at most em_steps EM iterations; once per object.  TAXOR_E_ARG with a message that names the situation for
+ * the two inputs the reference leaves undefined: an explained-by chain that runs into a cycle, and a multi-match read none of
+ * whose references has a prior */
+int taxor_gpu_profile_run(taxor_gpu_profile *p, uint32_t em_steps, uint32_t flags);
+/* pointers stay valid until _destroy */
+int taxor_gpu_profile_results(taxor_gpu_profile *p, taxor_profile_results *out);
+void taxor_gpu_profile_destroy(taxor_gpu_profile *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,26 @@ class Layout(C.Structure):
                 ("part", C.POINTER(C.c_uint64)), ("parts", C.POINTER(C.c_uint64))]
 
 
+class ProfileCsr(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_refs", C.c_uint64), ("n_matches", C.c_uint64), ("read_off", C.c_void_p), ("ref", C.c_void_p),
+                ("ref_len", C.c_void_p), ("hash_match", C.c_void_p), ("query_len", C.c_void_p), ("hash_count", C.c_void_p)]
+
+
+class ProfileResults(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_refs", C.c_uint64), ("n_matches", C.c_uint64), ("ref", C.POINTER(C.c_int32)),
+                ("ref_len", C.POINTER(C.c_uint64)), ("alive", C.POINTER(C.c_uint8)), ("best", C.POINTER(C.c_uint8)),
+                ("has_prior", C.POINTER(C.c_uint8)), ("taxa_len", C.POINTER(C.c_uint64)), ("ref_nts", C.POINTER(C.c_uint64)),
+                ("log_prior", C.POINTER(C.c_double)), ("explained_by", C.POINTER(C.c_int32)), ("unique_reads", C.POINTER(C.c_uint32)),
+                ("all_reads", C.POINTER(C.c_uint32)), ("all_nts", C.c_uint64), ("unclassified_nts", C.c_uint64),
+                ("log_unclassified", C.c_double), ("em_steps_needed", C.c_uint32), ("em_iterations", C.c_uint32), ("n_pairs", C.c_uint64),
+                ("pair_slots", C.c_uint64), ("pair_key", C.POINTER(C.c_uint64)), ("pair_count", C.POINTER(C.c_uint32)),
+                ("alive_round1", C.POINTER(C.c_uint8)), ("alive_round2", C.POINTER(C.c_uint8)), ("alive_round3", C.POINTER(C.c_uint8)),
+                ("iter_ref_nts", C.POINTER(C.c_uint64)), ("seconds_filter", C.c_double), ("seconds_em", C.c_double)]
+
+
+PROFILE_TRACE = 1
+
+
 SIGNATURES = {
     "taxor_gpu_last_error": (C.c_char_p, []),
     "taxor_gpu_index_create": (C.c_int, [C.POINTER(HixfView), C.c_int, C.POINTER(_P)]),
@@ -146,6 +166,10 @@ SIGNATURES = {
     "taxor_gpu_keyer_arrange": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.POINTER(C.c_uint64))]),
     "taxor_gpu_keyer_stats": (C.c_int, [_P, C.POINTER(KeyerStats)]),
     "taxor_gpu_keyer_destroy": (None, [_P]),
+    "taxor_gpu_profile_create": (C.c_int, [C.c_int, C.POINTER(ProfileCsr), C.POINTER(_P)]),
+    "taxor_gpu_profile_run": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
+    "taxor_gpu_profile_results": (C.c_int, [_P, C.POINTER(ProfileResults)]),
+    "taxor_gpu_profile_destroy": (None, [_P]),
     "taxor_gpu_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "taxor_build_layout": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(Layout))]),
     "taxor_layout_free": (None, [C.POINTER(Layout)]),

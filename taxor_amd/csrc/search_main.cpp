@@ -19,7 +19,9 @@ extern char **environ;
 #include <unistd.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cerrno>
+#include <cmath>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -35,7 +37,9 @@ extern char **environ;
 #include <mutex>
 #include <sstream>
 #include <string>
+#include <string_view>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 namespace {
@@ -762,6 +766,7 @@ uint64_t fnv1a(const char *p, size_t n)
 
 #include "pin_cmd.h"
 #include "build_cmd.h"
+#include "profile_cmd.h"
 
 } // namespace
 
@@ -1014,11 +1019,8 @@ int main(int argc, char **argv)
         return 0;
     }
     if (argc > 1 && strcmp(argv[1], "build") == 0) return build_command(argc, argv);   // genomes + taxonomy TSV -> .hixf (build_cmd.h)
+    if (argc > 1 && strcmp(argv[1], "profile") == 0) return profile_command(argc, argv);   // search TSV -> CAMI profile + binning (profile_cmd.h)
     if (argc > 1 && strcmp(argv[1], "search") == 0) a = 2;                 // `taxor search ...` like the reference
-    else if (argc > 1 && strcmp(argv[1], "profile") == 0) {
-        fprintf(stderr, "[TAXOR ERROR] the `profile` subcommand is not provided by this build\n");
-        return -1;
-    }
     Config cfg;
     // seqan3::argument_parser takes a long option's value either as the next argument or attached with '='
     // ("--threads 4" / "--threads=4"); split the second form so that one loop handles both
