@@ -386,6 +386,33 @@ int taxor_gpu_profile_run(taxor_gpu_profile *p, uint32_t em_steps, uint32_t flag
 int taxor_gpu_profile_results(taxor_gpu_profile *p, taxor_profile_results *out);
 void taxor_gpu_profile_destroy(taxor_gpu_profile *p);
 
+/* ---- search -> profile without the TSV (taxor_amd/csrc/profile_feed.hip): a feed on one device collects,
+ * batch by batch and in any order, the read -> matches CSR that taxor_gpu_profile_create takes from the host.  ref_of_bin[u] is the
+ * dense id of user bin u's accession (ids in byte-wise order of the distinct accession strings; user bins of one accession share an
+ * id), ref_len_of_bin[u] its species' seq_len.  flags 0 applies the search's output filter (taxor_search.cpp:268-306: a tuple is
+ * dropped iff (double)count < (double)max_count * 0.8; a read that keeps nothing is ONE match with ref -1 and QHASH_COUNT 0);
+ * TAXOR_FEED_KEEP_ALL appends every tuple (rows that passed the filter already).  A batch is never truncated: the stores grow.
+ * _add calls may come from several threads. */
+typedef struct taxor_gpu_profile_feed taxor_gpu_profile_feed;
+#define TAXOR_FEED_KEEP_ALL 1u
+int taxor_gpu_profile_feed_create(int device, uint64_t n_user_bins, const int32_t *ref_of_bin, const uint64_t *ref_len_of_bin, uint64_t n_refs,
+                                  taxor_gpu_profile_feed **out);
+/* the results of the searcher's last run where they lie on the feed's device (the buffers taxor_gpu_batch_export_device copies
+ * from; QUERY_LEN from the batch's offsets); first_read = index of the batch's first read among all reads.  Waits for the run; when
+ * it returns the searcher may run again */
+int taxor_gpu_profile_feed_add_batch(taxor_gpu_profile_feed *f, taxor_gpu_searcher *s, uint64_t first_read, uint32_t flags);
+/* the same over host arrays: tuples of read r at [read_off[r], read_off[r+1]) of user_bin / count, n_hashes and query_len [n_reads] */
+int taxor_gpu_profile_feed_add_csr(taxor_gpu_profile_feed *f, uint64_t first_read, uint64_t n_reads, const uint64_t *read_off, const int64_t *user_bin,
+                                   const uint32_t *count, const uint32_t *n_hashes, const uint64_t *query_len, uint32_t flags);
+/* rank_of_read[i] = position of read i in byte-wise order of the read ids.  Permutes the CSR into that order on the device and
+ * hands the device arrays to a new taxor_gpu_profile (_run, _results, _destroy as above; the caller destroys it).  TAXOR_E_ARG
+ * unless the batches' ranges cover [0, n_reads_total) exactly once and the ranks are a permutation */
+int taxor_gpu_profile_feed_finish(taxor_gpu_profile_feed *f, const uint64_t *rank_of_read, uint64_t n_reads_total, taxor_gpu_profile **profile);
+/* after _finish: the finished CSR (reads in rank order) in host memory, and per match the user bin it came from (-1 for the "-"
+ * match) -- a binning file prints the taxid of the ORIGINAL line.  Either pointer may be NULL.  Valid until _destroy */
+int taxor_gpu_profile_feed_matches(const taxor_gpu_profile_feed *f, taxor_profile_csr *csr, const int64_t **user_bin);
+void taxor_gpu_profile_feed_destroy(taxor_gpu_profile_feed *f);
+
 #ifdef __cplusplus
 }
 #endif

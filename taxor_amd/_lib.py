@@ -149,6 +149,7 @@ class ProfileResults(C.Structure):
 
 
 PROFILE_TRACE = 1
+FEED_KEEP_ALL = 1
 
 
 SIGNATURES = {
@@ -170,6 +171,12 @@ SIGNATURES = {
     "taxor_gpu_profile_run": (C.c_int, [_P, C.c_uint32, C.c_uint32]),
     "taxor_gpu_profile_results": (C.c_int, [_P, C.POINTER(ProfileResults)]),
     "taxor_gpu_profile_destroy": (None, [_P]),
+    "taxor_gpu_profile_feed_create": (C.c_int, [C.c_int, C.c_uint64, _P, _P, C.c_uint64, C.POINTER(_P)]),
+    "taxor_gpu_profile_feed_add_batch": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32]),
+    "taxor_gpu_profile_feed_add_csr": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint32]),
+    "taxor_gpu_profile_feed_finish": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P)]),
+    "taxor_gpu_profile_feed_matches": (C.c_int, [_P, C.POINTER(ProfileCsr), C.POINTER(C.POINTER(C.c_int64))]),
+    "taxor_gpu_profile_feed_destroy": (None, [_P]),
     "taxor_gpu_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "taxor_build_layout": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(Layout))]),
     "taxor_layout_free": (None, [C.POINTER(Layout)]),

@@ -22,6 +22,7 @@
 // -ffp-contract=off); every log and the one sequential sum of posteriors are the host's (run(), below).
 #include "../../include/taxor_gpu_tools.h"
 #include "keyset.h"
+#include "profile_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -369,11 +370,14 @@ double pf_now() { return std::chrono::duration<double>(std::chrono::steady_clock
 }   // namespace
 
 struct taxor_gpu_profile {
+    explicit taxor_gpu_profile(std::shared_ptr<taxor_profile_host_csr> h = std::make_shared<taxor_profile_host_csr>()) : host(std::move(h)) {}
     int device = 0;
     uint64_t n_reads = 0, n_refs = 0, n_matches = 0;
     hipStream_t st = nullptr;
-    // the CSR as given (host copies the host stages read)
-    std::vector<uint64_t> h_off, h_ref_len0, h_hash_match, h_query_len, h_hash_count;
+    // the CSR as given (host copies the host stages read; never written after the constructor functions -- a feed shares them)
+    std::shared_ptr<taxor_profile_host_csr> host;
+    std::vector<uint64_t> &h_off = host->off, &h_ref_len0 = host->ref_len, &h_hash_match = host->hash_match, &h_query_len = host->query_len,
+                          &h_hash_count = host->hash_count;
     PBuf<uint64_t> d_off, d_ref_len, d_hash_match, d_query_len, d_hash_count, d_taxa_len, d_keys;
     PBuf<int32_t> d_ref, d_ref2, d_expl;
     PBuf<uint8_t> d_alive, d_alive2, d_flag, d_dup, d_valid, d_best, d_has_prior;
@@ -450,6 +454,34 @@ int explained_by(uint64_t n_refs, const std::vector<uint32_t> &uniq, const std::
     return TAXOR_OK;
 }
 
+// everything a run works in, beside the six arrays of the CSR
+int alloc_work(taxor_gpu_profile *p)
+{
+    const uint64_t R = p->n_reads, F = p->n_refs, M = p->n_matches;
+    PF_TRY(p->d_ref2.alloc(M));
+    PF_TRY(p->d_alive.alloc(M));
+    PF_TRY(p->d_alive2.alloc(M));
+    PF_TRY(p->d_dup.alloc(M));
+    PF_TRY(p->d_valid.alloc(M));
+    PF_TRY(p->d_best.alloc(M));
+    PF_TRY(p->d_post.alloc(M));
+    PF_TRY(p->d_log_match.alloc(M));
+    PF_TRY(p->d_log_count.alloc(R));
+    PF_TRY(p->d_sum.alloc(R));
+    PF_TRY(p->d_flag.alloc(F));
+    PF_TRY(p->d_has_prior.alloc(F));
+    PF_TRY(p->d_uniq.alloc(F));
+    PF_TRY(p->d_all.alloc(F));
+    PF_TRY(p->d_first.alloc(F));
+    PF_TRY(p->d_ref_nts.alloc(F));
+    PF_TRY(p->d_prior.alloc(F));
+    PF_TRY(p->d_expl.alloc(F));
+    PF_TRY(p->d_taxa_len.alloc(F));
+    PF_TRY(p->d_totals.alloc(2));
+    PF_TRY(p->d_err.alloc(1));
+    return TAXOR_OK;
+}
+
 }   // namespace
 
 extern "C" int taxor_gpu_profile_create(int device, const taxor_profile_csr *csr, taxor_gpu_profile **out)
@@ -479,31 +511,11 @@ extern "C" int taxor_gpu_profile_create(int device, const taxor_profile_csr *csr
     PF_TRY(hipStreamCreate(&p->st));
     PF_TRY(p->d_off.alloc(R + 1));
     PF_TRY(p->d_ref.alloc(M));
-    PF_TRY(p->d_ref2.alloc(M));
     PF_TRY(p->d_ref_len.alloc(M));
     PF_TRY(p->d_hash_match.alloc(M));
     PF_TRY(p->d_query_len.alloc(R));
     PF_TRY(p->d_hash_count.alloc(R));
-    PF_TRY(p->d_alive.alloc(M));
-    PF_TRY(p->d_alive2.alloc(M));
-    PF_TRY(p->d_dup.alloc(M));
-    PF_TRY(p->d_valid.alloc(M));
-    PF_TRY(p->d_best.alloc(M));
-    PF_TRY(p->d_post.alloc(M));
-    PF_TRY(p->d_log_match.alloc(M));
-    PF_TRY(p->d_log_count.alloc(R));
-    PF_TRY(p->d_sum.alloc(R));
-    PF_TRY(p->d_flag.alloc(F));
-    PF_TRY(p->d_has_prior.alloc(F));
-    PF_TRY(p->d_uniq.alloc(F));
-    PF_TRY(p->d_all.alloc(F));
-    PF_TRY(p->d_first.alloc(F));
-    PF_TRY(p->d_ref_nts.alloc(F));
-    PF_TRY(p->d_prior.alloc(F));
-    PF_TRY(p->d_expl.alloc(F));
-    PF_TRY(p->d_taxa_len.alloc(F));
-    PF_TRY(p->d_totals.alloc(2));
-    PF_TRY(p->d_err.alloc(1));
+    if (int rc = alloc_work(p.get())) return rc;
     PF_TRY(hipMemcpy(p->d_off.p, csr->read_off, (R + 1) * 8, hipMemcpyHostToDevice));
     if (M) {
         PF_TRY(hipMemcpy(p->d_ref.p, csr->ref, M * 4, hipMemcpyHostToDevice));
@@ -513,6 +525,39 @@ extern "C" int taxor_gpu_profile_create(int device, const taxor_profile_csr *csr
         PF_TRY(hipMemcpy(p->d_query_len.p, csr->query_len, R * 8, hipMemcpyHostToDevice));
         PF_TRY(hipMemcpy(p->d_hash_count.p, csr->hash_count, R * 8, hipMemcpyHostToDevice));
     }
+    *out = p.release();
+    return TAXOR_OK;
+}
+
+// library-internal (profile_feed.hip): a profile over a CSR that is on the device already.  `host` holds the same CSR in host memory
+// (the host stages of run() read it; shared with the caller, not copied); the six device arrays are single hipMalloc blocks of at
+// least one element, matches' reference ids within [-1, n_refs).  On success the profile owns them, on failure the caller still does.
+extern "C" __attribute__((visibility("hidden"))) int taxor_profile_adopt_device(int device, const std::shared_ptr<taxor_profile_host_csr> *host, uint64_t n_refs,
+                                                                                uint64_t *d_off, int32_t *d_ref, uint64_t *d_ref_len, uint64_t *d_hash_match,
+                                                                                uint64_t *d_query_len, uint64_t *d_hash_count, taxor_gpu_profile **out)
+{
+    if (!host || !*host || !out || !d_off || !d_ref || !d_ref_len || !d_hash_match || !d_query_len || !d_hash_count) return pfail(TAXOR_E_ARG, "profile_adopt: null argument");
+    *out = nullptr;
+    const taxor_profile_host_csr &h = **host;
+    if (h.off.empty()) return pfail(TAXOR_E_ARG, "profile_adopt: read_off is empty");
+    const uint64_t R = h.off.size() - 1, F = n_refs, M = h.off[R];
+    if (F >= (1ull << 31)) return pfail(TAXOR_E_ARG, "profile_adopt: more than 2^31 - 1 references");
+    if (h.off[0] != 0 || h.ref_len.size() != M || h.hash_match.size() != M || h.query_len.size() != R || h.hash_count.size() != R)
+        return pfail(TAXOR_E_ARG, "profile_adopt: the host arrays do not span the reads and the matches");
+    PF_TRY(hipSetDevice(device));
+    auto p = std::make_unique<taxor_gpu_profile>(*host);
+    p->device = device;
+    p->n_reads = R;
+    p->n_refs = F;
+    p->n_matches = M;
+    PF_TRY(hipStreamCreate(&p->st));
+    if (int rc = alloc_work(p.get())) return rc;
+    p->d_off.p = d_off;
+    p->d_ref.p = d_ref;
+    p->d_ref_len.p = d_ref_len;
+    p->d_hash_match.p = d_hash_match;
+    p->d_query_len.p = d_query_len;
+    p->d_hash_count.p = d_hash_count;
     *out = p.release();
     return TAXOR_OK;
 }

@@ -203,6 +203,110 @@ bool profile_write_abundances(const std::string &path, const std::map<std::strin
     return fclose(f) == 0 && ok;
 }
 
+// the value of one of the profile's options into c, with the reference parser's messages (:19-76); false and *err on a value that
+// does not parse or lies outside its range.  `taxor search` takes the same options for its one-run mode (search_main.cpp).
+bool profile_set_option(const std::string &o, const std::string &v, ProfileConfig &c, std::string &err)
+{
+    char *end = nullptr;
+    errno = 0;
+    if (o == "--search-file") { c.search_file = v; c.have_search = true; }
+    else if (o == "--cami-report-file") { c.report_file = v; c.have_report = true; }
+    else if (o == "--seq-abundance-file") c.seq_abundance_file = v;
+    else if (o == "--binning-file") { c.binning_file = v; c.have_binning = true; }
+    else if (o == "--sample-id") { c.sample_id = v; c.have_sample = true; }
+    else if (o == "--min-abundance") {
+        const double x = strtod(v.c_str(), &end);
+        if (v.empty() || *end || errno) { err = "Value parse failed for " + o + ": Argument " + v + " could not be parsed as type double."; return false; }
+        if (!(x >= 0.0 && x <= 1.0)) {
+            err = "Validation failed for option " + o + ": Value " + std::to_string(x) + " is not in range [" + std::to_string(0.0) + "," + std::to_string(1.0) + "].";
+            return false;
+        }
+        c.threshold = x;
+    } else {
+        const long x = strtol(v.c_str(), &end, 10);
+        if (v.empty() || *end || errno) { err = "Value parse failed for " + o + ": Argument " + v + " could not be parsed as an integer."; return false; }
+        const long lo = o == "--em-steps" ? 1 : 0, hi = o == "--em-steps" ? 1000 : 1023;
+        if (x < lo || x > hi) {
+            err = "Validation failed for option " + o + ": Value " + std::to_string(x) + " is not in range [" + std::to_string(lo) + "," + std::to_string(hi) + "].";
+            return false;
+        }
+        if (o == "--em-steps") c.em_steps = x;
+        else c.device = (int)x;
+    }
+    return true;
+}
+
+// What the part after the device pipeline needs to know about the names behind the CSR's numbers: reads and references are
+// numbered in byte-wise order of their names.  `taxor profile` answers from the lines of its search file, `taxor search` from the
+// read ids it kept and the species table of the index.
+struct ProfileNames {
+    uint64_t n_reads = 0, n_refs = 0;
+    const uint64_t *read_off = nullptr;                                   // [n_reads + 1]
+    std::function<std::string_view(uint64_t)> read_id;                    // read -> its id, cut at the first space
+    std::function<std::string_view(uint64_t)> accession;                  // reference -> accession
+    std::function<std::string_view(uint64_t)> tax_id_str, tax_str;        // reference -> TAX_ID_STR / TAX_STR of its first line (:142-146)
+    std::function<std::string_view(uint64_t)> match_tax_id;               // match -> TAXID of its original line
+};
+
+// abundances (:734-738,:743-794), rank roll-up, the two CAMI files and the binning file, from the device's results.  Returns "" or
+// the error's text.
+std::string profile_write_outputs(const ProfileConfig &c, const taxor_profile_results &res, const ProfileNames &nm)
+{
+    const uint64_t R = nm.n_reads, F = nm.n_refs;
+    std::map<std::string, std::pair<std::string, std::string>> taxpath;      // accession -> (TAX_ID_STR, TAX_STR) (:142-146)
+    for (uint64_t x = 0; x < F; ++x)
+        if (res.has_prior[x]) taxpath.emplace(std::string(nm.accession(x)), std::make_pair(std::string(nm.tax_id_str(x)), std::string(nm.tax_str(x))));
+    std::map<std::string, double> seq_ab, gen_ab;
+    for (uint64_t x = 0; x < F; ++x)
+        if (res.has_prior[x]) seq_ab.emplace(std::string(nm.accession(x)), exp(res.log_prior[x]));
+    seq_ab.emplace("unclassified", exp(res.log_unclassified));               // insert: an accession of that name keeps its own value (:734)
+    {
+        double sum_avg_cov = 0.0;
+        std::vector<double> cov(F, 0.0);
+        for (uint64_t x = 0; x < F; ++x)
+            if (res.has_prior[x]) {
+                cov[x] = (double)res.ref_nts[x] / (double)res.taxa_len[x];
+                sum_avg_cov += cov[x];
+            }
+        const double log_sum = log(sum_avg_cov);
+        for (uint64_t x = 0; x < F; ++x)
+            if (res.has_prior[x]) gen_ab.emplace(std::string(nm.accession(x)), exp(log(cov[x] + 0.000000000001) - log_sum));
+    }
+    std::string err;
+    if (!c.seq_abundance_file.empty()) {
+        std::map<std::string, ProfileRank> ranks;
+        if (!profile_rank_rollup(std::vector<std::pair<std::string, double>>(seq_ab.begin(), seq_ab.end()), taxpath, ranks, err)) return err;
+        if (!profile_write_abundances(c.seq_abundance_file, ranks, c.sample_id, c.threshold, true)) return "cannot write " + c.seq_abundance_file;
+    }
+    {
+        std::map<std::string, ProfileRank> ranks;
+        if (!profile_rank_rollup(std::vector<std::pair<std::string, double>>(gen_ab.begin(), gen_ab.end()), taxpath, ranks, err)) return err;
+        if (!profile_write_abundances(c.report_file, ranks, c.sample_id, c.threshold, false)) return "cannot write " + c.report_file;
+    }
+    // ---- binning (profile_output.hpp:79-98): the first best match's tax_id as its ORIGINAL line has it; a read whose matches were
+    //      all erased is not listed
+    {
+        std::string o = "@SampleID:" + c.sample_id + "\n@Version:0.10.0\n@@SEQUENCEID\tTAXID\n";
+        for (uint64_t r = 0; r < R; ++r) {
+            bool present = false;
+            uint64_t first_best = ~0ull;
+            for (uint64_t i = nm.read_off[r]; i < nm.read_off[r + 1]; ++i) {
+                present |= res.alive[i] != 0 || res.best[i] != 0;
+                if (first_best == ~0ull && res.best[i]) first_best = i;
+            }
+            if (!present) continue;
+            o.append(nm.read_id(r));
+            o += "\t";
+            if (first_best != ~0ull) o.append(nm.match_tax_id(first_best));
+            else o += "-";
+            o += "\n";
+        }
+        FILE *f = fopen(c.binning_file.c_str(), "wb");
+        if (!f || fwrite(o.data(), 1, o.size(), f) != o.size() || fclose(f) != 0) return "cannot write " + c.binning_file;
+    }
+    return "";
+}
+
 int profile_command(int argc, char **argv)
 {
     const double t_start = now();
@@ -229,30 +333,8 @@ int profile_command(int argc, char **argv)
             o == "--min-abundance" || o == "--em-steps" || o == "--gpu") {
             if (i + 1 >= args.size()) return profile_error("Missing value for option " + o);
             const std::string v = args[++i];
-            char *end = nullptr;
-            errno = 0;
-            if (o == "--search-file") { c.search_file = v; c.have_search = true; }
-            else if (o == "--cami-report-file") { c.report_file = v; c.have_report = true; }
-            else if (o == "--seq-abundance-file") c.seq_abundance_file = v;
-            else if (o == "--binning-file") { c.binning_file = v; c.have_binning = true; }
-            else if (o == "--sample-id") { c.sample_id = v; c.have_sample = true; }
-            else if (o == "--min-abundance") {
-                const double x = strtod(v.c_str(), &end);
-                if (v.empty() || *end || errno) return profile_error("Value parse failed for " + o + ": Argument " + v + " could not be parsed as type double.");
-                if (!(x >= 0.0 && x <= 1.0))
-                    return profile_error("Validation failed for option " + o + ": Value " + std::to_string(x) + " is not in range [" + std::to_string(0.0) + "," +
-                                         std::to_string(1.0) + "].");
-                c.threshold = x;
-            } else {
-                const long x = strtol(v.c_str(), &end, 10);
-                if (v.empty() || *end || errno) return profile_error("Value parse failed for " + o + ": Argument " + v + " could not be parsed as an integer.");
-                const long lo = o == "--em-steps" ? 1 : 0, hi = o == "--em-steps" ? 1000 : 1023;
-                if (x < lo || x > hi)
-                    return profile_error("Validation failed for option " + o + ": Value " + std::to_string(x) + " is not in range [" + std::to_string(lo) + "," +
-                                         std::to_string(hi) + "].");
-                if (o == "--em-steps") c.em_steps = x;
-                else c.device = (int)x;
-            }
+            std::string err;
+            if (!profile_set_option(o, v, c, err)) return profile_error(err);
         } else
             return profile_error("Unknown option " + o + ". In case this is meant to be a non-option/argument/parameter, please specify the start of "
                                  "non-options with '--'. See -h/--help for program information.");
@@ -397,60 +479,19 @@ int profile_command(int argc, char **argv)
     printf("Number of EM steps needed: %u\n", res.em_steps_needed);
     fflush(stdout);
     const double t_device = now();
-    // ---- abundances (:734-738,:743-794), the species in key order
-    std::map<std::string, std::pair<std::string, std::string>> taxpath;      // accession -> (TAX_ID_STR, TAX_STR) (:142-146)
-    for (uint64_t x = 0; x < F; ++x)
-        if (res.has_prior[x]) {
-            const ProfileLine *L = acc_first[acc_order[x]];
-            taxpath.emplace(std::string(accs[acc_order[x]]), std::make_pair(std::string(L->tax_id_str), std::string(L->tax_str)));
-        }
-    std::map<std::string, double> seq_ab, gen_ab;
-    for (uint64_t x = 0; x < F; ++x)
-        if (res.has_prior[x]) seq_ab.emplace(std::string(accs[acc_order[x]]), exp(res.log_prior[x]));
-    seq_ab.emplace("unclassified", exp(res.log_unclassified));               // insert: an accession of that name keeps its own value (:734)
+    // ---- abundances, rank roll-up and the three files
     {
-        double sum_avg_cov = 0.0;
-        std::vector<double> cov(F, 0.0);
-        for (uint64_t x = 0; x < F; ++x)
-            if (res.has_prior[x]) {
-                cov[x] = (double)res.ref_nts[x] / (double)res.taxa_len[x];
-                sum_avg_cov += cov[x];
-            }
-        const double log_sum = log(sum_avg_cov);
-        for (uint64_t x = 0; x < F; ++x)
-            if (res.has_prior[x]) gen_ab.emplace(std::string(accs[acc_order[x]]), exp(log(cov[x] + 0.000000000001) - log_sum));
-    }
-    std::string err;
-    if (!c.seq_abundance_file.empty()) {
-        std::map<std::string, ProfileRank> ranks;
-        if (!profile_rank_rollup(std::vector<std::pair<std::string, double>>(seq_ab.begin(), seq_ab.end()), taxpath, ranks, err)) return profile_error(err);
-        if (!profile_write_abundances(c.seq_abundance_file, ranks, c.sample_id, c.threshold, true)) return profile_error("cannot write " + c.seq_abundance_file);
-    }
-    {
-        std::map<std::string, ProfileRank> ranks;
-        if (!profile_rank_rollup(std::vector<std::pair<std::string, double>>(gen_ab.begin(), gen_ab.end()), taxpath, ranks, err)) return profile_error(err);
-        if (!profile_write_abundances(c.report_file, ranks, c.sample_id, c.threshold, false)) return profile_error("cannot write " + c.report_file);
-    }
-    // ---- binning (profile_output.hpp:79-98): the first best match's tax_id as its ORIGINAL line has it; a read whose matches were
-    //      all erased is not listed
-    {
-        std::string o = "@SampleID:" + c.sample_id + "\n@Version:0.10.0\n@@SEQUENCEID\tTAXID\n";
-        for (uint64_t r = 0; r < R; ++r) {
-            bool present = false;
-            const ProfileLine *first_best = nullptr;
-            for (uint64_t i = off[r]; i < off[r + 1]; ++i) {
-                present |= res.alive[i] != 0 || res.best[i] != 0;
-                if (!first_best && res.best[i]) first_best = match_line[i];
-            }
-            if (!present) continue;
-            o.append(reads[read_order[r]].id);
-            o += "\t";
-            if (first_best) o.append(first_best->tax_id);
-            else o += "-";
-            o += "\n";
-        }
-        FILE *f = fopen(c.binning_file.c_str(), "wb");
-        if (!f || fwrite(o.data(), 1, o.size(), f) != o.size() || fclose(f) != 0) return profile_error("cannot write " + c.binning_file);
+        ProfileNames nm;
+        nm.n_reads = R;
+        nm.n_refs = F;
+        nm.read_off = off.data();
+        nm.read_id = [&](uint64_t r) { return reads[read_order[r]].id; };
+        nm.accession = [&](uint64_t x) { return accs[acc_order[x]]; };
+        nm.tax_id_str = [&](uint64_t x) { return acc_first[acc_order[x]]->tax_id_str; };
+        nm.tax_str = [&](uint64_t x) { return acc_first[acc_order[x]]->tax_str; };
+        nm.match_tax_id = [&](uint64_t i) { return match_line[i]->tax_id; };
+        const std::string err = profile_write_outputs(c, res, nm);
+        if (!err.empty()) return profile_error(err);
     }
     const double t_end = now();
     fprintf(stderr, "taxor profile: %llu reads, %llu references, %llu matches, %llu reference pairs, %u EM iterations; seconds: parse %.3f, "

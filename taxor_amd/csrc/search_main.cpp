@@ -219,7 +219,19 @@ void usage()
             "  --ixf-layout <spec>      search an index whose fingerprint vectors are laid out otherwise than data[row*stride + bin]\n"
             "                           (the spec `taxor verify --variants` / `taxor pin` print, e.g. bin-major,unpadded,segment-major);\n"
             "                           they are transposed on the device while the index is uploaded\n"
-            "  --expect <tsv>           compare the output per read with a TSV the reference wrote for the same input (exit 3 if it differs)\n");
+            "  --expect <tsv>           compare the output per read with a TSV the reference wrote for the same input (exit 3 if it differs)\n"
+            "search to profile in one run (the options of `taxor profile`; results go from the device's search buffers into the profile's\n"
+            "device pipeline, no TSV is written or parsed in between):\n"
+            "  --cami-report-file <f>   CAMI profile of genomic abundances      } all three are required as soon as one of the options\n"
+            "  --binning-file <f>       CAMI binning file (read -> taxid)       } of this group is given; --output-file is then optional\n"
+            "  --sample-id <id>         identifier of the sample                } (given, the TSV is written as well)\n"
+            "  --seq-abundance-file <f> sequence abundances in CAMI format (including unclassified reads)\n"
+            "  --min-abundance <0..1>   minimum abundance to report (default 0.001)\n"
+            "  --em-steps <1..1000>     steps of the expectation maximisation (default 100)\n"
+            "                           Limits of this mode: ONE index file and ONE device (--gpus above 1, a --gpu-list of several\n"
+            "                           devices and a comma list of index files are refused), and every read id -- the header up to its\n"
+            "                           first space -- must occur once: `taxor profile` merges the lines of reads that share an id into\n"
+            "                           one read, this mode refuses such input and names the id.\n");
 }
 
 double now()
@@ -768,6 +780,159 @@ uint64_t fnv1a(const char *p, size_t n)
 #include "build_cmd.h"
 #include "profile_cmd.h"
 
+// ---- search to profile in one run (`taxor search --cami-report-file ... --binning-file ... --sample-id ...`).
+// The GPU workers hand every batch's device-resident results to a profile feed (profile_feed.hip); the host keeps the read ids, cut
+// at the first space (taxor_profile.cpp:124-125), in input order.  At the end: rank the ids byte-wise, finish the feed, run the
+// profile, write the three files through the part `taxor profile` writes them with (profile_write_outputs).
+struct FusedProfile {
+    taxor_gpu_profile_feed *feed = nullptr;
+    const taxor_hixf_meta *meta = nullptr;
+    std::atomic<uint64_t> next_read{0};        // the next batch's first index in the feed
+    double t_feed = 0;                         // seconds inside taxor_gpu_profile_feed_add_batch, summed over workers
+    std::vector<uint32_t> bin_species;         // user bin -> species (the first that names it, species[0] if none: taxor_search.cpp:172-178,289)
+    std::vector<int32_t> ref_of_bin;
+    std::vector<std::string_view> accs;        // distinct accessions of the index in byte-wise order: reference id -> accession
+    std::string id_data;                       // read ids in input order
+    std::vector<uint64_t> id_off{0}, feed_index;   // feed_index[i] = the index input read i has in the feed
+
+    void begin(const taxor_hixf_view *view, const taxor_hixf_meta *m, int device)
+    {
+        meta = m;
+        if (m->n_species == 0) die("the index names no species: nothing to profile against");
+        const uint64_t nb = view->n_user_bins;
+        bin_species.assign(nb, 0u);
+        for (uint64_t i = m->n_species; i-- > 0;)
+            if (m->species[i].user_bin < nb) bin_species[m->species[i].user_bin] = (uint32_t)i;
+        for (uint64_t u = 0; u < nb; ++u) accs.emplace_back(m->species[bin_species[u]].accession_id);
+        std::sort(accs.begin(), accs.end());
+        accs.erase(std::unique(accs.begin(), accs.end()), accs.end());
+        ref_of_bin.resize(nb);
+        std::vector<uint64_t> ref_len_of_bin(nb);
+        for (uint64_t u = 0; u < nb; ++u) {
+            const taxor_species &sp = m->species[bin_species[u]];
+            ref_of_bin[u] = (int32_t)(std::lower_bound(accs.begin(), accs.end(), std::string_view(sp.accession_id)) - accs.begin());
+            ref_len_of_bin[u] = sp.seq_len;
+        }
+        if (taxor_gpu_profile_feed_create(device, nb, ref_of_bin.data(), ref_len_of_bin.data(), accs.size(), &feed) != TAXOR_OK) die(taxor_gpu_last_error());
+    }
+
+    // one chunk, in input order (the sequencer)
+    void take_ids(const Batch &bt)
+    {
+        for (size_t r = 0; r < bt.ids.size(); ++r) {
+            const char *p = bt.ids.ptr(r);
+            size_t n = bt.ids.len(r);
+            if (const void *sp = memchr(p, ' ', n)) n = (size_t)((const char *)sp - p);
+            id_data.append(p, n);
+            id_off.push_back(id_data.size());
+            feed_index.push_back(bt.feed_first + r);
+        }
+    }
+
+    std::string_view id(uint64_t i) const { return std::string_view(id_data.data() + id_off[i], id_off[i + 1] - id_off[i]); }
+
+    // input reads in byte-wise order of their ids (bytes compared as unsigned, like std::string::operator<): ranges sorted on
+    // `threads` threads, then merged pairwise
+    std::vector<uint32_t> sorted_reads(unsigned threads) const
+    {
+        const uint64_t n = feed_index.size();
+        std::vector<uint32_t> order(n);
+        for (uint64_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
+        auto less = [&](uint32_t a, uint32_t b) { const int c = id(a).compare(id(b)); return c != 0 ? c < 0 : a < b; };
+        const uint64_t parts = std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)threads, 16, n / 65536 + 1}));
+        std::vector<uint64_t> cut(parts + 1);
+        for (uint64_t t = 0; t <= parts; ++t) cut[t] = n * t / parts;
+        {
+            std::vector<std::thread> th;
+            for (uint64_t t = 0; t < parts; ++t) th.emplace_back([&, t] { std::sort(order.begin() + (std::ptrdiff_t)cut[t], order.begin() + (std::ptrdiff_t)cut[t + 1], less); });
+            for (auto &x : th) x.join();
+        }
+        for (uint64_t w = 1; w < parts; w *= 2) {
+            std::vector<std::thread> th;
+            for (uint64_t t = 0; t + w < parts; t += 2 * w)
+                th.emplace_back([&, t, w] {
+                    std::inplace_merge(order.begin() + (std::ptrdiff_t)cut[t], order.begin() + (std::ptrdiff_t)cut[t + w],
+                                       order.begin() + (std::ptrdiff_t)cut[std::min(parts, t + 2 * w)], less);
+                });
+            for (auto &x : th) x.join();
+        }
+        return order;
+    }
+
+    void finish(const ProfileConfig &c, unsigned threads, double seconds_search)
+    {
+        const double t0 = now();
+        const uint64_t n = feed_index.size();
+        if (n != next_read.load()) die("internal: the profile feed was given " + std::to_string(next_read.load()) + " reads, the sequencer saw " + std::to_string(n));
+        if (n >= (1ull << 32)) die("more than 2^32 - 1 reads: search to profile in one run numbers reads in 32 bits");
+        const std::vector<uint32_t> order = sorted_reads(threads);
+        for (uint64_t k = 1; k < n; ++k)
+            if (id(order[k - 1]) == id(order[k]))
+                die("read id " + std::string(id(order[k])) + " occurs twice in the query (reads " + std::to_string(order[k - 1] + 1) + " and " + std::to_string(order[k] + 1) +
+                    "); search to profile in one run needs unique read ids -- write a TSV with --output-file alone and run `taxor profile`, which merges such reads");
+        std::vector<uint64_t> rank(n);                      // by feed index
+        for (uint64_t k = 0; k < n; ++k) rank[feed_index[order[k]]] = k;
+        const double t_ranked = now();
+        taxor_gpu_profile *gp = nullptr;
+        if (taxor_gpu_profile_feed_finish(feed, rank.data(), n, &gp) != TAXOR_OK) die(taxor_gpu_last_error());
+        std::vector<uint64_t>().swap(rank);
+        if (taxor_gpu_profile_run(gp, (uint32_t)c.em_steps, 0) != TAXOR_OK) die(taxor_gpu_last_error());
+        taxor_profile_results res{};
+        taxor_profile_csr csr{};
+        const int64_t *match_bin = nullptr;
+        if (taxor_gpu_profile_results(gp, &res) != TAXOR_OK || taxor_gpu_profile_feed_matches(feed, &csr, &match_bin) != TAXOR_OK) die(taxor_gpu_last_error());
+        printf("Number of EM steps needed: %u\n", res.em_steps_needed);
+        fflush(stdout);
+        const double t_device = now();
+        // the taxonomy strings of an accession are those of its first line in the TSV (taxor_profile.cpp:142-146): of the user bin
+        // whose match comes first in input order.  That needs a look at the matches only where user bins of different species
+        // share an accession
+        std::vector<uint32_t> ref_species(accs.size(), ~0u);
+        uint64_t open_refs = 0;
+        {
+            std::vector<uint8_t> shared(accs.size(), 0);
+            for (uint64_t u = 0; u < ref_of_bin.size(); ++u) {
+                uint32_t &sp = ref_species[(uint64_t)ref_of_bin[u]];
+                if (sp == ~0u) sp = bin_species[u];
+                else if (sp != bin_species[u]) shared[(uint64_t)ref_of_bin[u]] = 1;
+            }
+            for (uint8_t x : shared) open_refs += x;
+            if (open_refs) {
+                std::vector<uint32_t> rank_of_input(n);
+                for (uint64_t k = 0; k < n; ++k) rank_of_input[order[k]] = (uint32_t)k;
+                for (uint64_t i = 0; i < n && open_refs; ++i)
+                    for (uint64_t j = csr.read_off[rank_of_input[i]]; j < csr.read_off[rank_of_input[i] + 1] && open_refs; ++j) {
+                        if (match_bin[j] < 0) continue;
+                        const uint64_t x = (uint64_t)ref_of_bin[(uint64_t)match_bin[j]];
+                        if (!shared[x]) continue;
+                        ref_species[x] = bin_species[(uint64_t)match_bin[j]];
+                        shared[x] = 0;
+                        --open_refs;
+                    }
+            }
+        }
+        ProfileNames nm;
+        nm.n_reads = n;
+        nm.n_refs = accs.size();
+        nm.read_off = csr.read_off;
+        nm.read_id = [&](uint64_t r) { return id(order[r]); };
+        nm.accession = [&](uint64_t x) { return accs[x]; };
+        nm.tax_id_str = [&](uint64_t x) { return std::string_view(meta->species[ref_species[x]].taxid_string); };
+        nm.tax_str = [&](uint64_t x) { return std::string_view(meta->species[ref_species[x]].taxnames_string); };
+        nm.match_tax_id = [&](uint64_t i) { return match_bin[i] < 0 ? std::string_view() : std::string_view(meta->species[bin_species[(uint64_t)match_bin[i]]].taxid); };
+        const std::string err = profile_write_outputs(c, res, nm);
+        if (!err.empty()) die(err);
+        const double t_end = now();
+        fprintf(stderr, "taxor search (profile): %llu reads, %llu references, %llu matches, %llu reference pairs, %u EM iterations; seconds: search %.3f "
+                        "(feed %.3f inside), rank %.3f, device %.3f (rounds %.3f, EM %.3f), write %.3f, profile total %.3f\n",
+                (unsigned long long)n, (unsigned long long)accs.size(), (unsigned long long)csr.n_matches, (unsigned long long)res.n_pairs, res.em_iterations,
+                seconds_search, t_feed, t_ranked - t0, t_device - t_ranked, res.seconds_filter, res.seconds_em, t_end - t_device, t_end - t0);
+        taxor_gpu_profile_destroy(gp);
+        taxor_gpu_profile_feed_destroy(feed);
+        feed = nullptr;
+    }
+};
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -1022,6 +1187,9 @@ int main(int argc, char **argv)
     if (argc > 1 && strcmp(argv[1], "profile") == 0) return profile_command(argc, argv);   // search TSV -> CAMI profile + binning (profile_cmd.h)
     if (argc > 1 && strcmp(argv[1], "search") == 0) a = 2;                 // `taxor search ...` like the reference
     Config cfg;
+    ProfileConfig prof;             // search to profile in one run: the options of `taxor profile` (profile_cmd.h)
+    bool profile_mode = false;
+    std::string gpus_option;        // --gpus / --gpu-list as given (named when the profile options refuse several devices)
     // seqan3::argument_parser takes a long option's value either as the next argument or attached with '='
     // ("--threads 4" / "--threads=4"); split the second form so that one loop handles both
     std::vector<std::string> args;
@@ -1068,12 +1236,20 @@ int main(int argc, char **argv)
         else if (k == "--gpus") {
             const int n = atoi(val().c_str());
             if (n < 1 || n > 64) die("Validation failed for option --gpus: Value not in range [1,64].");
+            gpus_option = k;
             cfg.gpus.clear();
             for (int i = 0; i < n; ++i) cfg.gpus.push_back(i);
         } else if (k == "--gpu-list") {
             cfg.gpus.clear();
             for (const auto &t : str_split(val(), ',')) cfg.gpus.push_back(atoi(t.c_str()));
             if (cfg.gpus.empty()) die("--gpu-list is empty");
+            gpus_option = k;
+        }
+        else if (k == "--cami-report-file" || k == "--binning-file" || k == "--sample-id" || k == "--seq-abundance-file" || k == "--min-abundance" ||
+                 k == "--em-steps") {
+            std::string err;
+            if (!profile_set_option(k, val(), prof, err)) die(err);
+            profile_mode = true;
         }
         else if (k == "--batch-reads") cfg.batch_reads = strtoull(val().c_str(), nullptr, 10);
         else if (k == "--expect") cfg.expect_file = val();
@@ -1095,7 +1271,25 @@ int main(int argc, char **argv)
         else if (k == "-h" || k == "--help" || k == "-hh" || k == "--advanced-help") { usage(); return 0; }
         else die("Unknown option " + k + ". In case this is meant to be a non-option/argument/parameter, please specify the start of non-options with '--'.");
     }
+    if (profile_mode) {            // like `taxor profile` (profile_cmd.h), and before any HIP call
+        if (!prof.have_report) die("Option --cami-report-file is required but not set.");
+        if (!prof.have_binning) die("Option --binning-file is required but not set.");
+        if (!prof.have_sample) die("Option --sample-id is required but not set.");
+    }
     if (cfg.index_file.empty()) die("Option --index-file is required but not set.");
+    if (profile_mode) {
+        if (cfg.index_file.find(',') != std::string::npos)
+            die("Validation failed for option --index-file: the profile options (--cami-report-file, --binning-file, --sample-id) take ONE index file; "
+                "search the indexes one by one, or write a TSV per index and run `taxor profile`.");
+        if (cfg.gpus.size() > 1)
+            die("Validation failed for option " + gpus_option + ": the profile options (--cami-report-file, --binning-file, --sample-id) run on ONE device; "
+                "give --gpu <id>.");
+        if (!cfg.gather.empty() && cfg.gather != "none")
+            die("Validation failed for option --gather: the profile options run on ONE device, where nothing is gathered; leave --gather out.");
+        if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
+        prof.device = cfg.gpus[0];
+    }
+    const bool write_tsv = !profile_mode || !cfg.report_file.empty();
     if (cfg.threads == 0) {
         // --threads not given.  The reference's default is one worker thread (taxor_search_configuration.hpp:17) -- there the
         // thread that classifies; here host threads only parse the query file and render text for the GPU, and one of them
@@ -1135,10 +1329,11 @@ int main(int argc, char **argv)
     printf("done!\n");
     trace("input checked");
 
-    FILE *out = fopen(cfg.report_file.c_str(), "wb");                       // search_hixf, :340-343
-    if (!out) die("cannot open output file " + cfg.report_file);
-    fputs("#QUERY_NAME\tACCESSION\tREFERENCE_NAME\tTAXID\tREF_LEN\tQUERY_LEN\tQHASH_COUNT\tQHASH_MATCH\tTAX_STR\tTAX_ID_STR\n", out);
+    FILE *out = write_tsv ? fopen(cfg.report_file.c_str(), "wb") : nullptr;  // search_hixf, :340-343
+    if (write_tsv && !out) die("cannot open output file " + cfg.report_file);
+    if (out) fputs("#QUERY_NAME\tACCESSION\tREFERENCE_NAME\tTAXID\tREF_LEN\tQUERY_LEN\tQHASH_COUNT\tQHASH_MATCH\tTAX_STR\tTAX_ID_STR\n", out);
 
+    FusedProfile fused;             // search to profile in one run (profile_mode)
     double t_index = 0, t_reads = 0, t_compute = 0, t_pin = 0, t_search = 0, t_gather = 0, t_search_wall = 0;
     uint64_t n_batches = 0, n_gpu_batches = 0;
     uint64_t total_reads = 0, total_bases = 0;
@@ -1289,8 +1484,8 @@ int main(int argc, char **argv)
         BoundedQueue<Piece> q_piece(4 * formatters + 16);
         // from here on the report goes to the file descriptor: the header line above was the last thing written through the FILE*
         // (flushed now); nothing may use `out`'s stdio buffer again until the pieces are done, or it would land out of order
-        fflush(out);
-        const int out_fd = fileno(out);
+        if (out) fflush(out);
+        const int out_fd = out ? fileno(out) : -1;
         static const uint64_t piece_bytes = [] { const char *e = tune_env("TAXOR_CLI_PIECE_KB"); const int v = e ? atoi(e) : 0; return (uint64_t)(v >= 16 ? v : 1024) << 10; }();
         std::atomic<uint64_t> out_written{0};
         double t_write = 0;            // seconds inside write()
@@ -1334,7 +1529,8 @@ int main(int argc, char **argv)
                     hd->b = std::move(cur);
                     const Batch &bt = *hd->b;
                     const size_t n = bt.ids.size();
-                    if (n == 0) { chunk_done(hd); continue; }
+                    if (profile_mode) fused.take_ids(bt);            // chunks pass here in input order
+                    if (n == 0 || !write_tsv) { chunk_done(hd); continue; }
                     // cut where the estimated text passes piece_bytes
                     const uint64_t per_tuple = line_bytes_guess.load();
                     std::vector<uint32_t> cuts{0};
@@ -1445,6 +1641,7 @@ int main(int argc, char **argv)
         std::thread releaser([h] { taxor_hixf_release_data(h); });
         const double t_search0 = now();
         const unsigned wpg = workers_per_gpu;       // with a communicator: that many searcher SETS (one searcher per device each), rounds alternate between them
+        if (profile_mode) fused.begin(view, taxor_hixf_get_meta(h), prof.device);
         std::vector<taxor_gpu_searcher *> sr(ng * wpg, nullptr);
         for (size_t g = 0; g < ng; ++g)
             for (unsigned w = 0; w < wpg; ++w)
@@ -1612,7 +1809,9 @@ int main(int argc, char **argv)
                             segs.clear();
                             for (auto &bt : group) segs.push_back({bt->bases.data(), bt->offsets.data(), bt->ids.size()});
                             const int rc = taxor_gpu_search_segments_begin(sr[wi], segs.data(), segs.size());
-                            return rc != TAXOR_OK ? rc : taxor_gpu_search_batch_end(sr[wi], &res);
+                            if (rc != TAXOR_OK) return rc;
+                            // without a TSV nothing on the host reads the tuples: they stay on the device for the profile feed
+                            return write_tsv ? taxor_gpu_search_batch_end(sr[wi], &res) : taxor_gpu_batch_sync(sr[wi]);
                         };
                         int rc = run();
                         if (rc == TAXOR_E_ALPHABET) {
@@ -1621,9 +1820,27 @@ int main(int argc, char **argv)
                             if (any) rc = run();
                         }
                         if (rc != TAXOR_OK) die(taxor_gpu_last_error());
+                        if (profile_mode) {
+                            // the batch's results go into the profile's CSR where they lie.  Chunks reach a worker in any order, so a
+                            // batch is numbered as it arrives; the sequencer, which sees the chunks in input order, notes which number
+                            // each read got (FusedProfile::take_ids)
+                            uint64_t nr = 0;
+                            for (auto &bt : group) nr += bt->ids.size();
+                            const uint64_t first = fused.next_read.fetch_add(nr);
+                            uint64_t at = first;
+                            for (auto &bt : group) { bt->feed_first = at; at += bt->ids.size(); }
+                            const double f0 = now();
+                            if (taxor_gpu_profile_feed_add_batch(fused.feed, sr[wi], first, 0) != TAXOR_OK) die(taxor_gpu_last_error());
+                            std::lock_guard<std::mutex> lk(stat_mu);
+                            fused.t_feed += now() - f0;
+                        }
                         --n_running;
                         const double t3 = now();
-                        split_results(group, res);
+                        if (write_tsv) split_results(group, res);
+                        else {
+                            std::lock_guard<std::mutex> lk(stat_mu);
+                            for (auto &bt : group) { ++n_batches; total_reads += bt->ids.size(); total_bases += bt->bases.size(); }
+                        }
                         {
                             std::lock_guard<std::mutex> lk(stat_mu);
                             t_pin += t2 - t1;
@@ -1666,6 +1883,10 @@ int main(int argc, char **argv)
         }
         for (size_t g = 0; g < ng; ++g) taxor_gpu_index_destroy(gidx[g]);
         trace("GPU memory released");
+        if (profile_mode) {
+            fused.finish(prof, cfg.threads, t_search_wall);
+            trace("profile written");
+        }
         releaser.join();
         taxor_hixf_free(h);
         trace("host index released");
@@ -1691,7 +1912,7 @@ int main(int argc, char **argv)
             for (size_t ii = 0; ii < index_files.size(); ++ii)
                 search_files(index_files[ii], {query_files[qi]}, qi + 1 == query_files.size() && ii + 1 == index_files.size());
     }
-    fclose(out);
+    if (out) fclose(out);
     trace("output closed");
     if (tune_env("TAXOR_CLI_TRACE"))
         fprintf(stderr, "[trace] %llu chunks in %llu GPU batches: pin %.3f s, search %.3f s, gather %.3f s, copy-out %.3f s (summed over workers); "
