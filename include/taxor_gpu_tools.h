@@ -230,6 +230,9 @@ typedef struct {
                                         level_requested_bytes bills each as one 64-B sector */
     uint32_t tree_stalls_recovered;  /* pieces of a small call whose one-launch traversal gave up waiting (its watchdog fired) and
                                         were classified again level by level; results are unaffected */
+    uint32_t small_pieces_rerun;     /* pieces of a small call that were classified again through the pipeline of large batches, for
+                                        any reason (a queue, the hit buffer or the result area too small, or a stall as above);
+                                        0 says that every piece of the call was assembled by the lanes' own finalize */
 } taxor_gpu_run_stats;
 int taxor_gpu_batch_stats(taxor_gpu_searcher *s, taxor_gpu_run_stats *out);
 /* Measurement aid: a searcher created while TAXOR_PROFILE_PHASES=1 is set launches instrumented instantiations of the

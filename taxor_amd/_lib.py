@@ -62,7 +62,7 @@ class RunStats(C.Structure):
                 ("query_bytes", C.c_uint64), ("query_touched_bytes", C.c_uint64), ("query_launches", C.c_uint32), ("query_ms", C.c_float),
                 ("syncmer_ms", C.c_float), ("finalize_ms", C.c_float), ("total_ms", C.c_float),
                 ("level_ms", C.c_float * 8), ("level_requested_bytes", C.c_uint64 * 8), ("level_row_reads", C.c_uint64 * 8),
-                ("level_sparse_loads", C.c_uint64 * 8), ("tree_stalls_recovered", C.c_uint32)]
+                ("level_sparse_loads", C.c_uint64 * 8), ("tree_stalls_recovered", C.c_uint32), ("small_pieces_rerun", C.c_uint32)]
 
 
 class CommStats(C.Structure):

@@ -2011,6 +2011,7 @@ int small_harvest_one(taxor_gpu_searcher *s)
         st.query_bytes += L.c->stats.query_bytes;
         st.query_touched_bytes += L.c->stats.query_touched_bytes;
         st.tree_stalls_recovered += tree_stalls;
+        ++st.small_pieces_rerun;
     } else {
         ro = o.read_off; ub = o.ub; cnt = o.cnt; nh = o.nh; nt = o.status[1];
         st.n_hashes += o.status[2];

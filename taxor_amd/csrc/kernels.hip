@@ -2107,8 +2107,7 @@ __global__ __launch_bounds__(1024) void k_finalize_small(const SmallFinalizeArgs
     __shared__ uint32_t sRoff[SMALL_FIN_MAX + 1];
     __shared__ uint32_t sCur[SMALL_FIN_MAX];
     __shared__ uint32_t sW[16];
-    __shared__ uint32_t sBig[64];
-    __shared__ uint32_t sNBig;
+    __shared__ unsigned long long sWide[SMALL_FIN_MAX / 64];      // bit l of word 4 w + j: read (64 w + l) * 4 + j has more than 64 tuples
     const uint32_t tid = threadIdx.x, n = a.n_reads;
     const uint32_t flags = a.ctr->flags;
     const uint32_t n_hits = min(a.ctr->n_hits.v, a.hit_cap);
@@ -2120,8 +2119,9 @@ __global__ __launch_bounds__(1024) void k_finalize_small(const SmallFinalizeArgs
         c[j] = r < n ? a.read_hits[r] : 0u;
         v += c[j];
         if (r < SMALL_FIN_MAX) sCur[r] = 0u;
+        const unsigned long long wide = __ballot(c[j] > 64u);
+        if (lane_id() == 0) sWide[(tid >> 6) * 4u + j] = wide;
     }
-    if (tid == 0) sNBig = 0u;
     const uint32_t incl = wave_incl_add(v);
     if (lane_id() == 63) sW[tid >> 6] = incl;
     __syncthreads();
@@ -2165,11 +2165,7 @@ __global__ __launch_bounds__(1024) void k_finalize_small(const SmallFinalizeArgs
         const uint32_t wave = tid >> 6, l = lane_id();
         for (uint32_t r = wave; r < n; r += 16u) {
             const uint32_t base = sRoff[r], m = sRoff[r + 1] - base;
-            if (m == 0u) continue;
-            if (m > 64u) {
-                if (l == 0) { const uint32_t k = atomicAdd(&sNBig, 1u); if (k < 64u) sBig[k] = r; }
-                continue;
-            }
+            if (m == 0u || m > 64u) continue;
             uint32_t key = 0xFFFFFFFFu, cnt = 0;
             int64_t ub = 0;
             if (l < m) { key = a.key[base + l]; ub = a.ub[base + l]; cnt = a.cnt[base + l]; }
@@ -2180,17 +2176,9 @@ __global__ __launch_bounds__(1024) void k_finalize_small(const SmallFinalizeArgs
         __threadfence_block();
         __syncthreads();
         // reads with more than 64 tuples (a threshold-0 read reports every leaf run): block-wide sorting network in the device
-        // scratch, then out; more than 64 such reads in one small batch are found by a second sweep
-        const uint32_t n_big = sNBig;
-        for (uint32_t bi = 0; bi < n_big; ++bi) {
-            uint32_t r;
-            if (bi < 64u) r = sBig[bi];
-            else {            // beyond the list: the bi-th read with more than 64 tuples, found by counting (block-uniform)
-                uint32_t seen = 0;
-                r = 0;
-                for (uint32_t q = 0; q < n; ++q)
-                    if (sRoff[q + 1] - sRoff[q] > 64u && seen++ == bi) { r = q; break; }
-            }
+        // scratch, then out.  Which reads those are comes from the scan's ballots, so every one of them is sorted exactly once
+        // whatever order the waves above went through theirs (the walk is block-uniform: every thread reads the same words)
+        auto sort_wide = [&](uint32_t r) {
             const uint32_t base = sRoff[r], m = sRoff[r + 1] - base;
             uint32_t N = 1;
             while (N < m) N <<= 1;
@@ -2213,7 +2201,10 @@ __global__ __launch_bounds__(1024) void k_finalize_small(const SmallFinalizeArgs
                 stage(kk - 1u);                                                // mirror within blocks of kk
                 for (uint32_t j = kk >> 2; j > 0; j >>= 1) stage(j);           // half-cleaners
             }
-        }
+        };
+        for (uint32_t wi = 0; wi < (n + 255u) / 256u * 4u; ++wi)              // the words of the waves that had reads
+            for (unsigned long long wide = sWide[wi]; wide; wide &= wide - 1ull)
+                sort_wide(((wi >> 2) * 64u + (uint32_t)__ffsll(wide) - 1u) * 4u + (wi & 3u));
         // out to the host in whole lines (scattered 8-byte stores over PCIe were most of this kernel's time)
         for (uint32_t i = tid; i < total; i += 1024u) { a.h_ub[i] = a.ub[i]; a.h_cnt[i] = a.cnt[i]; }
     }
