@@ -2,6 +2,7 @@
 // the batch pipeline (upload -> syncmers -> level-synchronous HIXF query -> DFS-ordered CSR) and the stage
 // entry points the parity tests use.  No CPU fallback exists: every compute entry point runs HIP kernels.
 #include "../../include/taxor_gpu_tools.h"
+#include "hip_host.h"
 #include "ixf_arith.h"
 #include "ixf_layout.h"
 #include "kernels.h"
@@ -11,8 +12,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -24,48 +23,16 @@ using namespace taxor;
 
 namespace {
 
-thread_local std::string g_err;
+thread_local std::string g_err;         // written through taxor_set_last_error() only (hip_host.h's fail())
 
-int fail(int code, const char *fmt, ...)
+#define HIP_TRY(expr) TAXOR_HIP_TRY_AT(expr, #expr)
+
+// growable device buffer: an eighth of slack
+template <typename T> int reserve(DeviceBuf<T> &b, size_t n)
 {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
+    HIP_TRY(b.reserve(n, n + n / 8 + 64));
+    return 0;
 }
-
-#define HIP_TRY(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return fail(TAXOR_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                          __FILE__, __LINE__);                                              \
-    } while (0)
-
-// growable device buffer
-template <typename T> struct DBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t n)
-    {
-        if (n <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = n + n / 8 + 64;
-        HIP_TRY(hipMalloc((void **)&p, want * sizeof(T)));
-        cap = want;
-        return 0;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
@@ -125,7 +92,7 @@ struct taxor_gpu_searcher {
     hipStream_t st_copy = nullptr;  // H2D of the sub-batches' bases, nothing else (streamed search_batch)
     std::vector<hipEvent_t> ev_sync_done, ev_query_done, ev_pack_done, ev_copy_done;
     hipEvent_t ev_reset = nullptr;
-    DBuf<uint32_t> d_sync_cursor;
+    DeviceBuf<uint32_t> d_sync_cursor;
     Counters *d_ctr = nullptr;
     unsigned long long *d_prof = nullptr;   // TAXOR_PROFILE_PHASES=1: per-phase cycle sums of the two big kernels
     Counters h_ctr{};
@@ -146,27 +113,27 @@ struct taxor_gpu_searcher {
     struct HostSpan { uint64_t vbegin, len; const char *ptr; };   // streamed batch: where the bases of [vbegin, vbegin+len) of the
     std::vector<HostSpan> host_spans;                              // (virtually concatenated) ASCII input live in host memory
     uint64_t n_reads = 0, n_bases = 0, mean_read_len = 1u << 20;
-    DBuf<uint8_t> d_ascii;
-    DBuf<uint64_t> d_aoff, d_poff, d_hoff;
-    DBuf<uint32_t> d_packed, d_rlen, d_hcap, d_nh, d_order;
-    DBuf<uint64_t> d_thr;
+    DeviceBuf<uint8_t> d_ascii;
+    DeviceBuf<uint64_t> d_aoff, d_poff, d_hoff;
+    DeviceBuf<uint32_t> d_packed, d_rlen, d_hcap, d_nh, d_order;
+    DeviceBuf<uint64_t> d_thr;
     std::vector<SubBatch> subs;
     uint64_t max_slots = 0, max_read_slots = 0;
     uint32_t max_sub_reads = 0;
     uint64_t packed_word_count = 0, packed_in_bytes = 0;
 
     // per-sub-batch scratch
-    DBuf<uint64_t> d_cand[2], d_hashes[2];   // double-buffered across sub-batches
-    DBuf<uint2> d_q[2], d_qs;     // work queues of two consecutive levels; the next level's queue grouped by IXF
-    DBuf<uint32_t> d_qhist;
-    DBuf<uint4> d_hits;
-    DBuf<uint32_t> d_read_hits, d_cursor, d_roff, d_biglist, d_gtab, d_scan;
+    DeviceBuf<uint64_t> d_cand[2], d_hashes[2];   // double-buffered across sub-batches
+    DeviceBuf<uint2> d_q[2], d_qs;     // work queues of two consecutive levels; the next level's queue grouped by IXF
+    DeviceBuf<uint32_t> d_qhist;
+    DeviceBuf<uint4> d_hits;
+    DeviceBuf<uint32_t> d_read_hits, d_cursor, d_roff, d_biglist, d_gtab, d_scan;
     uint32_t q_cap = 0, hit_cap = 0, gtab_stride = 0;
 
     // batch-resident output
-    DBuf<uint64_t> d_read_off;
-    DBuf<int64_t> d_out_ub;
-    DBuf<uint32_t> d_out_cnt, d_out_key;
+    DeviceBuf<uint64_t> d_read_off;
+    DeviceBuf<int64_t> d_out_ub;
+    DeviceBuf<uint32_t> d_out_cnt, d_out_key;
     uint64_t tuple_cap = 0;
     bool ran = false, synced = false;
 
@@ -182,7 +149,7 @@ struct taxor_gpu_searcher {
     struct SmallLane {
         taxor_gpu_searcher *c = nullptr;    // the lane: streams, counters, queues, hit buffers of its own
         hipEvent_t done = nullptr, copied = nullptr;   // piece finished / its bases are on the device
-        DBuf<uint8_t> d_in;                 // aoff | poff | hoff | rlen | hcap | order of the piece: ONE host-to-device copy
+        DeviceBuf<uint8_t> d_in;                 // aoff | poff | hoff | rlen | hcap | order of the piece: ONE host-to-device copy
         void *h_in = nullptr;               // its page-locked source
         size_t h_in_cap = 0;
         void *h_bases = nullptr;            // TAXOR_SMALL_STAGE=1 (experiment, profiles/r05/small_calls.txt): the piece's bases copied here by the
@@ -297,15 +264,15 @@ static int index_upload(taxor_gpu_index *idx, const taxor_hixf_view *v, void (*p
     }
     if (pieces.empty()) { if (progress) progress(pctx, idx->slab_bytes); return 0; }
     static const bool trace_up = tune_env("TAXOR_TRACE_UPLOAD") != nullptr;
-    const auto up_t0 = std::chrono::steady_clock::now();
+    const double up_t0 = now_s();
     struct UpTrace {
-        bool on; std::chrono::steady_clock::time_point t0; const std::vector<Piece> &pc; bool src;
+        bool on; double t0; const std::vector<Piece> &pc; bool src;
         ~UpTrace()
         {
             if (!on) return;
             uint64_t b = 0;
             for (const Piece &p : pc) b += p.len;
-            const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            const double dt = now_s() - t0;
             fprintf(stderr, "[upload] %.2f GB in %.3f s = %.1f GB/s (%s)\n", b / 1e9, dt, b / 1e9 / dt, src ? "source reader, page-locked staging" : "host pointers, runtime pageable path");
         }
     } up_trace{trace_up, up_t0, pieces, v->source != nullptr};
@@ -1169,8 +1136,8 @@ int ensure_scratch(taxor_gpu_searcher *s)
     const uint32_t R = std::max<uint32_t>(s->max_sub_reads, 1);
     const bool syncmer_mode = idx->w_min == 0;  // minimiser mode writes its hashes directly: no candidates, no dedup
     for (int b = 0; b < 2; ++b)
-        if ((syncmer_mode && s->d_cand[b].reserve(s->max_slots + 64)) || s->d_hashes[b].reserve(s->max_slots + 64)) return TAXOR_E_HIP;
-    if (s->d_sync_cursor.reserve(2 * (s->subs.size() + 1))) return TAXOR_E_HIP;      // block kernel + wave kernel per sub-batch
+        if ((syncmer_mode && reserve(s->d_cand[b], s->max_slots + 64)) || reserve(s->d_hashes[b], s->max_slots + 64)) return TAXOR_E_HIP;
+    if (reserve(s->d_sync_cursor, 2 * (s->subs.size() + 1))) return TAXOR_E_HIP;      // block kernel + wave kernel per sub-batch
     while (s->ev_sync_done.size() < s->subs.size() + 1) {
         hipEvent_t a, b, c;
         HIP_TRY(hipEventCreateWithFlags(&a, hipEventDisableTiming));
@@ -1190,11 +1157,11 @@ int ensure_scratch(taxor_gpu_searcher *s)
     const uint64_t hmin = std::max<uint64_t>(16ull * R, idx->leaf_runs + 64);
     if (s->q_cap < qmin) s->q_cap = (uint32_t)std::min<uint64_t>(qmin, 0x7FFFFFFFu);
     if (s->hit_cap < hmin) s->hit_cap = (uint32_t)std::min<uint64_t>(hmin, 0x7FFFFFFFu);
-    if (s->d_q[0].reserve(s->q_cap) || s->d_q[1].reserve(s->q_cap) || s->d_qs.reserve(s->q_cap) ||
-        s->d_qhist.reserve(idx->h_ixf.size() + 1))
+    if (reserve(s->d_q[0], s->q_cap) || reserve(s->d_q[1], s->q_cap) || reserve(s->d_qs, s->q_cap) ||
+        reserve(s->d_qhist, idx->h_ixf.size() + 1))
         return TAXOR_E_HIP;
-    if (s->d_hits.reserve(s->hit_cap)) return TAXOR_E_HIP;
-    if (s->d_read_hits.reserve(R) || s->d_cursor.reserve(R) || s->d_roff.reserve(R + 1) || s->d_biglist.reserve(R) || s->d_scan.reserve(R / 4096 + 8))
+    if (reserve(s->d_hits, s->hit_cap)) return TAXOR_E_HIP;
+    if (reserve(s->d_read_hits, R) || reserve(s->d_cursor, R) || reserve(s->d_roff, R + 1) || reserve(s->d_biglist, R) || reserve(s->d_scan, R / 4096 + 8))
         return TAXOR_E_HIP;
     // dedup scratch in global memory, only for reads that could select more syncmers than the LDS passes cover
     if (syncmer_mode && s->max_read_slots > SYNC_LDS_DEDUP_MAX) {
@@ -1202,13 +1169,13 @@ int ensure_scratch(taxor_gpu_searcher *s)
         while (ts < 2 * s->max_read_slots) ts <<= 1;
         if (ts > (1ull << 31)) return fail(TAXOR_E_ARG, "read too long for the dedup table");
         if (s->gtab_stride < ts) s->gtab_stride = (uint32_t)ts;
-        if (s->d_gtab.reserve((size_t)s->gtab_stride * (size_t)s->grid_sync)) return TAXOR_E_HIP;
+        if (reserve(s->d_gtab, (size_t)s->gtab_stride * (size_t)s->grid_sync)) return TAXOR_E_HIP;
     }
     const uint64_t tmin = std::max<uint64_t>(12 * s->n_reads + 1024, idx->leaf_runs + 64);   // 16 B per tuple
     if (s->tuple_cap < tmin) s->tuple_cap = tmin;
-    if (s->d_out_ub.reserve(s->tuple_cap) || s->d_out_cnt.reserve(s->tuple_cap) || s->d_out_key.reserve(s->tuple_cap))
+    if (reserve(s->d_out_ub, s->tuple_cap) || reserve(s->d_out_cnt, s->tuple_cap) || reserve(s->d_out_key, s->tuple_cap))
         return TAXOR_E_HIP;
-    if (s->d_read_off.reserve(s->n_reads + 1)) return TAXOR_E_HIP;
+    if (reserve(s->d_read_off, s->n_reads + 1)) return TAXOR_E_HIP;
     return 0;
 }
 
@@ -1502,8 +1469,8 @@ int prepare_batch(taxor_gpu_searcher *s, const char *bases, const uint64_t *offs
     std::vector<uint32_t> &rlen = s->h_rlen, &hcap = s->lay_hcap, &order = s->lay_order;
     // streamed: the first sub-batch's PCIe copy has nothing to hide behind either, so it is a quarter the size
     static const bool trace = tune_env("TAXOR_TRACE_BATCH") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto ms_since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
+    const double t0 = now_s();
+    auto ms_since = [&](double a) { return (now_s() - a) * 1e3; };
     if (int rc = layout_batch(s, offsets, n_reads, poff, rlen, hoff, hcap, order, streamed ? stream_first_div(s) : s->first_div, streamed))
         return rc;
     const double t_layout = ms_since(t0);
@@ -1511,10 +1478,10 @@ int prepare_batch(taxor_gpu_searcher *s, const char *bases, const uint64_t *offs
     const uint64_t a0 = offsets[0], nb = offsets[n_reads] - a0;
     s->n_bases = nb;
     s->mean_read_len = n_reads ? nb / n_reads : (1u << 20);
-    if (s->d_ascii.reserve(nb + 64) || s->d_aoff.reserve(n_reads + 1) || s->d_poff.reserve(n_reads + 1) ||
-        s->d_hoff.reserve(n_reads + 1) || s->d_rlen.reserve(n_reads + 1) || s->d_hcap.reserve(n_reads + 1) ||
-        s->d_nh.reserve(n_reads + 1) || s->d_thr.reserve(n_reads + 1) || s->d_order.reserve(n_reads + 1) ||
-        s->d_packed.reserve(s->packed_word_count))
+    if (reserve(s->d_ascii, nb + 64) || reserve(s->d_aoff, n_reads + 1) || reserve(s->d_poff, n_reads + 1) ||
+        reserve(s->d_hoff, n_reads + 1) || reserve(s->d_rlen, n_reads + 1) || reserve(s->d_hcap, n_reads + 1) ||
+        reserve(s->d_nh, n_reads + 1) || reserve(s->d_thr, n_reads + 1) || reserve(s->d_order, n_reads + 1) ||
+        reserve(s->d_packed, s->packed_word_count))
         return TAXOR_E_HIP;
     aoff.resize(n_reads + 1);
     for (uint64_t r = 0; r <= n_reads; ++r) aoff[r] = offsets[r] - a0;
@@ -1777,8 +1744,8 @@ int small_enqueue(taxor_gpu_searcher *s, uint32_t li, const char *bases, const u
 {
     const taxor_gpu_index *idx = s->idx;
     static const bool trace = tune_env("TAXOR_TRACE_BATCH") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto us = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
+    const double t0 = now_s();
+    auto us = [&] { return (now_s() - t0) * 1e6; };
     double t_ready = 0, t_layout = 0, t_scratch = 0, t_arrays = 0, t_bases = 0, t_hash = 0, t_query = 0;
     if (int rc = small_lane_ready(s, li, n, SMALL_TUPLES)) return rc;
     t_ready = us();
@@ -1839,7 +1806,7 @@ int small_enqueue(taxor_gpu_searcher *s, uint32_t li, const char *bases, const u
     c->subs.assign(1, SubBatch{0, n, n_long, slots, 0, nb});
     const size_t cap_before = c->d_read_hits.cap, qcap_before = c->d_q[0].cap;
     Counters *ctr_before = c->d_ctr;
-    if (L.d_in.reserve(in_bytes) || c->d_ascii.reserve(nb + 64) || c->d_packed.reserve(words + 16) || c->d_nh.reserve(n + 1) || c->d_thr.reserve(n + 1))
+    if (reserve(L.d_in, in_bytes) || reserve(c->d_ascii, nb + 64) || reserve(c->d_packed, words + 16) || reserve(c->d_nh, n + 1) || reserve(c->d_thr, n + 1))
         return TAXOR_E_HIP;
     if (int rc = ensure_scratch(c)) return rc;
     if (c->d_read_hits.cap != cap_before || c->d_ctr != ctr_before || c->d_q[0].cap != qcap_before) L.fresh = true;
@@ -1979,10 +1946,10 @@ int small_harvest_one(taxor_gpu_searcher *s)
     taxor_gpu_searcher::SmallLane &L = s->lanes[pc.lane];
     taxor_gpu_run_stats &st = s->stats;
     {   // the caller waits for a fraction of a millisecond: poll (a blocking wait's wake-up is tens of microseconds of it)
-        const auto t0 = std::chrono::steady_clock::now();
+        const double t0 = now_s();
         hipError_t e;
         while ((e = hipEventQuery(L.done)) == hipErrorNotReady)
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) { e = hipEventSynchronize(L.done); break; }
+            if (now_s() - t0 > 5e-3) { e = hipEventSynchronize(L.done); break; }
         if (e != hipSuccess) return fail(TAXOR_E_HIP, "small batch: %s", hipGetErrorString(e));
     }
     const SmallOut o = small_out(L, L.h_out);
@@ -2139,7 +2106,7 @@ int small_device_results(taxor_gpu_searcher *s)
 {
     if (!s->dev_results_stale) return 0;
     const uint64_t nr = s->n_reads, nt = s->h_ctr.tuple_total;
-    if (s->d_read_off.reserve(nr + 1) || s->d_nh.reserve(nr + 1) || s->d_out_ub.reserve(nt + 1) || s->d_out_cnt.reserve(nt + 1)) return TAXOR_E_HIP;
+    if (reserve(s->d_read_off, nr + 1) || reserve(s->d_nh, nr + 1) || reserve(s->d_out_ub, nt + 1) || reserve(s->d_out_cnt, nt + 1)) return TAXOR_E_HIP;
     HIP_TRY(hipMemcpyAsync(s->d_read_off.p, s->h_read_off.data(), (nr + 1) * 8, hipMemcpyHostToDevice, s->st));
     if (nr) HIP_TRY(hipMemcpyAsync(s->d_nh.p, s->h_nh.data(), nr * 4, hipMemcpyHostToDevice, s->st));
     if (nt) {
@@ -2291,7 +2258,7 @@ extern "C" __attribute__((visibility("hidden"))) int taxor_searcher_device_read_
     if (s->small_active) {
         const uint64_t nr = s->n_reads;
         if (s->h_rlen.size() != nr) return fail(TAXOR_E_INTERNAL, "device_read_lengths: the small call kept no read lengths");
-        if (s->d_rlen.reserve(nr + 1)) return TAXOR_E_HIP;
+        if (reserve(s->d_rlen, nr + 1)) return TAXOR_E_HIP;
         if (nr) HIP_TRY(hipMemcpyAsync(s->d_rlen.p, s->h_rlen.data(), nr * 4, hipMemcpyHostToDevice, s->st));
         HIP_TRY(hipStreamSynchronize(s->st));
     }
@@ -2411,8 +2378,8 @@ extern "C" int taxor_gpu_search_batch(taxor_gpu_searcher *s, const char *bases, 
                                       taxor_gpu_results *out)
 {
     static const bool trace = tune_env("TAXOR_TRACE_BATCH") != nullptr;   // phase times of this call on stderr
-    const auto t0 = std::chrono::steady_clock::now();
-    auto ms_since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
+    const double t0 = now_s();
+    auto ms_since = [&](double a) { return (now_s() - a) * 1e3; };
     if (int rc = taxor_gpu_search_batch_begin(s, bases, offsets, n_reads)) return rc;
     const double t_enq = ms_since(t0);
     const int rc = taxor_gpu_search_batch_end(s, out);
@@ -2474,7 +2441,7 @@ int stage_hash_list(taxor_gpu_searcher *s, const uint64_t *hashes, uint64_t n, u
     s->max_slots = n + 64;
     s->max_read_slots = 16;
     s->max_sub_reads = 1;
-    if (s->d_hoff.reserve(2) || s->d_nh.reserve(2) || s->d_thr.reserve(2)) return TAXOR_E_HIP;
+    if (reserve(s->d_hoff, 2) || reserve(s->d_nh, 2) || reserve(s->d_thr, 2)) return TAXOR_E_HIP;
     if (int rc = ensure_scratch(s)) return rc;
     const uint64_t zero = 0;
     const uint32_t nh = (uint32_t)n;

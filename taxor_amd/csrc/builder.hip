@@ -44,6 +44,7 @@
 // set in HBM) -- for a child of leaf bins not a copy but the child's OWN key range plus one mark byte per key (BinJob::keep: the
 // kernels skip unmarked keys), so that a level's unions cost an eighth of its keys in memory instead of all of them again.
 #include "../../include/taxor_gpu_tools.h"
+#include "hip_host.h"
 #include "ixf_arith.h"
 #include "kernels.h"
 #include "keyset.h"
@@ -51,7 +52,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -61,7 +61,6 @@
 
 using namespace taxor;
 
-extern "C" __attribute__((visibility("hidden"))) void taxor_set_last_error(const char *msg);
 
 namespace {
 
@@ -435,14 +434,6 @@ __global__ __launch_bounds__(BB) void k_synth_keys(uint64_t *out, uint64_t first
     for (uint64_t i = (uint64_t)blockIdx.x * BB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BB) out[i] = synth_key(first + i, salt);
 }
 
-int bfail(int code, const std::string &m)
-{
-    taxor_set_last_error(m.c_str());
-    return code;
-}
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 } // namespace
 
 // library-internal accessors implemented in api.hip
@@ -458,11 +449,7 @@ extern "C" __attribute__((visibility("hidden"))) void taxor_index_set_build_ctx(
 
 namespace {
 
-#define E_TRY(expr)                                                                                      \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return bfail(TAXOR_E_HIP, std::string("build: ") + #expr + ": " + hipGetErrorString(e_)); \
-    } while (0)
+#define E_TRY(expr) TAXOR_HIP_TRY_PREFIX("build", expr, #expr)
 
 // The chunk engine: scratch for one chunk of bins, reused from chunk to chunk, on a stream of its own.
 struct Engine {
@@ -547,7 +534,7 @@ struct Engine {
             if (d_w) (void)hipFree(d_w);
             d_w = nullptr;
             w_bytes = 0;
-            if (hipMalloc(&d_w, wb) != hipSuccess) return bfail(TAXOR_E_NOMEM, "build: no device memory for the peeling state");
+            if (hipMalloc(&d_w, wb) != hipSuccess) return fail(TAXOR_E_NOMEM, "build: no device memory for the peeling state");
             w_bytes = wb;
         }
         if (slots > cap_slots) {
@@ -557,7 +544,7 @@ struct Engine {
             cap_slots = 0;
             if (hipMalloc((void **)&d_list, slots * 8) != hipSuccess || hipMalloc((void **)&d_log, slots * 4) != hipSuccess ||
                 hipMalloc((void **)&d_pushed, slots * 2) != hipSuccess)
-                return bfail(TAXOR_E_NOMEM, "build: no device memory for the peeling work list");
+                return fail(TAXOR_E_NOMEM, "build: no device memory for the peeling work list");
             cap_slots = slots;
         }
         if (jobs > cap_jobs) {
@@ -567,7 +554,7 @@ struct Engine {
             cap_jobs = 0;
             if (hipMalloc((void **)&d_jobs, jobs * sizeof(BinJob)) != hipSuccess || hipMalloc((void **)&d_job_peeled, jobs * 8) != hipSuccess ||
                 hipMalloc((void **)&d_skip, jobs) != hipSuccess)
-                return bfail(TAXOR_E_NOMEM, "build: no device memory for the bin table");
+                return fail(TAXOR_E_NOMEM, "build: no device memory for the bin table");
             cap_jobs = jobs;
         }
         stats.scratch_bytes = std::max<uint64_t>(stats.scratch_bytes, w_bytes + cap_slots * 14 + cap_jobs * (sizeof(BinJob) + 9) + sizeof(Ctl));
@@ -611,10 +598,10 @@ struct Engine {
             wide |= j.n_keys >= WIDE_KEYS;
             max_keys = std::max<uint64_t>(max_keys, j.n_keys);
             group_rows[j.group] = 3ull * j.seg_len;
-            if (j.n_kept > 3ull * j.seg_len) return bfail(TAXOR_E_ARG, "build: a bin holds more keys than its IXF has rows");
-            if (j.n_keys >= 0xFFFFFFFFull) return bfail(TAXOR_E_ARG, "build: more than 2^32 - 2 keys in one bin");
+            if (j.n_kept > 3ull * j.seg_len) return fail(TAXOR_E_ARG, "build: a bin holds more keys than its IXF has rows");
+            if (j.n_keys >= 0xFFFFFFFFull) return fail(TAXOR_E_ARG, "build: more than 2^32 - 2 keys in one bin");
         }
-        if (ns >= 0xFFFFFFF8ull || jobs.size() >= (1ull << 31)) return bfail(TAXOR_E_INTERNAL, "build: chunk too large");
+        if (ns >= 0xFFFFFFF8ull || jobs.size() >= (1ull << 31)) return fail(TAXOR_E_INTERNAL, "build: chunk too large");
         E_TRY(hipSetDevice(device));
         const int rc = ensure(ns, jobs.size(), wide);
         if (rc != TAXOR_OK) return rc;
@@ -665,7 +652,7 @@ int Engine::run_typed(std::vector<BinJob> &jobs, uint32_t n_groups, std::vector<
             if (d_items) (void)hipFree(d_items);
             d_items = nullptr;
             cap_items = 0;
-            if (hipMalloc((void **)&d_items, (items.size() + items.size() / 4) * sizeof(CountItem)) != hipSuccess) return bfail(TAXOR_E_NOMEM, "build: no device memory for the count items");
+            if (hipMalloc((void **)&d_items, (items.size() + items.size() / 4) * sizeof(CountItem)) != hipSuccess) return fail(TAXOR_E_NOMEM, "build: no device memory for the count items");
             cap_items = items.size() + items.size() / 4;
         }
         E_TRY(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(CountItem), hipMemcpyHostToDevice, st));
@@ -700,7 +687,7 @@ int Engine::run_typed(std::vector<BinJob> &jobs, uint32_t n_groups, std::vector<
         return TAXOR_OK;
     };
     while (!done) {
-        if (launched >= MAX_ROUNDS) return bfail(TAXOR_E_INTERNAL, "build: peeling did not end within 16000 rounds");
+        if (launched >= MAX_ROUNDS) return fail(TAXOR_E_INTERNAL, "build: peeling did not end within 16000 rounds");
         const uint32_t lo = launched, hi = std::min(MAX_ROUNDS, launched + ROUND_BATCH);
         for (uint32_t t = lo; t < hi; ++t) hipLaunchKernelGGL((k_round<WT>), dim3(round_grid), dim3(BB), 0, st, a, t);
         launched = hi;
@@ -742,7 +729,7 @@ int Engine::run_typed(std::vector<BinJob> &jobs, uint32_t n_groups, std::vector<
         for (size_t j = 0; j < jobs.size(); ++j)
             if (got[j] != jobs[j].n_kept) group_ok[jobs[j].group] = 0;
         for (uint32_t g = 0; g < n_groups; ++g) n_failed += !group_ok[g];
-        if (!n_failed) return bfail(TAXOR_E_INTERNAL, "build: peeled keys fall short but every bin is complete");
+        if (!n_failed) return fail(TAXOR_E_INTERNAL, "build: peeled keys fall short but every bin is complete");
         std::vector<uint8_t> skip(n_groups);
         for (uint32_t g = 0; g < n_groups; ++g) skip[g] = !group_ok[g];
         E_TRY(hipMemcpyAsync(d_skip, skip.data(), n_groups, hipMemcpyHostToDevice, st));
@@ -782,7 +769,7 @@ int Engine::run_typed(std::vector<BinJob> &jobs, uint32_t n_groups, std::vector<
         E_TRY(hipStreamSynchronize(st));
         E_TRY(hipGetLastError());
         if (h_counts[1] != 0)
-            return bfail(TAXOR_E_INTERNAL, "build: " + std::to_string(h_counts[1]) + " keys do not match their own columns after construction");
+            return fail(TAXOR_E_INTERNAL, "build: " + std::to_string(h_counts[1]) + " keys do not match their own columns after construction");
     }
     for (const auto &j : jobs)
         if (group_ok[j.group]) {
@@ -865,13 +852,13 @@ int build_plans(Engine &eng, taxor_gpu_index *idx, std::vector<IxfPlan> &plans)
             // one IXF in several chunks of its bins; a bin that does not peel restarts the IXF under a new seed
             IxfPlan &p = plans[todo[0]];
             const uint64_t per_bin = 3 * p.seg_len;
-            if (per_bin > budget) return bfail(TAXOR_E_NOMEM, "build: one bin of IXF " + std::to_string(p.ixf) + " does not fit the peeling scratch");
+            if (per_bin > budget) return fail(TAXOR_E_NOMEM, "build: one bin of IXF " + std::to_string(p.ixf) + " does not fit the peeling scratch");
             bool built = false;
             const bool all_bins = p.n_with_keys == p.bins;
             while (!built) {
                 built = true;
                 const uint64_t inserted_before = eng.stats.keys_inserted, lds_before = eng.stats.keys_counted_in_lds;      // (an attempt that is thrown away does not count)
-                if (all_bins && hipMemsetAsync(p.data, 0, 3 * p.seg_len * p.stride, eng.st) != hipSuccess) return bfail(TAXOR_E_HIP, "build: clearing an IXF failed");
+                if (all_bins && hipMemsetAsync(p.data, 0, 3 * p.seg_len * p.stride, eng.st) != hipSuccess) return fail(TAXOR_E_HIP, "build: clearing an IXF failed");
                 for (uint64_t b0 = 0; b0 < p.bins && built;) {
                     uint64_t b1 = b0, s = 0, k = 0;
                     while (b1 < p.bins && (p.n[b1] == 0 || (s + per_bin <= budget && k + p.n[b1] < (1ull << 32)))) {
@@ -889,7 +876,7 @@ int build_plans(Engine &eng, taxor_gpu_index *idx, std::vector<IxfPlan> &plans)
                 if (!built) {
                     eng.stats.keys_inserted = inserted_before;
                     eng.stats.keys_counted_in_lds = lds_before;
-                    if (++p.attempts >= 32) return bfail(TAXOR_E_INTERNAL, "build: no seed peeled every bin of IXF " + std::to_string(p.ixf) + " in 32 attempts (duplicate keys inside a bin?)");
+                    if (++p.attempts >= 32) return fail(TAXOR_E_INTERNAL, "build: no seed peeled every bin of IXF " + std::to_string(p.ixf) + " in 32 attempts (duplicate keys inside a bin?)");
                     p.seed = next_seed(p.seed);
                 }
             }
@@ -904,7 +891,7 @@ int build_plans(Engine &eng, taxor_gpu_index *idx, std::vector<IxfPlan> &plans)
             IxfPlan &p = plans[members[m]];
             if (ok[m]) taxor_index_set_seed(idx, p.ixf, p.seed);
             else {
-                if (++p.attempts >= 32) return bfail(TAXOR_E_INTERNAL, "build: no seed peeled every bin of IXF " + std::to_string(p.ixf) + " in 32 attempts (duplicate keys inside a bin?)");
+                if (++p.attempts >= 32) return fail(TAXOR_E_INTERNAL, "build: no seed peeled every bin of IXF " + std::to_string(p.ixf) + " in 32 attempts (duplicate keys inside a bin?)");
                 p.seed = next_seed(p.seed);         // re-seed and rebuild every bin of this IXF, like construct_ixf.cpp:100-108
                 again.push_back(members[m]);
             }
@@ -917,7 +904,7 @@ int build_plans(Engine &eng, taxor_gpu_index *idx, std::vector<IxfPlan> &plans)
 
 int plan_ixf(taxor_gpu_index *idx, uint64_t ixf, IxfPlan &p, int *device)
 {
-    if (taxor_index_ixf_info(idx, ixf, &p.data, &p.stride, &p.seg_len, &p.bins, device)) return bfail(TAXOR_E_ARG, "build: bad index / IXF id");
+    if (taxor_index_ixf_info(idx, ixf, &p.data, &p.stride, &p.seg_len, &p.bins, device)) return fail(TAXOR_E_ARG, "build: bad index / IXF id");
     p.ixf = ixf;
     p.keys.assign(p.bins, nullptr);
     p.keep.assign(p.bins, nullptr);
@@ -984,22 +971,22 @@ extern "C" uint64_t taxor_synth_key(uint64_t i, uint64_t salt) { return synth_ke
 
 extern "C" int taxor_gpu_synth_keys(int device, uint64_t *d_out, uint64_t first, uint64_t n, uint64_t salt)
 {
-    if (!d_out && n) return bfail(TAXOR_E_ARG, "synth_keys: null output");
-    if (hipSetDevice(device) != hipSuccess) return bfail(TAXOR_E_HIP, "synth_keys: hipSetDevice failed");
+    if (!d_out && n) return fail(TAXOR_E_ARG, "synth_keys: null output");
+    if (hipSetDevice(device) != hipSuccess) return fail(TAXOR_E_HIP, "synth_keys: hipSetDevice failed");
     for (uint64_t o = 0; o < n; o += (1ull << 30)) {          // (a billion keys per launch: ~1.5 ms)
         const uint64_t m = std::min<uint64_t>(1ull << 30, n - o);
         hipLaunchKernelGGL(k_synth_keys, dim3((uint32_t)std::min<uint64_t>(8192, (m + BB - 1) / BB)), dim3(BB), 0, nullptr, d_out + o, first + o, m, salt);
     }
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return bfail(TAXOR_E_HIP, "synth_keys: kernel failed");
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(TAXOR_E_HIP, "synth_keys: kernel failed");
     return TAXOR_OK;
 }
 
 extern "C" int taxor_gpu_malloc(int device, uint64_t bytes, void **out)
 {
-    if (!out) return bfail(TAXOR_E_ARG, "taxor_gpu_malloc: null output");
+    if (!out) return fail(TAXOR_E_ARG, "taxor_gpu_malloc: null output");
     *out = nullptr;
-    if (hipSetDevice(device) != hipSuccess) return bfail(TAXOR_E_HIP, "taxor_gpu_malloc: hipSetDevice failed");
-    if (hipMalloc(out, bytes ? bytes : 8) != hipSuccess) return bfail(TAXOR_E_NOMEM, "taxor_gpu_malloc: no device memory for " + std::to_string(bytes) + " bytes");
+    if (hipSetDevice(device) != hipSuccess) return fail(TAXOR_E_HIP, "taxor_gpu_malloc: hipSetDevice failed");
+    if (hipMalloc(out, bytes ? bytes : 8) != hipSuccess) return fail(TAXOR_E_NOMEM, "taxor_gpu_malloc: no device memory for " + std::to_string(bytes) + " bytes");
     return TAXOR_OK;
 }
 
@@ -1010,12 +997,12 @@ extern "C" void taxor_gpu_free(void *p)
 
 extern "C" int taxor_gpu_memcpy_from_host(void *d_dst, const void *src, uint64_t bytes)
 {
-    return hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? TAXOR_OK : bfail(TAXOR_E_HIP, "taxor_gpu_memcpy_from_host failed");
+    return hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? TAXOR_OK : fail(TAXOR_E_HIP, "taxor_gpu_memcpy_from_host failed");
 }
 
 extern "C" int taxor_gpu_memcpy_to_host(void *dst, const void *d_src, uint64_t bytes)
 {
-    return hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? TAXOR_OK : bfail(TAXOR_E_HIP, "taxor_gpu_memcpy_to_host failed");
+    return hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? TAXOR_OK : fail(TAXOR_E_HIP, "taxor_gpu_memcpy_to_host failed");
 }
 
 // Keys from pageable host memory to the device.  One hipMemcpy of tens of GB goes through the runtime's own staging at ~10 GB/s; a
@@ -1071,27 +1058,27 @@ static int build_ixf_impl(taxor_gpu_index *idx, uint64_t ixf, const uint64_t *ke
 {
     std::vector<IxfPlan> plans(1);
     int device = 0;
-    if (!idx || !key_off) return bfail(TAXOR_E_ARG, "build_ixf: bad index / IXF id");
+    if (!idx || !key_off) return fail(TAXOR_E_ARG, "build_ixf: bad index / IXF id");
     int rc = plan_ixf(idx, ixf, plans[0], &device);
     if (rc != TAXOR_OK) return rc;
     IxfPlan &p = plans[0];
-    if (hipSetDevice(device) != hipSuccess) return bfail(TAXOR_E_HIP, "build_ixf: hipSetDevice failed");
+    if (hipSetDevice(device) != hipSuccess) return fail(TAXOR_E_HIP, "build_ixf: hipSetDevice failed");
     for (uint64_t b = 0; b < p.bins; ++b)
-        if (key_off[b + 1] < key_off[b]) return bfail(TAXOR_E_ARG, "build_ixf: key_off not monotone");
+        if (key_off[b + 1] < key_off[b]) return fail(TAXOR_E_ARG, "build_ixf: key_off not monotone");
     const uint64_t total = key_off[p.bins] - key_off[0];
     if (seed_out) *seed_out = seed0;
     if (rounds_out) *rounds_out = 0;
     if (stats_out) *stats_out = taxor_build_stats{};
     if (!total) return TAXOR_OK;
-    if (!keys) return bfail(TAXOR_E_ARG, "build_ixf: null keys");
+    if (!keys) return fail(TAXOR_E_ARG, "build_ixf: null keys");
     const double t0 = now_s();
     uint64_t *d_own = nullptr;
     const uint64_t *d_keys = keys + key_off[0];
     if (!keys_on_device) {
-        if (hipMalloc((void **)&d_own, total * 8) != hipSuccess) return bfail(TAXOR_E_NOMEM, "build_ixf: no device memory for the keys");
+        if (hipMalloc((void **)&d_own, total * 8) != hipSuccess) return fail(TAXOR_E_NOMEM, "build_ixf: no device memory for the keys");
         if (upload_keys(device, d_own, keys + key_off[0], total) != hipSuccess) {
             (void)hipFree(d_own);
-            return bfail(TAXOR_E_HIP, "build_ixf: key upload failed");
+            return fail(TAXOR_E_HIP, "build_ixf: key upload failed");
         }
         d_keys = d_own;
     }
@@ -1132,7 +1119,7 @@ static int build_hixf_impl(taxor_gpu_index *idx, const uint64_t *keys, int keys_
 {
     uint64_t n_ixf = 0;
     const uint32_t *bin_base = nullptr, *binfo = nullptr;
-    if (!idx || !key_off || taxor_index_tree(idx, &n_ixf, &bin_base, &binfo)) return bfail(TAXOR_E_ARG, "build_hixf: bad index");
+    if (!idx || !key_off || taxor_index_tree(idx, &n_ixf, &bin_base, &binfo)) return fail(TAXOR_E_ARG, "build_hixf: bad index");
     std::vector<IxfPlan> plan(n_ixf);
     int device = 0;
     for (uint64_t i = 0; i < n_ixf; ++i) {
@@ -1140,19 +1127,19 @@ static int build_hixf_impl(taxor_gpu_index *idx, const uint64_t *keys, int keys_
         if (rc != TAXOR_OK) return rc;
         plan[i].seed = seed0 + 0x9E3779B97F4A7C15ull * i;
     }
-    if (hipSetDevice(device) != hipSuccess) return bfail(TAXOR_E_HIP, "build_hixf: hipSetDevice failed");
+    if (hipSetDevice(device) != hipSuccess) return fail(TAXOR_E_HIP, "build_hixf: hipSetDevice failed");
     const uint64_t total_bins = bin_base[n_ixf];
     for (uint64_t g = 0; g < total_bins; ++g) {
-        if (key_off[g + 1] < key_off[g]) return bfail(TAXOR_E_ARG, "build_hixf: key_off not monotone");
+        if (key_off[g + 1] < key_off[g]) return fail(TAXOR_E_ARG, "build_hixf: key_off not monotone");
         if ((binfo[g] & BINFO_MERGED) && (key_off[g + 1] != key_off[g] || (gen_count && gen_count[g])))
-            return bfail(TAXOR_E_ARG, "build_hixf: a merged bin must not bring keys of its own (they come from its child)");
+            return fail(TAXOR_E_ARG, "build_hixf: a merged bin must not bring keys of its own (they come from its child)");
         if (gen_count && gen_count[g] && key_off[g + 1] != key_off[g])
-            return bfail(TAXOR_E_ARG, "build_hixf: a bin brings its keys OR has them generated, not both");
-        if (gen_count && gen_count[g] >= 0xFFFFFFFFull) return bfail(TAXOR_E_ARG, "build_hixf: more than 2^32 - 2 generated keys in one bin");
+            return fail(TAXOR_E_ARG, "build_hixf: a bin brings its keys OR has them generated, not both");
+        if (gen_count && gen_count[g] >= 0xFFFFFFFFull) return fail(TAXOR_E_ARG, "build_hixf: more than 2^32 - 2 generated keys in one bin");
     }
-    if ((gen_first == nullptr) != (gen_count == nullptr)) return bfail(TAXOR_E_ARG, "build_hixf: gen_first and gen_count come together");
+    if ((gen_first == nullptr) != (gen_count == nullptr)) return fail(TAXOR_E_ARG, "build_hixf: gen_first and gen_count come together");
     const uint64_t total = key_off[total_bins] - key_off[0];
-    if (total && !keys) return bfail(TAXOR_E_ARG, "build_hixf: null keys");
+    if (total && !keys) return fail(TAXOR_E_ARG, "build_hixf: null keys");
     if (rounds_out) *rounds_out = 0;
     if (stats_out) *stats_out = taxor_build_stats{};
     const double t0 = now_s();
@@ -1170,7 +1157,7 @@ static int build_hixf_impl(taxor_gpu_index *idx, const uint64_t *keys, int keys_
                 const uint32_t bi = binfo[bin_base[i] + b];
                 if (!(bi & BINFO_MERGED)) continue;
                 const uint64_t c = bi & 0x3FFFFFFFu;
-                if (c >= n_ixf || depth[c] >= 0) return bfail(TAXOR_E_ARG, "build_hixf: the hierarchy is not a tree");
+                if (c >= n_ixf || depth[c] >= 0) return fail(TAXOR_E_ARG, "build_hixf: the hierarchy is not a tree");
                 depth[c] = depth[i] + 1;
                 parent[c] = (int64_t)i;
                 max_depth = std::max(max_depth, depth[c]);
@@ -1189,10 +1176,10 @@ static int build_hixf_impl(taxor_gpu_index *idx, const uint64_t *keys, int keys_
     double t_upload = 0.0;
     if (total && !keys_on_device) {
         const double tu0 = now_s();
-        if (hipMalloc((void **)&d_leaf, total * 8) != hipSuccess) return bfail(TAXOR_E_NOMEM, "build_hixf: no device memory for the keys");
+        if (hipMalloc((void **)&d_leaf, total * 8) != hipSuccess) return fail(TAXOR_E_NOMEM, "build_hixf: no device memory for the keys");
         if (upload_keys(device, d_leaf, keys + key_off[0], total) != hipSuccess) {
             cleanup();
-            return bfail(TAXOR_E_HIP, "build_hixf: key upload failed");
+            return fail(TAXOR_E_HIP, "build_hixf: key upload failed");
         }
         d_keys = d_leaf;
         t_upload = now_s() - tu0;
@@ -1269,14 +1256,14 @@ static int build_hixf_impl(taxor_gpu_index *idx, const uint64_t *keys, int keys_
         const double tu = now_s();
         uint64_t *arena = nullptr, *concat = nullptr;
         uint8_t *mark = nullptr;
-        if (mark_bytes && !(mark = ctx->marks(d & 1, mark_bytes))) { rc = bfail(TAXOR_E_NOMEM, "build_hixf: no device memory for the duplicate marks of one level"); break; }
-        if (arena_keys && hipMalloc((void **)&arena, arena_keys * 8) != hipSuccess) { rc = bfail(TAXOR_E_NOMEM, "build_hixf: no device memory for the key unions of one level"); break; }
+        if (mark_bytes && !(mark = ctx->marks(d & 1, mark_bytes))) { rc = fail(TAXOR_E_NOMEM, "build_hixf: no device memory for the duplicate marks of one level"); break; }
+        if (arena_keys && hipMalloc((void **)&arena, arena_keys * 8) != hipSuccess) { rc = fail(TAXOR_E_NOMEM, "build_hixf: no device memory for the key unions of one level"); break; }
         arenas.back() = arena;
         uint64_t used = 0, marked = 0;
         for (uint64_t i : ids) {
             IxfPlan &p = plan[i];
             if (!p.total) continue;
-            if (p.total >= 0xFFFFFFFFull) { rc = bfail(TAXOR_E_ARG, "build_hixf: more than 2^32 - 2 keys below one merged bin"); break; }
+            if (p.total >= 0xFFFFFFFFull) { rc = fail(TAXOR_E_ARG, "build_hixf: more than 2^32 - 2 keys below one merged bin"); break; }
             if (leaf_only[i] == 2) {
                 // generated keys of consecutive indices: their union is the range of indices itself (a bijection: no duplicates, no memory)
                 uint64_t first = NO_GEN;
@@ -1293,24 +1280,24 @@ static int build_hixf_impl(taxor_gpu_index *idx, const uint64_t *keys, int keys_
                 const uint64_t *src = d_keys + (key_off[bin_base[i]] - key_off[0]);
                 uint64_t kept = 0;
                 const hipError_t e = unioner.mark(src, p.total, mark + marked, &kept, eng.st);
-                if (e != hipSuccess) { rc = bfail(TAXOR_E_HIP, std::string("build_hixf: key union failed: ") + hipGetErrorString(e)); break; }
+                if (e != hipSuccess) { rc = fail(TAXOR_E_HIP, std::string("build_hixf: key union failed: ") + hipGetErrorString(e)); break; }
                 uni[i] = Union{src, kept == p.total ? nullptr : mark + marked, p.total, kept, NO_GEN};
                 marked += p.total;
                 continue;
             }
             // bins of several kinds: everything gathered (a child's range goes in WITH its duplicates: the set drops them again)
-            if (!concat && hipMalloc((void **)&concat, concat_max * 8) != hipSuccess) { rc = bfail(TAXOR_E_NOMEM, "build_hixf: no device memory for the keys of one IXF"); break; }
+            if (!concat && hipMalloc((void **)&concat, concat_max * 8) != hipSuccess) { rc = fail(TAXOR_E_NOMEM, "build_hixf: no device memory for the keys of one IXF"); break; }
             uint64_t o = 0;
             for (uint64_t b = 0; b < p.bins; ++b) {
                 if (p.n[b] && p.gen_first[b] != NO_GEN)       // generated keys are written out for the set
                     hipLaunchKernelGGL(k_synth_keys, dim3((uint32_t)std::min<uint64_t>(8192, (p.n[b] + BB - 1) / BB)), dim3(BB), 0, eng.st, concat + o, p.gen_first[b], p.n[b], gen_salt);
-                else if (p.n[b] && hipMemcpyAsync(concat + o, p.keys[b], p.n[b] * 8, hipMemcpyDeviceToDevice, eng.st) != hipSuccess) rc = bfail(TAXOR_E_HIP, "build_hixf: device copy failed");
+                else if (p.n[b] && hipMemcpyAsync(concat + o, p.keys[b], p.n[b] * 8, hipMemcpyDeviceToDevice, eng.st) != hipSuccess) rc = fail(TAXOR_E_HIP, "build_hixf: device copy failed");
                 o += p.n[b];
             }
             if (rc != TAXOR_OK) break;
             uint64_t n_out = 0;
             const hipError_t e = unioner.unique(concat, p.total, arena + used, &n_out, eng.st);
-            if (e != hipSuccess) { rc = bfail(TAXOR_E_HIP, std::string("build_hixf: key union failed: ") + hipGetErrorString(e)); break; }
+            if (e != hipSuccess) { rc = fail(TAXOR_E_HIP, std::string("build_hixf: key union failed: ") + hipGetErrorString(e)); break; }
             uni[i] = Union{arena + used, nullptr, n_out, n_out, NO_GEN};
             used += n_out;
         }

@@ -15,6 +15,7 @@
 // it is selectable for machines without a working RCCL and is what the parity tests compare the RCCL transport with.
 // A failure is an error return with a message -- a communicator never silently changes transport.
 #include "../../include/taxor_gpu_tools.h"
+#include "hip_host.h"
 #include "tuning.h"
 using taxor::tune_env;
 
@@ -25,14 +26,12 @@ using taxor::tune_env;
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <thread>
 #include <vector>
 
-extern "C" __attribute__((visibility("hidden"))) void taxor_set_last_error(const char *msg);
 extern "C" __attribute__((visibility("hidden"))) int taxor_index_create_empty(const taxor_hixf_view *v, int device, taxor_gpu_index **out);
 extern "C" __attribute__((visibility("hidden"))) int taxor_index_slab(taxor_gpu_index *idx, uint8_t **slab, uint64_t *slab_bytes,
                                                                       const uint64_t **ixf_off, uint64_t *n_ixf, int *device);
@@ -58,22 +57,9 @@ static constexpr ncclDataType_t ncclUint8 = 1;
 
 namespace {
 
-int cfail(int code, const char *fmt, ...)
-{
-    char buf[768];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    taxor_set_last_error(buf);
-    return code;
-}
+using namespace taxor;
 
-#define C_HIP(expr)                                                                                                   \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess) return cfail(TAXOR_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+#define C_HIP(expr) TAXOR_HIP_TRY_AT(expr, #expr)
 
 // the RCCL entry points this file uses, resolved once
 struct Rccl {
@@ -142,7 +128,7 @@ Rccl &rccl()
     do {                                                                                                                   \
         ncclResult_t r_ = (expr);                                                                                          \
         if (r_ != ncclSuccess)                                                                                             \
-            return cfail(TAXOR_E_HIP, "RCCL: %s failed: %s (%s:%d)", #expr, rccl().GetErrorString ? rccl().GetErrorString(r_) : "?", \
+            return fail(TAXOR_E_HIP, "RCCL: %s failed: %s (%s:%d)", #expr, rccl().GetErrorString ? rccl().GetErrorString(r_) : "?", \
                          __FILE__, __LINE__);                                                                              \
     } while (0)
 
@@ -153,22 +139,12 @@ __global__ void k_rebase_offsets(const uint64_t *__restrict__ in, uint64_t *__re
         out[i] = in[i] + tuple_base;
 }
 
-template <typename T> struct GBuf {           // growable buffer on one device
-    T *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t n)
-    {
-        if (n <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = n + n / 4 + 1024;
-        C_HIP(hipMalloc((void **)&p, want * sizeof(T)));
-        cap = want;
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
+// the gather target grows with a quarter of slack
+template <typename T> int reserve(DeviceBuf<T> &b, size_t n)
+{
+    C_HIP(b.reserve(n, n + n / 4 + 1024));
+    return 0;
+}
 
 } // namespace
 
@@ -178,9 +154,9 @@ struct taxor_gpu_comm {
     std::vector<ncclComm_t> comms;        // RCCL transport: one per device, all in this process (ncclCommInitAll)
     std::vector<hipStream_t> streams;     // one per device, for the collectives and the result transfers
     // gather target on devices[0]
-    GBuf<uint64_t> g_read_off, g_off_tmp;
-    GBuf<int64_t> g_ub;
-    GBuf<uint32_t> g_cnt, g_nh;
+    DeviceBuf<uint64_t> g_read_off, g_off_tmp;
+    DeviceBuf<int64_t> g_ub;
+    DeviceBuf<uint32_t> g_cnt, g_nh;
     // host side of the gathered results (valid until the next gather on this communicator)
     std::vector<uint64_t> h_read_off;
     std::vector<int64_t> h_ub;
@@ -262,7 +238,7 @@ static int comm_selftest(taxor_gpu_comm *c)
     }
     (void)hipSetDevice(c->devices[0]);
     if (rx) (void)hipFree(rx);
-    if (rc != TAXOR_OK) return cfail(rc, "%s (the host transport, --gather host, stages the same transfers through host memory)", msg.c_str());
+    if (rc != TAXOR_OK) return fail(rc, "%s (the host transport, --gather host, stages the same transfers through host memory)", msg.c_str());
     c->stats.selftest_bytes = (uint64_t)n * W * 4 * 2;
     return TAXOR_OK;
 }
@@ -270,12 +246,12 @@ static int comm_selftest(taxor_gpu_comm *c)
 extern "C" int taxor_gpu_comm_create(const int *devices, uint32_t n_devices, int transport, taxor_gpu_comm **out)
 {
     taxor_runtime_env_once();
-    if (!devices || !n_devices || !out) return cfail(TAXOR_E_ARG, "comm_create: no devices");
-    if (transport != TAXOR_COMM_RCCL && transport != TAXOR_COMM_HOST) return cfail(TAXOR_E_ARG, "comm_create: unknown transport %d", transport);
+    if (!devices || !n_devices || !out) return fail(TAXOR_E_ARG, "comm_create: no devices");
+    if (transport != TAXOR_COMM_RCCL && transport != TAXOR_COMM_HOST) return fail(TAXOR_E_ARG, "comm_create: unknown transport %d", transport);
     int have = 0;
     C_HIP(hipGetDeviceCount(&have));
     for (uint32_t i = 0; i < n_devices; ++i)
-        if (devices[i] < 0 || devices[i] >= have) return cfail(TAXOR_E_ARG, "comm_create: device %d does not exist (%d visible)", devices[i], have);
+        if (devices[i] < 0 || devices[i] >= have) return fail(TAXOR_E_ARG, "comm_create: device %d does not exist (%d visible)", devices[i], have);
     auto c = new taxor_gpu_comm();
     c->transport = transport;
     c->devices.assign(devices, devices + n_devices);
@@ -285,7 +261,7 @@ extern "C" int taxor_gpu_comm_create(const int *devices, uint32_t n_devices, int
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->streams[i], hipStreamNonBlocking);
         if (e != hipSuccess) {
             taxor_gpu_comm_destroy(c);
-            return cfail(TAXOR_E_HIP, "comm_create: stream on device %d: %s", devices[i], hipGetErrorString(e));
+            return fail(TAXOR_E_HIP, "comm_create: stream on device %d: %s", devices[i], hipGetErrorString(e));
         }
     }
     if (transport == TAXOR_COMM_RCCL) {
@@ -293,24 +269,24 @@ extern "C" int taxor_gpu_comm_create(const int *devices, uint32_t n_devices, int
             for (uint32_t j = i + 1; j < n_devices; ++j)
                 if (devices[i] == devices[j]) {
                     taxor_gpu_comm_destroy(c);
-                    return cfail(TAXOR_E_ARG, "comm_create: device %d is listed twice; RCCL takes one rank per device (use the host transport)", devices[i]);
+                    return fail(TAXOR_E_ARG, "comm_create: device %d is listed twice; RCCL takes one rank per device (use the host transport)", devices[i]);
                 }
         Rccl &R = rccl();
         if (!R.ok) {
             taxor_gpu_comm_destroy(c);
-            return cfail(TAXOR_E_HIP, "comm_create: %s", R.error.c_str());
+            return fail(TAXOR_E_HIP, "comm_create: %s", R.error.c_str());
         }
         c->comms.assign(n_devices, nullptr);
         const ncclResult_t r = R.CommInitAll(c->comms.data(), (int)n_devices, c->devices.data());
         if (r != ncclSuccess) {
             c->comms.clear();
             taxor_gpu_comm_destroy(c);
-            return cfail(TAXOR_E_HIP, "comm_create: ncclCommInitAll over %u devices failed: %s", n_devices, R.GetErrorString(r));
+            return fail(TAXOR_E_HIP, "comm_create: ncclCommInitAll over %u devices failed: %s", n_devices, R.GetErrorString(r));
         }
         if (int rc = comm_selftest(c)) {
             const std::string msg = taxor_gpu_last_error();
             taxor_gpu_comm_destroy(c);
-            return cfail(rc, "comm_create: %s", msg.c_str());
+            return fail(rc, "comm_create: %s", msg.c_str());
         }
     }
     *out = c;
@@ -335,15 +311,15 @@ extern "C" void taxor_gpu_comm_destroy(taxor_gpu_comm *c)
 
 extern "C" int taxor_gpu_comm_set_self_exchange(taxor_gpu_comm *c, int on)
 {
-    if (!c) return cfail(TAXOR_E_ARG, "comm_set_self_exchange: null communicator");
-    if (on && c->transport != TAXOR_COMM_RCCL) return cfail(TAXOR_E_ARG, "comm_set_self_exchange: only the RCCL transport has a send/recv path");
+    if (!c) return fail(TAXOR_E_ARG, "comm_set_self_exchange: null communicator");
+    if (on && c->transport != TAXOR_COMM_RCCL) return fail(TAXOR_E_ARG, "comm_set_self_exchange: only the RCCL transport has a send/recv path");
     c->self_exchange = on != 0;
     return TAXOR_OK;
 }
 
 extern "C" int taxor_gpu_comm_info(const taxor_gpu_comm *c, taxor_gpu_comm_stats *out)
 {
-    if (!c || !out) return cfail(TAXOR_E_ARG, "comm_info: null argument");
+    if (!c || !out) return fail(TAXOR_E_ARG, "comm_info: null argument");
     *out = c->stats;
     out->rccl_version = c->transport == TAXOR_COMM_RCCL ? rccl().version : 0;
     out->transport = c->transport;
@@ -356,13 +332,13 @@ extern "C" int taxor_gpu_comm_info(const taxor_gpu_comm *c, taxor_gpu_comm_stats
 // =====================================================================================================================
 extern "C" int taxor_gpu_index_create_replicated(taxor_gpu_comm *c, const taxor_hixf_view *view, taxor_gpu_index **out)
 {
-    if (!c || !view || !out) return cfail(TAXOR_E_ARG, "index_create_replicated: null argument");
+    if (!c || !view || !out) return fail(TAXOR_E_ARG, "index_create_replicated: null argument");
     const size_t n = c->devices.size();
     for (size_t i = 0; i < n; ++i) out[i] = nullptr;
     auto destroy_all = [&] {
         for (size_t i = 0; i < n; ++i) { if (out[i]) taxor_gpu_index_destroy(out[i]); out[i] = nullptr; }
     };
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = now_s();
     // (An RCCL communicator of ONE rank takes the RCCL path below too: create-empty, the upload thread with its watermark, the
     // broadcast loop behind it -- an in-place ncclBroadcast on one rank moves nothing, but every line a larger run executes
     // is executed, which is what a one-GPU test box can verify.)
@@ -382,12 +358,12 @@ extern "C" int taxor_gpu_index_create_replicated(taxor_gpu_comm *c, const taxor_
                 const int rc = rcs[i];
                 const std::string msg = errs[i];
                 destroy_all();
-                return cfail(rc, "%s", msg.c_str());
+                return fail(rc, "%s", msg.c_str());
             }
         c->stats.index_bytes = taxor_gpu_index_data_bytes(out[0]);
         c->stats.index_upload_bytes = c->stats.index_bytes * n;
         c->stats.index_broadcast_bytes = 0;
-        c->stats.index_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        c->stats.index_seconds = now_s() - t0;
         return TAXOR_OK;
     }
 
@@ -396,7 +372,7 @@ extern "C" int taxor_gpu_index_create_replicated(taxor_gpu_comm *c, const taxor_
         if (int rc = taxor_index_create_empty(view, c->devices[i], &out[i])) {
             const std::string msg = taxor_gpu_last_error();
             destroy_all();
-            return cfail(rc, "%s", msg.c_str());
+            return fail(rc, "%s", msg.c_str());
         }
     std::vector<uint8_t *> slab(n, nullptr);
     uint64_t slab_bytes = 0, n_ixf = 0;
@@ -404,9 +380,9 @@ extern "C" int taxor_gpu_index_create_replicated(taxor_gpu_comm *c, const taxor_
         int dev;
         uint64_t sb, ni;
         const uint64_t *off;
-        if (taxor_index_slab(out[i], &slab[i], &sb, &off, &ni, &dev)) { destroy_all(); return cfail(TAXOR_E_INTERNAL, "index_create_replicated: slab"); }
+        if (taxor_index_slab(out[i], &slab[i], &sb, &off, &ni, &dev)) { destroy_all(); return fail(TAXOR_E_INTERNAL, "index_create_replicated: slab"); }
         if (i == 0) { slab_bytes = sb; n_ixf = ni; }
-        else if (sb != slab_bytes) { destroy_all(); return cfail(TAXOR_E_INTERNAL, "index_create_replicated: replicas differ in size"); }
+        else if (sb != slab_bytes) { destroy_all(); return fail(TAXOR_E_INTERNAL, "index_create_replicated: replicas differ in size"); }
     }
     // Upload thread: the library's own upload into device 0 (pieces, possibly several threads; api.hip), which reports the
     // slab offset below which device 0 holds final bytes -- the watermark the broadcast follows.
@@ -453,12 +429,12 @@ extern "C" int taxor_gpu_index_create_replicated(taxor_gpu_comm *c, const taxor_
         if (view->source || view->ixf[i].data) uploaded += 3 * view->ixf[i].seg_len * view->ixf[i].stride;
     if (rc) {
         destroy_all();
-        return cfail(rc, "%s", bc_err.c_str());
+        return fail(rc, "%s", bc_err.c_str());
     }
     c->stats.index_bytes = taxor_gpu_index_data_bytes(out[0]);
     c->stats.index_upload_bytes = uploaded;
     c->stats.index_broadcast_bytes = slab_bytes * (n - 1);
-    c->stats.index_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    c->stats.index_seconds = now_s() - t0;
     return TAXOR_OK;
 }
 
@@ -467,18 +443,18 @@ extern "C" int taxor_gpu_index_create_replicated(taxor_gpu_comm *c, const taxor_
 // =====================================================================================================================
 extern "C" int taxor_gpu_gather_results(taxor_gpu_comm *c, taxor_gpu_searcher *const *searchers, taxor_gpu_results *out)
 {
-    if (!c || !searchers || !out) return cfail(TAXOR_E_ARG, "gather_results: null argument");
+    if (!c || !searchers || !out) return fail(TAXOR_E_ARG, "gather_results: null argument");
     const size_t n = c->devices.size();
-    const auto t0 = std::chrono::steady_clock::now();
+    const double t0 = now_s();
     std::vector<uint64_t> nr(n), nt(n), rbase(n + 1, 0), tbase(n + 1, 0);
     std::vector<const uint64_t *> d_ro(n);
     std::vector<const int64_t *> d_ub(n);
     std::vector<const uint32_t *> d_ct(n), d_nh(n);
     for (size_t i = 0; i < n; ++i) {
-        if (!searchers[i]) return cfail(TAXOR_E_ARG, "gather_results: searcher %zu is null", i);
+        if (!searchers[i]) return fail(TAXOR_E_ARG, "gather_results: searcher %zu is null", i);
         int dev = -1;
         if (int rc = taxor_searcher_device_results(searchers[i], &d_ro[i], &d_ub[i], &d_ct[i], &d_nh[i], &nr[i], &nt[i], &dev)) return rc;
-        if (dev != c->devices[i]) return cfail(TAXOR_E_ARG, "gather_results: searcher %zu lives on device %d, the communicator's rank %zu is device %d", i, dev, i, c->devices[i]);
+        if (dev != c->devices[i]) return fail(TAXOR_E_ARG, "gather_results: searcher %zu lives on device %d, the communicator's rank %zu is device %d", i, dev, i, c->devices[i]);
         rbase[i + 1] = rbase[i] + nr[i];
         tbase[i + 1] = tbase[i] + nt[i];
     }
@@ -512,8 +488,8 @@ extern "C" int taxor_gpu_gather_results(taxor_gpu_comm *c, taxor_gpu_searcher *c
     } else {
         Rccl &R = rccl();
         C_HIP(hipSetDevice(c->devices[0]));
-        if (c->g_read_off.reserve(NR + 1) || c->g_off_tmp.reserve(NR + n) || c->g_ub.reserve(NT + 1) || c->g_cnt.reserve(NT + 1) ||
-            c->g_nh.reserve(NR + 1))
+        if (reserve(c->g_read_off, NR + 1) || reserve(c->g_off_tmp, NR + n) || reserve(c->g_ub, NT + 1) || reserve(c->g_cnt, NT + 1) ||
+            reserve(c->g_nh, NR + 1))
             return TAXOR_E_HIP;
         hipStream_t s0 = c->streams[0];
         // rank 0's own part: device-to-device on device 0
@@ -545,7 +521,7 @@ extern "C" int taxor_gpu_gather_results(taxor_gpu_comm *c, taxor_gpu_searcher *c
             }
             const ncclResult_t r2 = R.GroupEnd();
             if (r == ncclSuccess) r = r2;
-            if (r != ncclSuccess) return cfail(TAXOR_E_HIP, "gather_results: grouped ncclSend/ncclRecv failed: %s", R.GetErrorString(r));
+            if (r != ncclSuccess) return fail(TAXOR_E_HIP, "gather_results: grouped ncclSend/ncclRecv failed: %s", R.GetErrorString(r));
         }
         // rebase the offsets on device 0 (stream order: behind the receives), close the CSR, one D2H per array
         C_HIP(hipSetDevice(c->devices[0]));
@@ -579,6 +555,6 @@ extern "C" int taxor_gpu_gather_results(taxor_gpu_comm *c, taxor_gpu_searcher *c
     out->n_hashes = c->h_nh.data();
     c->stats.gathers++;
     c->stats.gather_bytes += (NR - nr[0]) * 12 + (NT - nt[0]) * 12;
-    c->stats.gather_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    c->stats.gather_seconds += now_s() - t0;
     return TAXOR_OK;
 }

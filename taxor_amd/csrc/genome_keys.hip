@@ -21,6 +21,8 @@
 // such segment per call.  _finish gathers the segments per bin, sorts every bin (rocPRIM segmented radix sort), and drops the
 // duplicates of bins with several segments.
 #include "../../include/taxor_gpu_tools.h"
+#include "device_prims.h"
+#include "hip_host.h"
 #include "ixf_arith.h"
 #include "keyset.h"
 
@@ -28,13 +30,10 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <map>
 #include <string>
 #include <vector>
-
-extern "C" __attribute__((visibility("hidden"))) void taxor_set_last_error(const char *msg);
 
 namespace {
 
@@ -49,112 +48,6 @@ constexpr uint64_t CC_BLOCK = 4096;                  // elements per block of th
 constexpr uint64_t REGION_MIN = 4096;                // slots of the smallest per-bin table
 
 enum : uint32_t { GK_ALPHABET = 1u, GK_TABLE_FULL = 2u };
-
-__device__ __forceinline__ uint32_t gk_lane() { return threadIdx.x & 63u; }
-
-__device__ __forceinline__ int gk_wave_incl_max(int v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d);
-        if ((int)gk_lane() >= d) v = max(v, t);
-    }
-    return v;
-}
-
-// exclusive prefix max over the block (identity -1); scratch >= 4 words
-__device__ __forceinline__ int gk_block_excl_max(int v, int *scratch)
-{
-    const int incl = gk_wave_incl_max(v);
-    const uint32_t w = threadIdx.x >> 6;
-    __syncthreads();
-    if (gk_lane() == 63) scratch[w] = incl;
-    __syncthreads();
-    int off = -1;
-#pragma unroll
-    for (uint32_t i = 0; i < GB / 64; ++i)
-        if (i < w) off = max(off, scratch[i]);
-    int prev = __shfl_up(incl, 1);
-    if (gk_lane() == 0) prev = -1;
-    return max(off, prev);
-}
-
-__device__ __forceinline__ uint32_t gk_wave_incl_add(uint32_t v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(v, d);
-        if ((int)gk_lane() >= d) v += t;
-    }
-    return v;
-}
-
-// exclusive prefix sum over the block; *total = block sum; scratch >= 4 words
-__device__ __forceinline__ uint32_t gk_block_excl_add(uint32_t v, uint32_t *scratch, uint32_t *total)
-{
-    const uint32_t incl = gk_wave_incl_add(v);
-    const uint32_t w = threadIdx.x >> 6;
-    __syncthreads();
-    if (gk_lane() == 63) scratch[w] = incl;
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < GB / 64; ++i) {
-        const uint32_t x = scratch[i];
-        if (i < w) off += x;
-        tot += x;
-    }
-    *total = tot;
-    return off + incl - v;
-}
-
-// seqan3 dna4 char_to_rank: IUPAC codes -> first base, U -> T, N -> A; both cases.  0xFF = not dna15 (as k_pack_dna4)
-__device__ __forceinline__ uint32_t gk_code(uint8_t c)
-{
-    if ((uint8_t)((c | 0x20) - 'a') >= 26u) return 0xFFu;
-    switch (c | 0x20) {
-    case 'a': case 'r': case 'w': case 'm': case 'd': case 'h': case 'v': case 'n': return 0;
-    case 'c': case 'y': case 's': case 'b': return 1;
-    case 'g': case 'k': return 2;
-    case 't': case 'u': return 3;
-    default: return 0xFFu;
-    }
-}
-
-__device__ __forceinline__ uint64_t gk_revcomp(uint64_t x, int nb)
-{
-    x = __brevll(~x);
-    x = ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
-    return x >> (64 - 2 * nb);
-}
-
-// n-base value (n <= 32) starting at base o (0..15) of word a, read from a and the two words after it (first base in the top bits)
-__device__ __forceinline__ uint64_t gk_bases3(uint32_t a, uint32_t b, uint32_t c, uint32_t o, int n)
-{
-    const uint64_t hi = ((uint64_t)a << 32) | b;
-    const int end = 2 * (int)o + 2 * n;
-    const uint64_t mask = (n < 32) ? ((1ull << (2 * n)) - 1ull) : ~0ull;
-    if (end <= 64) return (hi >> (64 - end)) & mask;
-    const int sh = end - 64;                          // 1..30
-    return ((hi << sh) | (uint64_t)(c >> (32 - sh))) & mask;
-}
-
-__device__ __forceinline__ uint64_t gk_lds_bases(const uint32_t *W, uint32_t word, uint32_t o, int n)
-{
-    return gk_bases3(W[word], W[word + 1], W[word + 2], o, n);
-}
-
-__device__ __forceinline__ uint64_t gk_global_bases(const uint32_t *pk, uint32_t nwords, uint32_t pos, int n)
-{
-    const uint32_t wi = pos >> 4;
-    return gk_bases3(pk[wi], wi + 1 < nwords ? pk[wi + 1] : 0u, wi + 2 < nwords ? pk[wi + 2] : 0u, pos & 15u, n);
-}
-
-__device__ __forceinline__ uint64_t gk_canon(uint64_t f, int n)
-{
-    const uint64_t rc = gk_revcomp(f, n);
-    return f < rc ? f : rc;
-}
 
 struct GkArgs {
     const uint32_t *packed;
@@ -201,7 +94,7 @@ __global__ __launch_bounds__(GB) void k_gk_pack(const uint8_t *__restrict__ asci
 #pragma unroll
         for (int c = 0; c < 16; ++c) {
             if (b0 + (uint64_t)c < len) {
-                uint32_t code = gk_code(ascii[a0 + b0 + (uint64_t)c]);
+                uint32_t code = dna4_code(ascii[a0 + b0 + (uint64_t)c]);
                 if (code > 3u) { bad = true; code = 0; }
                 word |= code << (30 - 2 * c);
             }
@@ -240,7 +133,7 @@ __global__ __launch_bounds__(GB) void k_gk_syncmers(const GkArgs a)
         // canonical s-mer values (syncmer.cpp:103-110; the s-mer "hash" is the raw 2-bit value)
         for (int i = tid; i < nw_tile + w - 1; i += GB) {
             const uint32_t pos = (uint32_t)(x0 + i);
-            sV[i] = gk_canon(gk_lds_bases(sW, (pos >> 4) - wbase, pos & 15u, s), s);
+            sV[i] = canon(lds_bases(sW, (pos >> 4) - wbase, pos & 15u, s), s);
         }
         __syncthreads();
         // leftmost / rightmost argmin per window (interleaved: conflict-free LDS)
@@ -268,7 +161,7 @@ __global__ __launch_bounds__(GB) void k_gk_syncmers(const GkArgs a)
             }
         }
         if (first_anchor < GT) atomicMin(&sFirst, first_anchor);
-        const int anchor = gk_block_excl_max(last_anchor, sScr);   // (its barriers also publish sFirst)
+        const int anchor = block_excl_max<GB / 64>(last_anchor, sScr);   // (its barriers also publish sFirst)
         bool known = anchor >= 0;
         int p = -1;
         if (known && xs < nw_tile) {
@@ -284,7 +177,7 @@ __global__ __launch_bounds__(GB) void k_gk_syncmers(const GkArgs a)
                 else if (known && p < xl) p = xl + rm;
                 if (known && p == xl + t - 1) {                    // an open syncmer (syncmer.cpp:142-145)
                     const uint32_t pos = (uint32_t)(x0 + xl);
-                    gk_emit(a, reg, wyhash_u64(gk_canon(gk_lds_bases(sW, (pos >> 4) - wbase, pos & 15u, k), k)));
+                    gk_emit(a, reg, wyhash_u64(canon(lds_bases(sW, (pos >> 4) - wbase, pos & 15u, k), k)));
                 }
             }
         }
@@ -299,7 +192,7 @@ __device__ int gk_rm_global(const uint32_t *pk, uint32_t nwords, int x, int s, i
     uint64_t m = ~0ull;
     int rm = 0;
     for (int j = 0; j < w; ++j) {
-        const uint64_t v = gk_canon(gk_global_bases(pk, nwords, (uint32_t)(x + j), s), s);
+        const uint64_t v = canon(global_bases(pk, nwords, (uint32_t)(x + j), s), s);
         if (v <= m) { m = v; rm = j; }
     }
     return rm;
@@ -325,7 +218,7 @@ __global__ __launch_bounds__(GB) void k_gk_fixup(const GkArgs a)
             const int pe = (int)a.pend[tj];
             for (int x = x0; x < x0 + pe; ++x) {                   // windows without a unique minimum: only the chain moves p
                 if (p < x) p = x + gk_rm_global(pk, nwords, x, s, w);
-                if (p == x + t - 1) gk_emit(a, reg, wyhash_u64(gk_canon(gk_global_bases(pk, nwords, (uint32_t)x, k), k)));
+                if (p == x + t - 1) gk_emit(a, reg, wyhash_u64(canon(global_bases(pk, nwords, (uint32_t)x, k), k)));
             }
             if (pe < nw_tile) break;                               // the tile has an anchor: k_gk_syncmers did the rest
             a.carry[tj] = p;
@@ -360,8 +253,8 @@ __global__ __launch_bounds__(GB) void k_gk_minimisers(const GkArgs a)
         __syncthreads();
         for (int i = tid; i < nw_tile + W - 1; i += GB) {
             const uint32_t pos = (uint32_t)(x0 + i);
-            const uint64_t f = gk_lds_bases(sW, (pos >> 4) - wbase, pos & 15u, k);
-            const uint64_t rc = gk_revcomp(f, k);
+            const uint64_t f = lds_bases(sW, (pos >> 4) - wbase, pos & 15u, k);
+            const uint64_t rc = revcomp64(f, k);
             sV[i] = min(f ^ a.seed, rc ^ a.seed);
         }
         __syncthreads();
@@ -407,7 +300,7 @@ __global__ __launch_bounds__(GB) void k_cc_scatter(const uint64_t *__restrict__ 
         const uint64_t i = j + threadIdx.x;
         const bool keep = i < i1 && cc_keep(in, flag, i);
         uint32_t tot;
-        const uint32_t rank = gk_block_excl_add(keep ? 1u : 0u, sScr, &tot);
+        const uint32_t rank = block_excl_add<GB / 64>(keep ? 1u : 0u, sScr, &tot);
         if (keep) out[at + rank] = in[i];
         at += tot;
     }
@@ -440,44 +333,10 @@ __global__ __launch_bounds__(GB) void k_gk_dup_flags(const uint64_t *__restrict_
         keep[i] = (i == 0 || start[i] || a[i] != a[i - 1]) ? 1 : 0;
 }
 
-int gfail(int code, const std::string &msg)
-{
-    taxor_set_last_error(msg.c_str());
-    return code;
-}
+#define GK_TRY(expr) TAXOR_HIP_TRY_PREFIX("keyer", expr, #expr)
 
-#define GK_TRY(expr)                                                                                                  \
-    do {                                                                                                              \
-        const hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess) return gfail(TAXOR_E_HIP, std::string("keyer: ") + #expr + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    uint64_t cap = 0;
-    hipError_t want(uint64_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        release();
-        const uint64_t m = std::max<uint64_t>(n, 16);
-        const hipError_t e = hipMalloc((void **)&p, m * sizeof(T));
-        if (e == hipSuccess) cap = m;
-        else p = nullptr;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    ~DevBuf() { release(); }
-};
-
-int grid_for(uint64_t items, int per_block, int cap)
-{
-    return (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)cap, (items + (uint64_t)per_block - 1) / (uint64_t)per_block));
-}
+// scratch grows to what a call needs, never below 16 elements
+template <class T> hipError_t want(DeviceBuf<T> &b, uint64_t n) { return b.reserve(n, std::max<uint64_t>(n, 16)); }
 
 // order-preserving compaction of d_in[0, n) (kept: d_flag[i] != 0, or the slots that are not empty when d_flag is null) into a new
 // device array *d_out of exactly the kept size (nullptr when nothing is kept); new_bounds[j] = elements kept before bounds[j]
@@ -487,10 +346,10 @@ int ordered_compact(const uint64_t *d_in, const uint8_t *d_flag, uint64_t n, con
     *d_out = nullptr;
     *total = 0;
     const uint64_t nblk = (n + CC_BLOCK - 1) / CC_BLOCK;
-    DevBuf<uint64_t> cnt, base, bnd, nbnd;
+    DeviceBuf<uint64_t> cnt, base, bnd, nbnd;
     std::vector<uint64_t> h(nblk + 1, 0);
     if (nblk) {
-        GK_TRY(cnt.want(nblk));
+        GK_TRY(want(cnt, nblk));
         hipLaunchKernelGGL(k_cc_count, dim3((uint32_t)nblk), dim3(GB), 0, st, d_in, d_flag, n, cnt.p);
         GK_TRY(hipGetLastError());
         GK_TRY(hipMemcpyAsync(h.data(), cnt.p, nblk * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -504,7 +363,7 @@ int ordered_compact(const uint64_t *d_in, const uint8_t *d_flag, uint64_t n, con
     }
     h[nblk] = run;
     *total = run;
-    GK_TRY(base.want(nblk + 1));
+    GK_TRY(want(base, nblk + 1));
     GK_TRY(hipMemcpyAsync(base.p, h.data(), (nblk + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     if (run) {
         GK_TRY(hipMalloc((void **)d_out, run * sizeof(uint64_t)));
@@ -514,8 +373,8 @@ int ordered_compact(const uint64_t *d_in, const uint8_t *d_flag, uint64_t n, con
     const uint64_t nb = bounds.size();
     new_bounds.assign(nb, 0);
     if (nb) {
-        GK_TRY(bnd.want(nb));
-        GK_TRY(nbnd.want(nb));
+        GK_TRY(want(bnd, nb));
+        GK_TRY(want(nbnd, nb));
         GK_TRY(hipMemcpyAsync(bnd.p, bounds.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_cc_bounds, dim3(grid_for(nb, GB, 4096)), dim3(GB), 0, st, d_in, d_flag, n, base.p, bnd.p, nb, nbnd.p);
         GK_TRY(hipGetLastError());
@@ -524,8 +383,6 @@ int ordered_compact(const uint64_t *d_in, const uint8_t *d_flag, uint64_t n, con
     GK_TRY(hipStreamSynchronize(st));
     return TAXOR_OK;
 }
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 } // namespace
 
@@ -538,11 +395,11 @@ struct taxor_gpu_keyer {
     double limit = 0.0;
     int grid = 2048;
     // scratch of one call (grows, never shrinks until _finish)
-    DevBuf<uint8_t> ascii;
-    DevBuf<uint64_t> aoff, poff, tab, reg_base, reg_mask;
-    DevBuf<uint32_t> packed, rlen, rreg, pend, reg_marker, flags;
-    DevBuf<uint2> tiles;
-    DevBuf<int> carry;
+    DeviceBuf<uint8_t> ascii;
+    DeviceBuf<uint64_t> aoff, poff, tab, reg_base, reg_mask;
+    DeviceBuf<uint32_t> packed, rlen, rreg, pend, reg_marker, flags;
+    DeviceBuf<uint2> tiles;
+    DeviceBuf<int> carry;
     // what the calls left: per call one bin-grouped array, per (user bin, call) one segment of it
     struct Seg { uint64_t bin, chunk, off, n; };
     std::vector<uint64_t *> chunks;
@@ -578,21 +435,21 @@ extern "C" {
 
 int taxor_gpu_keyer_create(int device, const taxor_keyer_params *prm, taxor_gpu_keyer **out)
 {
-    if (!prm || !out) return gfail(TAXOR_E_ARG, "keyer_create: null argument");
+    if (!prm || !out) return fail(TAXOR_E_ARG, "keyer_create: null argument");
     *out = nullptr;
     const taxor_keyer_params &p = *prm;
-    if (p.n_bins == 0 || p.n_bins >= (1ull << 32)) return gfail(TAXOR_E_ARG, "keyer_create: n_bins must be in [1, 2^32)");
+    if (p.n_bins == 0 || p.n_bins >= (1ull << 32)) return fail(TAXOR_E_ARG, "keyer_create: n_bins must be in [1, 2^32)");
     if (p.use_syncmer) {
         const int k = (int)p.kmer_size, s = (int)p.syncmer_size, t = (int)p.t_syncmer;
         if (k < 2 || k > 32 || s < 1 || s >= k || k - s + 1 > 32 || t < 1 || t > k - s + 1)
-            return gfail(TAXOR_E_ARG, "keyer_create: unsupported k=" + std::to_string(k) + " s=" + std::to_string(s) + " t=" + std::to_string(t) +
+            return fail(TAXOR_E_ARG, "keyer_create: unsupported k=" + std::to_string(k) + " s=" + std::to_string(s) + " t=" + std::to_string(t) +
                                       " (need k <= 32, 1 <= s < k, k - s < 32, 1 <= t <= k - s + 1)");
     } else {
-        if (p.kmer_size < 1 || p.kmer_size > 32) return gfail(TAXOR_E_ARG, "keyer_create: k-mer size outside [1,32]");
+        if (p.kmer_size < 1 || p.kmer_size > 32) return fail(TAXOR_E_ARG, "keyer_create: k-mer size outside [1,32]");
         if (p.window_size < p.kmer_size || p.window_size - p.kmer_size + 1 > (uint64_t)GMAX_W)
-            return gfail(TAXOR_E_ARG, "keyer_create: window size must be in [k, k+511]");
+            return fail(TAXOR_E_ARG, "keyer_create: window size must be in [k, k+511]");
     }
-    if (hipSetDevice(device) != hipSuccess) return gfail(TAXOR_E_HIP, "keyer_create: no device " + std::to_string(device));
+    if (hipSetDevice(device) != hipSuccess) return fail(TAXOR_E_HIP, "keyer_create: no device " + std::to_string(device));
     auto kr = new taxor_gpu_keyer();
     kr->device = device;
     kr->p = p;
@@ -604,7 +461,7 @@ int taxor_gpu_keyer_create(int device, const taxor_keyer_params *prm, taxor_gpu_
     if (hipStreamCreateWithFlags(&kr->st, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&kr->ev0) != hipSuccess ||
         hipEventCreate(&kr->ev1) != hipSuccess) {
         delete kr;
-        return gfail(TAXOR_E_HIP, "keyer_create: stream / event creation failed");
+        return fail(TAXOR_E_HIP, "keyer_create: stream / event creation failed");
     }
     *out = kr;
     return TAXOR_OK;
@@ -614,10 +471,10 @@ void taxor_gpu_keyer_destroy(taxor_gpu_keyer *kr) { delete kr; }
 
 int taxor_gpu_keyer_add(taxor_gpu_keyer *kr, const char *bases, const uint64_t *rec_off, const uint32_t *rec_bin, uint64_t n_records)
 {
-    if (!kr || (n_records && (!bases || !rec_off || !rec_bin))) return gfail(TAXOR_E_ARG, "keyer_add: null argument");
-    if (kr->finished) return gfail(TAXOR_E_ARG, "keyer_add: the keyer is finished");
+    if (!kr || (n_records && (!bases || !rec_off || !rec_bin))) return fail(TAXOR_E_ARG, "keyer_add: null argument");
+    if (kr->finished) return fail(TAXOR_E_ARG, "keyer_add: the keyer is finished");
     if (n_records == 0) return TAXOR_OK;
-    if (n_records >= (1ull << 31)) return gfail(TAXOR_E_ARG, "keyer_add: too many records in one call");
+    if (n_records >= (1ull << 31)) return fail(TAXOR_E_ARG, "keyer_add: too many records in one call");
     const double t0 = now_s();
     GK_TRY(hipSetDevice(kr->device));
     const taxor_keyer_params &p = kr->p;
@@ -631,11 +488,11 @@ int taxor_gpu_keyer_add(taxor_gpu_keyer *kr, const char *bases, const uint64_t *
     std::vector<uint64_t> reg_bin, reg_bound;
     uint64_t words = 0;
     for (uint64_t r = 0; r < n_records; ++r) {
-        if (rec_off[r + 1] < rec_off[r]) return gfail(TAXOR_E_ARG, "keyer_add: record offsets decrease");
+        if (rec_off[r + 1] < rec_off[r]) return fail(TAXOR_E_ARG, "keyer_add: record offsets decrease");
         const uint64_t L = rec_off[r + 1] - rec_off[r];
-        if (L >= (1ull << 31)) return gfail(TAXOR_E_ARG, "keyer_add: record " + std::to_string(r) + " is longer than 2^31 - 1 bases");
+        if (L >= (1ull << 31)) return fail(TAXOR_E_ARG, "keyer_add: record " + std::to_string(r) + " is longer than 2^31 - 1 bases");
         if (rec_bin[r] >= p.n_bins)
-            return gfail(TAXOR_E_ARG, "keyer_add: record " + std::to_string(r) + " names user bin " + std::to_string(rec_bin[r]) + " of " +
+            return fail(TAXOR_E_ARG, "keyer_add: record " + std::to_string(r) + " names user bin " + std::to_string(rec_bin[r]) + " of " +
                                           std::to_string(p.n_bins));
         aoff[r] = rec_off[r] - a_first;
         poff[r] = words;
@@ -663,7 +520,7 @@ int taxor_gpu_keyer_add(taxor_gpu_keyer *kr, const char *bases, const uint64_t *
     const uint64_t a_total = rec_off[n_records] - a_first;
     aoff[n_records] = a_total;
     poff[n_records] = words;
-    if (tiles.size() >= (1ull << 32)) return gfail(TAXOR_E_ARG, "keyer_add: too many tiles in one call");
+    if (tiles.size() >= (1ull << 32)) return fail(TAXOR_E_ARG, "keyer_add: too many tiles in one call");
     const uint64_t n_reg = reg_bin.size();
     std::vector<uint64_t> reg_base(n_reg + 1), reg_mask(n_reg);
     uint64_t slots = 0;
@@ -677,20 +534,20 @@ int taxor_gpu_keyer_add(taxor_gpu_keyer *kr, const char *bases, const uint64_t *
     reg_base[n_reg] = slots;
     // ---- device
     hipStream_t st = kr->st;
-    GK_TRY(kr->ascii.want(a_total + 64));
-    GK_TRY(kr->aoff.want(n_records + 1));
-    GK_TRY(kr->poff.want(n_records + 1));
-    GK_TRY(kr->rlen.want(n_records));
-    GK_TRY(kr->rreg.want(n_records));
-    GK_TRY(kr->packed.want(words + 4));
-    GK_TRY(kr->tiles.want(tiles.size()));
-    GK_TRY(kr->carry.want(tiles.size()));
-    GK_TRY(kr->pend.want(tiles.size()));
-    GK_TRY(kr->tab.want(slots));
-    GK_TRY(kr->reg_base.want(n_reg + 1));
-    GK_TRY(kr->reg_mask.want(n_reg));
-    GK_TRY(kr->reg_marker.want(n_reg));
-    GK_TRY(kr->flags.want(1));
+    GK_TRY(want(kr->ascii, a_total + 64));
+    GK_TRY(want(kr->aoff, n_records + 1));
+    GK_TRY(want(kr->poff, n_records + 1));
+    GK_TRY(want(kr->rlen, n_records));
+    GK_TRY(want(kr->rreg, n_records));
+    GK_TRY(want(kr->packed, words + 4));
+    GK_TRY(want(kr->tiles, tiles.size()));
+    GK_TRY(want(kr->carry, tiles.size()));
+    GK_TRY(want(kr->pend, tiles.size()));
+    GK_TRY(want(kr->tab, slots));
+    GK_TRY(want(kr->reg_base, n_reg + 1));
+    GK_TRY(want(kr->reg_mask, n_reg));
+    GK_TRY(want(kr->reg_marker, n_reg));
+    GK_TRY(want(kr->flags, 1));
     if (a_total) GK_TRY(hipMemcpyAsync(kr->ascii.p, bases + a_first, a_total, hipMemcpyHostToDevice, st));
     GK_TRY(hipMemcpyAsync(kr->aoff.p, aoff.data(), aoff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     GK_TRY(hipMemcpyAsync(kr->poff.p, poff.data(), poff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
@@ -744,8 +601,8 @@ int taxor_gpu_keyer_add(taxor_gpu_keyer *kr, const char *bases, const uint64_t *
     GK_TRY(hipStreamSynchronize(st));
     float ms = 0.f;
     GK_TRY(hipEventElapsedTime(&ms, kr->ev0, kr->ev1));
-    if (flags & GK_ALPHABET) return gfail(TAXOR_E_ALPHABET, "keyer_add: character outside the dna15 alphabet in the input");
-    if (flags & GK_TABLE_FULL) return gfail(TAXOR_E_INTERNAL, "keyer_add: a user bin's set outgrew its selection bound");
+    if (flags & GK_ALPHABET) return fail(TAXOR_E_ALPHABET, "keyer_add: character outside the dna15 alphabet in the input");
+    if (flags & GK_TABLE_FULL) return fail(TAXOR_E_INTERNAL, "keyer_add: a user bin's set outgrew its selection bound");
     // ---- the call's sets -> one bin-grouped array; one segment per user bin
     std::vector<uint64_t> nb;
     uint64_t *chunk = nullptr, total = 0;
@@ -768,7 +625,7 @@ int taxor_gpu_keyer_add(taxor_gpu_keyer *kr, const char *bases, const uint64_t *
 
 int taxor_gpu_keyer_finish(taxor_gpu_keyer *kr, const uint64_t **bin_off, const uint64_t **keys, const uint64_t **d_keys)
 {
-    if (!kr) return gfail(TAXOR_E_ARG, "keyer_finish: null keyer");
+    if (!kr) return fail(TAXOR_E_ARG, "keyer_finish: null keyer");
     GK_TRY(hipSetDevice(kr->device));
     hipStream_t st = kr->st;
     if (!kr->finished) {
@@ -785,7 +642,7 @@ int taxor_gpu_keyer_finish(taxor_gpu_keyer *kr, const uint64_t **bin_off, const 
         std::vector<uint64_t> off(nbin + 1, 0);
         for (uint64_t b = 0; b < nbin; ++b) off[b + 1] = off[b] + cnt[b];
         const uint64_t N = off[nbin];
-        if (N >= (1ull << 32)) return gfail(TAXOR_E_ARG, "keyer_finish: more than 2^32 - 1 keys (the segmented sort's limit)");
+        if (N >= (1ull << 32)) return fail(TAXOR_E_ARG, "keyer_finish: more than 2^32 - 1 keys (the segmented sort's limit)");
         uint64_t *A = nullptr, *B = nullptr;
         GK_TRY(hipMalloc((void **)&A, (N + 1) * sizeof(uint64_t)));
         GK_TRY(hipMalloc((void **)&B, (N + 1) * sizeof(uint64_t)));
@@ -805,26 +662,26 @@ int taxor_gpu_keyer_finish(taxor_gpu_keyer *kr, const uint64_t **bin_off, const 
         if (N) {
             std::vector<uint32_t> beg(nbin), end(nbin);
             for (uint64_t b = 0; b < nbin; ++b) { beg[b] = (uint32_t)off[b]; end[b] = (uint32_t)off[b + 1]; }
-            DevBuf<uint32_t> d_beg, d_end;
-            GK_TRY(d_beg.want(nbin));
-            GK_TRY(d_end.want(nbin));
+            DeviceBuf<uint32_t> d_beg, d_end;
+            GK_TRY(want(d_beg, nbin));
+            GK_TRY(want(d_end, nbin));
             GK_TRY(hipMemcpyAsync(d_beg.p, beg.data(), nbin * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             GK_TRY(hipMemcpyAsync(d_end.p, end.data(), nbin * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             size_t tmp_bytes = 0;
             GK_TRY(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, A, B, (unsigned)N, (unsigned)nbin, d_beg.p, d_end.p, 0, 64, st));
-            DevBuf<uint8_t> tmp;
-            GK_TRY(tmp.want(tmp_bytes));
+            DeviceBuf<uint8_t> tmp;
+            GK_TRY(want(tmp, tmp_bytes));
             GK_TRY(rocprim::segmented_radix_sort_keys((void *)tmp.p, tmp_bytes, A, B, (unsigned)N, (unsigned)nbin, d_beg.p, d_end.p, 0, 64, st));
             GK_TRY(hipStreamSynchronize(st));
         }
         (void)hipFree(A);
         if (multi && N) {
             // a bin whose records came in several calls holds a key once per call that met it: keep the first of each run
-            DevBuf<uint8_t> start, keep;
-            DevBuf<uint64_t> d_off;
-            GK_TRY(start.want(N));
-            GK_TRY(keep.want(N));
-            GK_TRY(d_off.want(nbin + 1));
+            DeviceBuf<uint8_t> start, keep;
+            DeviceBuf<uint64_t> d_off;
+            GK_TRY(want(start, N));
+            GK_TRY(want(keep, N));
+            GK_TRY(want(d_off, nbin + 1));
             GK_TRY(hipMemsetAsync(start.p, 0, N, st));
             GK_TRY(hipMemcpyAsync(d_off.p, off.data(), (nbin + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(k_gk_starts, dim3(grid_for(nbin, GB, 4096)), dim3(GB), 0, st, d_off.p, nbin, start.p);
@@ -856,18 +713,18 @@ int taxor_gpu_keyer_finish(taxor_gpu_keyer *kr, const uint64_t **bin_off, const 
 
 int taxor_gpu_keyer_union_size(taxor_gpu_keyer *kr, const uint32_t *bins, uint64_t n, uint64_t *out)
 {
-    if (!kr || (n && !bins) || !out) return gfail(TAXOR_E_ARG, "keyer_union_size: null argument");
-    if (!kr->finished) return gfail(TAXOR_E_ARG, "keyer_union_size: call taxor_gpu_keyer_finish first");
+    if (!kr || (n && !bins) || !out) return fail(TAXOR_E_ARG, "keyer_union_size: null argument");
+    if (!kr->finished) return fail(TAXOR_E_ARG, "keyer_union_size: call taxor_gpu_keyer_finish first");
     *out = 0;
     GK_TRY(hipSetDevice(kr->device));
     uint64_t tot = 0;
     for (uint64_t i = 0; i < n; ++i) {
-        if (bins[i] >= kr->p.n_bins) return gfail(TAXOR_E_ARG, "keyer_union_size: user bin out of range");
+        if (bins[i] >= kr->p.n_bins) return fail(TAXOR_E_ARG, "keyer_union_size: user bin out of range");
         tot += kr->bin_off[bins[i] + 1] - kr->bin_off[bins[i]];
     }
     if (!tot) return TAXOR_OK;
-    DevBuf<uint64_t> cat;
-    GK_TRY(cat.want(tot));
+    DeviceBuf<uint64_t> cat;
+    GK_TRY(want(cat, tot));
     uint64_t at = 0;
     for (uint64_t i = 0; i < n; ++i) {
         const uint64_t lo = kr->bin_off[bins[i]], m = kr->bin_off[bins[i] + 1] - lo;
@@ -880,13 +737,13 @@ int taxor_gpu_keyer_union_size(taxor_gpu_keyer *kr, const uint32_t *bins, uint64
 
 int taxor_gpu_keyer_arrange(taxor_gpu_keyer *kr, const uint64_t *first, const uint64_t *count, uint64_t n_ranges, const uint64_t **d_out)
 {
-    if (!kr || (n_ranges && (!first || !count)) || !d_out) return gfail(TAXOR_E_ARG, "keyer_arrange: null argument");
-    if (!kr->finished) return gfail(TAXOR_E_ARG, "keyer_arrange: call taxor_gpu_keyer_finish first");
+    if (!kr || (n_ranges && (!first || !count)) || !d_out) return fail(TAXOR_E_ARG, "keyer_arrange: null argument");
+    if (!kr->finished) return fail(TAXOR_E_ARG, "keyer_arrange: call taxor_gpu_keyer_finish first");
     GK_TRY(hipSetDevice(kr->device));
     const uint64_t N = kr->bin_off.back();
     uint64_t tot = 0;
     for (uint64_t i = 0; i < n_ranges; ++i) {
-        if (first[i] > N || count[i] > N - first[i]) return gfail(TAXOR_E_ARG, "keyer_arrange: range outside the keys");
+        if (first[i] > N || count[i] > N - first[i]) return fail(TAXOR_E_ARG, "keyer_arrange: range outside the keys");
         tot += count[i];
     }
     if (kr->d_arranged) (void)hipFree(kr->d_arranged);
@@ -904,14 +761,14 @@ int taxor_gpu_keyer_arrange(taxor_gpu_keyer *kr, const uint64_t *first, const ui
 
 int taxor_gpu_keyer_stats(const taxor_gpu_keyer *kr, taxor_keyer_stats *out)
 {
-    if (!kr || !out) return gfail(TAXOR_E_ARG, "keyer_stats: null argument");
+    if (!kr || !out) return fail(TAXOR_E_ARG, "keyer_stats: null argument");
     *out = kr->stats;
     return TAXOR_OK;
 }
 
 int taxor_gpu_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes)
 {
-    if (!free_bytes || !total_bytes) return gfail(TAXOR_E_ARG, "device_memory: null argument");
+    if (!free_bytes || !total_bytes) return fail(TAXOR_E_ARG, "device_memory: null argument");
     GK_TRY(hipSetDevice(device));
     size_t f = 0, t = 0;
     GK_TRY(hipMemGetInfo(&f, &t));

@@ -12,6 +12,7 @@
 // bins of a fingerprint row (16 bins = one aligned 16-B unit per lane), so every probe is three coalesced
 // row segments; hashes run in the loop; per-bin counters live in registers as packed bytes.
 #include "kernels.h"
+#include "device_prims.h"
 #include "ixf_arith.h"
 #include "tuning.h"
 
@@ -23,94 +24,8 @@ namespace taxor {
 static constexpr int BLK = 256;
 
 // ------------------------------------------------------------------------------------------------------
-// small wave / block primitives (wave = 64 lanes)
-// ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t t = __shfl_up(v, d);
-        if ((int)lane_id() >= d) v += t;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int wave_incl_max(int v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        int t = __shfl_up(v, d);
-        if ((int)lane_id() >= d) v = max(v, t);
-    }
-    return v;
-}
-
-// exclusive prefix sum over the 256 threads of a block; *total = block sum.  scratch: >= 4 words.
-__device__ __forceinline__ uint32_t block_excl_add(uint32_t v, uint32_t *scratch, uint32_t *total)
-{
-    const uint32_t incl = wave_incl_add(v);
-    const uint32_t w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane_id() == 63) scratch[w] = incl;
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < BLK / 64; ++i) {
-        const uint32_t x = scratch[i];
-        if (i < w) off += x;
-        tot += x;
-    }
-    *total = tot;
-    return off + incl - v;
-}
-
-// exclusive prefix max over the 256 threads (identity -1)
-__device__ __forceinline__ int block_excl_max(int v, int *scratch)
-{
-    const int incl = wave_incl_max(v);
-    const uint32_t w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane_id() == 63) scratch[w] = incl;
-    __syncthreads();
-    int off = -1;
-#pragma unroll
-    for (uint32_t i = 0; i < BLK / 64; ++i)
-        if (i < w) off = max(off, scratch[i]);
-    int prev = __shfl_up(incl, 1);
-    if (lane_id() == 0) prev = -1;
-    return max(off, prev);
-}
-
-// append one record per participating lane with a single atomic per wave (ballot + popcount).
-// Returns the slot for lanes with pred, undefined otherwise.
-__device__ __forceinline__ uint32_t wave_append(bool pred, uint32_t *counter)
-{
-    const unsigned long long m = __ballot(pred);
-    if (m == 0ull) return 0;
-    const int leader = __ffsll((long long)m) - 1;
-    uint32_t base = 0;
-    if ((int)lane_id() == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = __shfl(base, leader);
-    return base + (uint32_t)__popcll(m & ((1ull << lane_id()) - 1ull));
-}
-
-// ------------------------------------------------------------------------------------------------------
 // k_pack_dna4 : one block per read (grid-stride), one thread per 16-base word
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t dna4_code(uint8_t c)
-{
-    // seqan3 dna4 char_to_rank: IUPAC codes -> first base, U -> T, N -> A; both cases. 0xFF = not dna15.
-    switch (c | 0x20) {
-    case 'a': case 'r': case 'w': case 'm': case 'd': case 'h': case 'v': case 'n': return 0;
-    case 'c': case 'y': case 's': case 'b': return 1;
-    case 'g': case 'k': return 2;
-    case 't': case 'u': return 3;
-    default: return 0xFFu;
-    }
-}
-
 __global__ __launch_bounds__(BLK) void k_pack_dna4(const uint8_t *__restrict__ ascii,
                                                    const uint64_t *__restrict__ aoff,
                                                    const uint64_t *__restrict__ poff,
@@ -118,7 +33,7 @@ __global__ __launch_bounds__(BLK) void k_pack_dna4(const uint8_t *__restrict__ a
                                                    Counters *ctr)
 {
     __shared__ uint8_t sLut[256]; // char -> 2-bit code, 0xFF = not a dna15 letter
-    sLut[threadIdx.x] = (uint8_t)(((uint8_t)((threadIdx.x | 0x20u) - 'a') < 26u) ? dna4_code((uint8_t)threadIdx.x) : 0xFFu);
+    sLut[threadIdx.x] = (uint8_t)dna4_code((uint8_t)threadIdx.x);
     __syncthreads();
     for (uint32_t r = blockIdx.x; r < n_reads; r += gridDim.x) {
         const uint64_t a0 = aoff[r];
@@ -187,31 +102,6 @@ static constexpr int SY_WORDS = SY_T / 16 + 8; // packed words staged per tile
 static constexpr int SY_LDS_TAB = 4096;        // dedup slots held in LDS
 static constexpr int SY_LDS_CAND = 2048;       // candidate hashes held in LDS (the rest spill to global)
 static constexpr int SY_CHUNK_MAX = 8;         // reads taken per cursor atomic, at most
-
-__device__ __forceinline__ uint32_t revcomp32(uint32_t x, int nb)
-{
-    x = __brev(~x);
-    x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
-    return x >> (32 - 2 * nb);
-}
-
-__device__ __forceinline__ uint64_t revcomp64(uint64_t x, int nb)
-{
-    x = __brevll(~x);
-    x = ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
-    return x >> (64 - 2 * nb);
-}
-
-// n-base value starting at base `pos` (tile-local word array W, wbase = first staged word), n <= 32
-__device__ __forceinline__ uint64_t extract_bases(const uint32_t *W, uint32_t pos_word, uint32_t o, int n)
-{
-    const uint64_t hi = ((uint64_t)W[pos_word] << 32) | W[pos_word + 1];
-    const int end = 2 * (int)o + 2 * n;
-    const uint64_t mask = (n < 32) ? ((1ull << (2 * n)) - 1ull) : ~0ull;
-    if (end <= 64) return (hi >> (64 - end)) & mask;
-    const int sh = end - 64; // 1..30
-    return ((hi << sh) | (uint64_t)(W[pos_word + 2] >> (32 - sh))) & mask;
-}
 
 __device__ __forceinline__ uint32_t dedup_slot(uint64_t h, uint32_t mask)
 {
@@ -342,7 +232,7 @@ template <int FW, bool PROF = false> __global__ __launch_bounds__(BLK) void k_sy
                     uint32_t v = 0x07FFFFFFu; // above every canonical value of <= 13 bases, and (v << 5) still fits
                     if (i < nv) {
                         const uint32_t pos = (uint32_t)(x0 + i);
-                        const uint32_t f = (uint32_t)extract_bases(sW, (pos >> 4) - wbase, pos & 15u, s) & smask;
+                        const uint32_t f = (uint32_t)lds_bases(sW, (pos >> 4) - wbase, pos & 15u, s) & smask;
                         const uint32_t rc = revcomp32(f, s);
                         v = min(f, rc);
                     }
@@ -387,7 +277,7 @@ template <int FW, bool PROF = false> __global__ __launch_bounds__(BLK) void k_sy
                     uint32_t v = 0xFFFFFFFFu;
                     if (i < nv) {
                         const uint32_t pos = (uint32_t)(x0 + i);
-                        const uint32_t f = (uint32_t)extract_bases(sW, (pos >> 4) - wbase, pos & 15u, s) & smask;
+                        const uint32_t f = (uint32_t)lds_bases(sW, (pos >> 4) - wbase, pos & 15u, s) & smask;
                         const uint32_t rc = revcomp32(f, s);
                         v = min(f, rc);
                     }
@@ -422,7 +312,7 @@ template <int FW, bool PROF = false> __global__ __launch_bounds__(BLK) void k_sy
                 }
             }
             PMARK(3)                                                 // 3: window argmins (min trees / scan)
-            const int anchor = block_excl_max(last_anchor, (int *)sScr);
+            const int anchor = block_excl_max<BLK / 64>(last_anchor, (int *)sScr);
             uint32_t selmask = 0;
             int p; // tile-local s-mer start currently tracked (may be -1: last position of the previous tile)
             if (xs < nw_tile) {
@@ -444,12 +334,12 @@ template <int FW, bool PROF = false> __global__ __launch_bounds__(BLK) void k_sy
             PMARK(4)                                                 // 4: anchor scan + chain walk + selection
             // ---- emit wyhash(canonical k-mer) of the selected windows, in window order --------------
             uint32_t tot;
-            uint32_t pos = n_sel + block_excl_add((uint32_t)__popc(selmask), sScr, &tot);
+            uint32_t pos = n_sel + block_excl_add<BLK / 64>((uint32_t)__popc(selmask), sScr, &tot);
             while (selmask) {
                 const int c = __ffs((int)selmask) - 1;
                 selmask &= selmask - 1;
                 const uint32_t x = (uint32_t)(x0 + xs + c);
-                const uint64_t f = extract_bases(sW, (x >> 4) - wbase, x & 15u, k);
+                const uint64_t f = lds_bases(sW, (x >> 4) - wbase, x & 15u, k);
                 const uint64_t rc = revcomp64(f, k);
                 const uint64_t h = wyhash_u64(f < rc ? f : rc); // syncmer.cpp:144-145
                 if (pos < cap) {
@@ -496,7 +386,7 @@ template <int FW, bool PROF = false> __global__ __launch_bounds__(BLK) void k_sy
                 n_dist = n_sel;
             } else {
                 uint32_t tot;
-                const uint32_t rank = block_excl_add(first ? 1u : 0u, sScr, &tot);
+                const uint32_t rank = block_excl_add<BLK / 64>(first ? 1u : 0u, sScr, &tot);
                 if (first) outh[rank] = h;
                 n_dist = tot;
             }
@@ -623,7 +513,7 @@ template <int FW, bool PROF = false> __global__ __launch_bounds__(BLK) void k_sy
                         if (first && a.scaling_limit > 0.0 && !((double)wyhash_u64(h) <= a.scaling_limit)) first = 0;
                     }
                     uint32_t tot;
-                    const uint32_t rank = block_excl_add(first, sScr, &tot);
+                    const uint32_t rank = block_excl_add<BLK / 64>(first, sScr, &tot);
                     if (first) outh[n_dist + rank] = h;
                     n_dist += tot;
                 }
@@ -726,7 +616,7 @@ template <int FW> __global__ __launch_bounds__(BLK) void k_syncmers_wave(const S
                     uint32_t v = 0x07FFFFFFu;
                     if (i < nv) {
                         const uint32_t pos = (uint32_t)(x0 + i);
-                        const uint32_t f = (uint32_t)extract_bases(sW, (pos >> 4) - wbase, pos & 15u, s) & smask;
+                        const uint32_t f = (uint32_t)lds_bases(sW, (pos >> 4) - wbase, pos & 15u, s) & smask;
                         v = min(f, revcomp32(f, s));
                     }
                     sV[(i & (WV_C - 1)) * WV_RS + (i >> 3)] = v;
@@ -796,7 +686,7 @@ template <int FW> __global__ __launch_bounds__(BLK) void k_syncmers_wave(const S
                     const int c = __ffs((int)selmask) - 1;
                     selmask &= selmask - 1;
                     const uint32_t x = (uint32_t)(x0 + xs + c);
-                    const uint64_t f = extract_bases(sW, (x >> 4) - wbase, x & 15u, k);
+                    const uint64_t f = lds_bases(sW, (x >> 4) - wbase, x & 15u, k);
                     const uint64_t rc = revcomp64(f, k);
                     if (pos < cap) sCand[pos] = wyhash_u64(f < rc ? f : rc);       // syncmer.cpp:144-145
                     ++pos;
@@ -947,7 +837,7 @@ __global__ __launch_bounds__(BLK) void k_minimisers(const SyncmerArgs a)
             const int nval = nw_tile + W - 1;
             for (int i = (int)tid; i < nval; i += BLK) {
                 const uint32_t pos = (uint32_t)(j0 + i);
-                const uint64_t f = extract_bases(sW, (pos >> 4) - wbase, pos & 15u, k);
+                const uint64_t f = lds_bases(sW, (pos >> 4) - wbase, pos & 15u, k);
                 const uint64_t rc = revcomp64(f, k);
                 sV[i] = min(f ^ seed, rc ^ seed);
             }
@@ -1001,7 +891,7 @@ __global__ __launch_bounds__(BLK) void k_minimisers(const SyncmerArgs a)
                 }
             }
             uint32_t tot;
-            uint32_t off = n_out + block_excl_add(cnt, sScr, &tot);
+            uint32_t off = n_out + block_excl_add<BLK / 64>(cnt, sScr, &tot);
 #pragma unroll
             for (int c = 0; c < MN_C; ++c)
                 if (em[c]) {

@@ -21,6 +21,8 @@
 // EM arithmetic: the device does integer sums, IEEE double add / subtract / divide and comparisons (this file is compiled with
 // -ffp-contract=off); every log and the one sequential sum of posteriors are the host's (run(), below).
 #include "../../include/taxor_gpu_tools.h"
+#include "device_prims.h"
+#include "hip_host.h"
 #include "keyset.h"
 #include "profile_host.h"
 
@@ -28,15 +30,12 @@
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
-
-extern "C" __attribute__((visibility("hidden"))) void taxor_set_last_error(const char *msg);
 
 namespace {
 
@@ -49,7 +48,6 @@ constexpr uint64_t NO_POS = ~0ull;
 
 enum : uint32_t { PF_TABLE_FULL = 1u, PF_NO_PRIOR = 2u };
 
-__device__ __forceinline__ uint32_t pf_lane() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint64_t pf_first_read() { return (uint64_t)blockIdx.x * PW + (threadIdx.x >> 6); }
 __device__ __forceinline__ uint64_t pf_read_step() { return (uint64_t)gridDim.x * PW; }
 
@@ -59,7 +57,7 @@ __device__ __forceinline__ uint64_t pf_count(const uint8_t *__restrict__ alive, 
     uint64_t n = 0;
     *mine = NO_POS;
     for (uint64_t base = lo; base < hi; base += 64) {
-        const uint64_t i = base + pf_lane();
+        const uint64_t i = base + lane_id();
         const bool a = i < hi && alive[i];
         if (a) *mine = i;
         n += (uint64_t)__popcll(__ballot(a));
@@ -85,14 +83,14 @@ __global__ __launch_bounds__(PB) void k_pf_filter(const uint64_t *__restrict__ o
         uint64_t n = 0;
         bool any = false;
         for (uint64_t base = lo; base < hi; base += 64) {
-            const uint64_t i = base + pf_lane();
+            const uint64_t i = base + lane_id();
             const bool a = i < hi && alive[i];
             const bool f = a && ref[i] >= 0 && flag[ref[i]];
             n += (uint64_t)__popcll(__ballot(a));
             any |= __ballot(f) != 0;
         }
         if (n < 2 || !any) continue;
-        for (uint64_t i = lo + pf_lane(); i < hi; i += 64)
+        for (uint64_t i = lo + lane_id(); i < hi; i += 64)
             if (alive[i] && !(ref[i] >= 0 && flag[ref[i]])) alive[i] = 0;
     }
 }
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(PB) void k_pf_hist(const uint64_t *__restrict__ off
         if (n == 1) {
             if (mine != NO_POS && ref[mine] >= 0) atomicAdd(&uniq[ref[mine]], 1u);
         } else if (n > 1) {
-            for (uint64_t i = lo + pf_lane(); i < hi; i += 64)
+            for (uint64_t i = lo + lane_id(); i < hi; i += 64)
                 if (alive[i] && ref[i] >= 0) atomicAdd(&amb[ref[i]], 1u);
         }
     }
@@ -154,7 +152,7 @@ __global__ __launch_bounds__(PB) void k_pf_assoc(const uint64_t *__restrict__ of
                 atomicMin(&first_pos[ref[mine]], (unsigned long long)mine);
             }
         } else if (n > 1) {
-            for (uint64_t i = lo + pf_lane(); i < hi; i += 64)
+            for (uint64_t i = lo + lane_id(); i < hi; i += 64)
                 if (alive[i] && ref[i] >= 0) {
                     atomicAdd(&all[ref[i]], 1u);
                     atomicMin(&first_pos[ref[i]], (unsigned long long)i);
@@ -162,7 +160,7 @@ __global__ __launch_bounds__(PB) void k_pf_assoc(const uint64_t *__restrict__ of
             for (uint64_t a = lo; a < hi; ++a) {                           // a is the same in every lane
                 if (!alive[a] || ref[a] < 0) continue;
                 const uint64_t ra = (uint64_t)(uint32_t)ref[a];
-                for (uint64_t j = lo + pf_lane(); j < hi; j += 64)
+                for (uint64_t j = lo + lane_id(); j < hi; j += 64)
                     if (alive[j] && ref[j] >= 0 && (uint64_t)(uint32_t)ref[j] != ra) pf_pair_add(keys, cnt, mask, ra << 32 | (uint32_t)ref[j], err);
             }
         }
@@ -178,7 +176,7 @@ __global__ __launch_bounds__(PB) void k_pf_explain(const uint64_t *__restrict__ 
         const uint64_t lo = off[r], hi = off[r + 1];
         uint64_t mine;
         const uint64_t n = pf_count(alive_in, lo, hi, &mine);
-        for (uint64_t i = lo + pf_lane(); i < hi; i += 64) {
+        for (uint64_t i = lo + lane_id(); i < hi; i += 64) {
             int32_t x = ref_in[i];
             uint8_t a = alive_in[i];
             if (n > 1 && a && x >= 0 && expl[x] >= 0) {
@@ -202,7 +200,7 @@ __global__ __launch_bounds__(PB) void k_pf_dup(const uint64_t *__restrict__ off,
 {
     for (uint64_t r = pf_first_read(); r < n_reads; r += pf_read_step()) {
         const uint64_t lo = off[r], hi = off[r + 1];
-        for (uint64_t i = lo + pf_lane(); i < hi; i += 64) {
+        for (uint64_t i = lo + lane_id(); i < hi; i += 64) {
             bool d = false;
             if (alive[i] && ref[i] >= 0)
                 for (uint64_t j = lo; j < i && !d; ++j) d = alive[j] && ref[j] == ref[i];
@@ -221,7 +219,7 @@ __global__ __launch_bounds__(PB) void k_pf_sum_ratio(const uint64_t *__restrict_
         double s = 0.0;
         uint64_t n = 0;
         for (uint64_t base = lo; base < hi; base += 64) {
-            const uint64_t i = base + pf_lane();
+            const uint64_t i = base + lane_id();
             const bool a = i < hi && alive[i];
             const double ratio = a ? (double)hash_match[i] / c : 0.0;
             uint64_t m = __ballot(a);
@@ -232,28 +230,8 @@ __global__ __launch_bounds__(PB) void k_pf_sum_ratio(const uint64_t *__restrict_
                 m &= m - 1;
             }
         }
-        if (pf_lane() == 0) sum[r] = n > 1 ? s : -1.0;
+        if (lane_id() == 0) sum[r] = n > 1 ? s : -1.0;
     }
-}
-
-__device__ __forceinline__ double pf_wave_max(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const double t = __shfl_xor(v, d);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ long long pf_wave_max_ll(long long v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const long long t = __shfl_xor(v, d);
-        v = t > v ? t : v;
-    }
-    return v;
 }
 
 // One EM iteration's device part.  post / valid / best are written for every match of every read; totals = {all_nts, unclassified_nts}.
@@ -272,7 +250,7 @@ __global__ __launch_bounds__(PB) void k_pf_em(const uint64_t *__restrict__ off, 
         const uint64_t n = pf_count(alive, lo, hi, &mine);
         if (n <= 1) {
             bool counted = false, unclassified = false;
-            for (uint64_t i = lo + pf_lane(); i < hi; i += 64) {
+            for (uint64_t i = lo + lane_id(); i < hi; i += 64) {
                 uint8_t v = 0, b = 0;
                 if (n == 1 && i == mine) {
                     const int32_t x = ref[i];
@@ -296,7 +274,7 @@ __global__ __launch_bounds__(PB) void k_pf_em(const uint64_t *__restrict__ off, 
         const double lc = log_count[r], ls = log_sum[r];
         double mx = -DBL_MAX;
         long long last = -1;
-        for (uint64_t i = lo + pf_lane(); i < hi; i += 64) {
+        for (uint64_t i = lo + lane_id(); i < hi; i += 64) {
             uint8_t v = 0;
             const int32_t x = ref[i];
             if (alive[i] && x >= 0 && has_prior[x]) {
@@ -315,10 +293,10 @@ __global__ __launch_bounds__(PB) void k_pf_em(const uint64_t *__restrict__ off, 
             }
             valid[i] = v;
         }
-        mx = pf_wave_max(mx);
-        last = pf_wave_max_ll(last);
+        mx = wave_max(mx);
+        last = wave_max(last);
         bool any_best = false;
-        for (uint64_t i = lo + pf_lane(); i < hi; i += 64) {
+        for (uint64_t i = lo + lane_id(); i < hi; i += 64) {
             const bool b = valid[i] && post[i] >= mx;                       // ties stay, in match order (:699-707)
             best[i] = b ? 1 : 0;
             if (b) {
@@ -328,44 +306,20 @@ __global__ __launch_bounds__(PB) void k_pf_em(const uint64_t *__restrict__ off, 
         }
         if (__ballot(any_best)) acc_all += qlen;
         if (last < 0) {
-            if (pf_lane() == 0) atomicOr(err, PF_NO_PRIOR);
-        } else if (pf_lane() == 0)
+            if (lane_id() == 0) atomicOr(err, PF_NO_PRIOR);
+        } else if (lane_id() == 0)
             alive[last] = 0;
     }
-    if (pf_lane() == 0) {
+    if (lane_id() == 0) {
         if (acc_all) atomicAdd(&totals[0], acc_all);
         if (acc_un) atomicAdd(&totals[1], acc_un);
     }
 }
 
-int pfail(int code, const std::string &msg)
-{
-    taxor_set_last_error(msg.c_str());
-    return code;
-}
+#define PF_TRY(expr) TAXOR_HIP_TRY_PREFIX("profile", expr, #expr)
 
-#define PF_TRY(expr)                                                                                                    \
-    do {                                                                                                                \
-        const hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return pfail(TAXOR_E_HIP, std::string("profile: ") + #expr + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T> struct PBuf {
-    T *p = nullptr;
-    hipError_t alloc(uint64_t n)
-    {
-        release();
-        return hipMalloc((void **)&p, std::max<uint64_t>(n, 1) * sizeof(T));
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    ~PBuf() { release(); }
-};
-
-double pf_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// every array is allocated anew, with at least one element
+template <class T> hipError_t alloc(DeviceBuf<T> &b, uint64_t n) { return b.alloc(std::max<uint64_t>(n, 1)); }
 
 }   // namespace
 
@@ -378,12 +332,12 @@ struct taxor_gpu_profile {
     std::shared_ptr<taxor_profile_host_csr> host;
     std::vector<uint64_t> &h_off = host->off, &h_ref_len0 = host->ref_len, &h_hash_match = host->hash_match, &h_query_len = host->query_len,
                           &h_hash_count = host->hash_count;
-    PBuf<uint64_t> d_off, d_ref_len, d_hash_match, d_query_len, d_hash_count, d_taxa_len, d_keys;
-    PBuf<int32_t> d_ref, d_ref2, d_expl;
-    PBuf<uint8_t> d_alive, d_alive2, d_flag, d_dup, d_valid, d_best, d_has_prior;
-    PBuf<uint32_t> d_uniq, d_all, d_cnt, d_err;
-    PBuf<unsigned long long> d_first, d_ref_nts, d_totals;
-    PBuf<double> d_log_match, d_log_count, d_sum, d_prior, d_post;
+    DeviceBuf<uint64_t> d_off, d_ref_len, d_hash_match, d_query_len, d_hash_count, d_taxa_len, d_keys;
+    DeviceBuf<int32_t> d_ref, d_ref2, d_expl;
+    DeviceBuf<uint8_t> d_alive, d_alive2, d_flag, d_dup, d_valid, d_best, d_has_prior;
+    DeviceBuf<uint32_t> d_uniq, d_all, d_cnt, d_err;
+    DeviceBuf<unsigned long long> d_first, d_ref_nts, d_totals;
+    DeviceBuf<double> d_log_match, d_log_count, d_sum, d_prior, d_post;
     uint64_t pair_slots = 0;
     // results
     std::vector<int32_t> r_ref, r_explained;
@@ -400,8 +354,6 @@ struct taxor_gpu_profile {
 };
 
 namespace {
-
-int grid_reads(uint64_t n_reads) { return (int)std::max<uint64_t>(1, std::min<uint64_t>(P_GRID_CAP, (n_reads + PW - 1) / PW)); }
 
 // :349-399 over the downloaded counts.  expl[x] = the reference that explains x, or -1.  Map order is id order.
 int explained_by(uint64_t n_refs, const std::vector<uint32_t> &uniq, const std::vector<uint32_t> &all, const std::vector<uint64_t> &pair_key,
@@ -439,7 +391,7 @@ int explained_by(uint64_t n_refs, const std::vector<uint32_t> &uniq, const std::
     bool found = true;
     for (uint64_t pass = 0; found; ++pass) {
         if (pass > entries + 1)
-            return pfail(TAXOR_E_ARG, "profile: the explained-by relation between references runs into a cycle (a reference is explained, through "
+            return fail(TAXOR_E_ARG, "profile: the explained-by relation between references runs into a cycle (a reference is explained, through "
                                       "others, by itself); the chain resolution of the reference implementation does not end on such input");
         found = false;
         for (uint64_t x = 0; x < n_refs; ++x) {
@@ -458,27 +410,27 @@ int explained_by(uint64_t n_refs, const std::vector<uint32_t> &uniq, const std::
 int alloc_work(taxor_gpu_profile *p)
 {
     const uint64_t R = p->n_reads, F = p->n_refs, M = p->n_matches;
-    PF_TRY(p->d_ref2.alloc(M));
-    PF_TRY(p->d_alive.alloc(M));
-    PF_TRY(p->d_alive2.alloc(M));
-    PF_TRY(p->d_dup.alloc(M));
-    PF_TRY(p->d_valid.alloc(M));
-    PF_TRY(p->d_best.alloc(M));
-    PF_TRY(p->d_post.alloc(M));
-    PF_TRY(p->d_log_match.alloc(M));
-    PF_TRY(p->d_log_count.alloc(R));
-    PF_TRY(p->d_sum.alloc(R));
-    PF_TRY(p->d_flag.alloc(F));
-    PF_TRY(p->d_has_prior.alloc(F));
-    PF_TRY(p->d_uniq.alloc(F));
-    PF_TRY(p->d_all.alloc(F));
-    PF_TRY(p->d_first.alloc(F));
-    PF_TRY(p->d_ref_nts.alloc(F));
-    PF_TRY(p->d_prior.alloc(F));
-    PF_TRY(p->d_expl.alloc(F));
-    PF_TRY(p->d_taxa_len.alloc(F));
-    PF_TRY(p->d_totals.alloc(2));
-    PF_TRY(p->d_err.alloc(1));
+    PF_TRY(alloc(p->d_ref2, M));
+    PF_TRY(alloc(p->d_alive, M));
+    PF_TRY(alloc(p->d_alive2, M));
+    PF_TRY(alloc(p->d_dup, M));
+    PF_TRY(alloc(p->d_valid, M));
+    PF_TRY(alloc(p->d_best, M));
+    PF_TRY(alloc(p->d_post, M));
+    PF_TRY(alloc(p->d_log_match, M));
+    PF_TRY(alloc(p->d_log_count, R));
+    PF_TRY(alloc(p->d_sum, R));
+    PF_TRY(alloc(p->d_flag, F));
+    PF_TRY(alloc(p->d_has_prior, F));
+    PF_TRY(alloc(p->d_uniq, F));
+    PF_TRY(alloc(p->d_all, F));
+    PF_TRY(alloc(p->d_first, F));
+    PF_TRY(alloc(p->d_ref_nts, F));
+    PF_TRY(alloc(p->d_prior, F));
+    PF_TRY(alloc(p->d_expl, F));
+    PF_TRY(alloc(p->d_taxa_len, F));
+    PF_TRY(alloc(p->d_totals, 2));
+    PF_TRY(alloc(p->d_err, 1));
     return TAXOR_OK;
 }
 
@@ -486,17 +438,17 @@ int alloc_work(taxor_gpu_profile *p)
 
 extern "C" int taxor_gpu_profile_create(int device, const taxor_profile_csr *csr, taxor_gpu_profile **out)
 {
-    if (!csr || !out) return pfail(TAXOR_E_ARG, "profile_create: null argument");
+    if (!csr || !out) return fail(TAXOR_E_ARG, "profile_create: null argument");
     *out = nullptr;
     const uint64_t R = csr->n_reads, F = csr->n_refs, M = csr->n_matches;
     if (!csr->read_off || (M && (!csr->ref || !csr->ref_len || !csr->hash_match)) || (R && (!csr->query_len || !csr->hash_count)))
-        return pfail(TAXOR_E_ARG, "profile_create: null array");
-    if (F >= (1ull << 31)) return pfail(TAXOR_E_ARG, "profile_create: more than 2^31 - 1 references");
-    if (csr->read_off[0] != 0 || csr->read_off[R] != M) return pfail(TAXOR_E_ARG, "profile_create: read_off does not span the matches");
+        return fail(TAXOR_E_ARG, "profile_create: null array");
+    if (F >= (1ull << 31)) return fail(TAXOR_E_ARG, "profile_create: more than 2^31 - 1 references");
+    if (csr->read_off[0] != 0 || csr->read_off[R] != M) return fail(TAXOR_E_ARG, "profile_create: read_off does not span the matches");
     for (uint64_t r = 0; r < R; ++r)
-        if (csr->read_off[r + 1] < csr->read_off[r]) return pfail(TAXOR_E_ARG, "profile_create: read_off decreases");
+        if (csr->read_off[r + 1] < csr->read_off[r]) return fail(TAXOR_E_ARG, "profile_create: read_off decreases");
     for (uint64_t i = 0; i < M; ++i)
-        if (csr->ref[i] < -1 || (csr->ref[i] >= 0 && (uint64_t)csr->ref[i] >= F)) return pfail(TAXOR_E_ARG, "profile_create: reference id out of range");
+        if (csr->ref[i] < -1 || (csr->ref[i] >= 0 && (uint64_t)csr->ref[i] >= F)) return fail(TAXOR_E_ARG, "profile_create: reference id out of range");
     PF_TRY(hipSetDevice(device));
     auto p = std::make_unique<taxor_gpu_profile>();
     p->device = device;
@@ -509,12 +461,12 @@ extern "C" int taxor_gpu_profile_create(int device, const taxor_profile_csr *csr
     p->h_query_len.assign(csr->query_len, csr->query_len + R);
     p->h_hash_count.assign(csr->hash_count, csr->hash_count + R);
     PF_TRY(hipStreamCreate(&p->st));
-    PF_TRY(p->d_off.alloc(R + 1));
-    PF_TRY(p->d_ref.alloc(M));
-    PF_TRY(p->d_ref_len.alloc(M));
-    PF_TRY(p->d_hash_match.alloc(M));
-    PF_TRY(p->d_query_len.alloc(R));
-    PF_TRY(p->d_hash_count.alloc(R));
+    PF_TRY(alloc(p->d_off, R + 1));
+    PF_TRY(alloc(p->d_ref, M));
+    PF_TRY(alloc(p->d_ref_len, M));
+    PF_TRY(alloc(p->d_hash_match, M));
+    PF_TRY(alloc(p->d_query_len, R));
+    PF_TRY(alloc(p->d_hash_count, R));
     if (int rc = alloc_work(p.get())) return rc;
     PF_TRY(hipMemcpy(p->d_off.p, csr->read_off, (R + 1) * 8, hipMemcpyHostToDevice));
     if (M) {
@@ -536,14 +488,14 @@ extern "C" __attribute__((visibility("hidden"))) int taxor_profile_adopt_device(
                                                                                 uint64_t *d_off, int32_t *d_ref, uint64_t *d_ref_len, uint64_t *d_hash_match,
                                                                                 uint64_t *d_query_len, uint64_t *d_hash_count, taxor_gpu_profile **out)
 {
-    if (!host || !*host || !out || !d_off || !d_ref || !d_ref_len || !d_hash_match || !d_query_len || !d_hash_count) return pfail(TAXOR_E_ARG, "profile_adopt: null argument");
+    if (!host || !*host || !out || !d_off || !d_ref || !d_ref_len || !d_hash_match || !d_query_len || !d_hash_count) return fail(TAXOR_E_ARG, "profile_adopt: null argument");
     *out = nullptr;
     const taxor_profile_host_csr &h = **host;
-    if (h.off.empty()) return pfail(TAXOR_E_ARG, "profile_adopt: read_off is empty");
+    if (h.off.empty()) return fail(TAXOR_E_ARG, "profile_adopt: read_off is empty");
     const uint64_t R = h.off.size() - 1, F = n_refs, M = h.off[R];
-    if (F >= (1ull << 31)) return pfail(TAXOR_E_ARG, "profile_adopt: more than 2^31 - 1 references");
+    if (F >= (1ull << 31)) return fail(TAXOR_E_ARG, "profile_adopt: more than 2^31 - 1 references");
     if (h.off[0] != 0 || h.ref_len.size() != M || h.hash_match.size() != M || h.query_len.size() != R || h.hash_count.size() != R)
-        return pfail(TAXOR_E_ARG, "profile_adopt: the host arrays do not span the reads and the matches");
+        return fail(TAXOR_E_ARG, "profile_adopt: the host arrays do not span the reads and the matches");
     PF_TRY(hipSetDevice(device));
     auto p = std::make_unique<taxor_gpu_profile>(*host);
     p->device = device;
@@ -571,16 +523,16 @@ extern "C" void taxor_gpu_profile_destroy(taxor_gpu_profile *p)
 
 extern "C" int taxor_gpu_profile_run(taxor_gpu_profile *p, uint32_t em_steps, uint32_t flags)
 {
-    if (!p) return pfail(TAXOR_E_ARG, "profile_run: null argument");
-    if (em_steps < 1) return pfail(TAXOR_E_ARG, "profile_run: em_steps < 1");
-    if (p->ran) return pfail(TAXOR_E_ARG, "profile_run: this object has run already (the rounds consume its matches)");
+    if (!p) return fail(TAXOR_E_ARG, "profile_run: null argument");
+    if (em_steps < 1) return fail(TAXOR_E_ARG, "profile_run: em_steps < 1");
+    if (p->ran) return fail(TAXOR_E_ARG, "profile_run: this object has run already (the rounds consume its matches)");
     p->ran = true;
     const bool trace = (flags & TAXOR_PROFILE_TRACE) != 0;
     const uint64_t R = p->n_reads, F = p->n_refs, M = p->n_matches;
-    const double t0 = pf_now();
+    const double t0 = now_s();
     PF_TRY(hipSetDevice(p->device));
     hipStream_t st = p->st;
-    const int g = grid_reads(R), gf = (int)std::max<uint64_t>(1, std::min<uint64_t>(P_GRID_CAP, (F + PB - 1) / PB));
+    const int g = grid_for(R, PW, P_GRID_CAP), gf = grid_for(F, PB, P_GRID_CAP);
     auto snapshot = [&](std::vector<uint8_t> &v) -> hipError_t {
         v.resize(M);
         return M ? hipMemcpyAsync(v.data(), p->d_alive.p, M, hipMemcpyDeviceToHost, st) : hipSuccess;
@@ -615,8 +567,8 @@ extern "C" int taxor_gpu_profile_run(taxor_gpu_profile *p, uint32_t em_steps, ui
     uint64_t slots = 64;
     while (slots < 2 * pair_bound) slots <<= 1;
     p->pair_slots = slots;
-    PF_TRY(p->d_keys.alloc(slots));
-    PF_TRY(p->d_cnt.alloc(slots));
+    PF_TRY(alloc(p->d_keys, slots));
+    PF_TRY(alloc(p->d_cnt, slots));
     PF_TRY(hipMemsetAsync(p->d_keys.p, 0xFF, slots * 8, st));
     PF_TRY(hipMemsetAsync(p->d_cnt.p, 0, slots * 4, st));
     PF_TRY(hipMemsetAsync(p->d_uniq.p, 0, std::max<uint64_t>(F, 1) * 4, st));
@@ -638,7 +590,7 @@ extern "C" int taxor_gpu_profile_run(taxor_gpu_profile *p, uint32_t em_steps, ui
     }
     PF_TRY(hipMemcpyAsync(&h_err, p->d_err.p, 4, hipMemcpyDeviceToHost, st));
     PF_TRY(hipStreamSynchronize(st));
-    if (h_err & PF_TABLE_FULL) return pfail(TAXOR_E_INTERNAL, "profile: the pair table overflowed its sizing bound");
+    if (h_err & PF_TABLE_FULL) return fail(TAXOR_E_INTERNAL, "profile: the pair table overflowed its sizing bound");
     p->r_pair_key.clear();
     p->r_pair_count.clear();
     for (uint64_t s = 0; s < slots; ++s)
@@ -703,7 +655,7 @@ extern "C" int taxor_gpu_profile_run(taxor_gpu_profile *p, uint32_t em_steps, ui
     unsigned long long h_tot[2] = {0, 0};
     double cond = -DBL_MAX, log_unclassified = 0.0;
     uint32_t step = 0, iterations = 0;
-    const double t_em = pf_now();
+    const double t_em = now_s();
     while (step < em_steps) {
         k_pf_sum_ratio<<<g, PB, 0, st>>>(p->d_off.p, p->d_alive.p, p->d_hash_match.p, p->d_hash_count.p, R, p->d_sum.p);
         if (R) PF_TRY(hipMemcpyAsync(h_sum.data(), p->d_sum.p, R * 8, hipMemcpyDeviceToHost, st));
@@ -725,7 +677,7 @@ extern "C" int taxor_gpu_profile_run(taxor_gpu_profile *p, uint32_t em_steps, ui
         PF_TRY(hipMemcpyAsync(&h_err, p->d_err.p, 4, hipMemcpyDeviceToHost, st));
         PF_TRY(hipStreamSynchronize(st));
         if (h_err & PF_NO_PRIOR)
-            return pfail(TAXOR_E_ARG, "profile: in EM iteration " + std::to_string(iterations) + " a read with several matches has none whose reference "
+            return fail(TAXOR_E_ARG, "profile: in EM iteration " + std::to_string(iterations) + " a read with several matches has none whose reference "
                                       "carries a prior (all of them were explained away); the reference implementation erases an invalid iterator there");
         ++iterations;
         if (trace) p->r_iter_ref_nts.insert(p->r_iter_ref_nts.end(), p->r_ref_nts.begin(), p->r_ref_nts.end());
@@ -748,7 +700,7 @@ extern "C" int taxor_gpu_profile_run(taxor_gpu_profile *p, uint32_t em_steps, ui
         PF_TRY(hipMemcpyAsync(p->r_best.data(), p->d_best.p, M, hipMemcpyDeviceToHost, st));
     }
     PF_TRY(hipStreamSynchronize(st));
-    const double t1 = pf_now();
+    const double t1 = now_s();
     taxor_profile_results &o = p->res;
     memset(&o, 0, sizeof o);
     o.n_reads = R;
@@ -788,8 +740,8 @@ extern "C" int taxor_gpu_profile_run(taxor_gpu_profile *p, uint32_t em_steps, ui
 
 extern "C" int taxor_gpu_profile_results(taxor_gpu_profile *p, taxor_profile_results *out)
 {
-    if (!p || !out) return pfail(TAXOR_E_ARG, "profile_results: null argument");
-    if (!p->done) return pfail(TAXOR_E_ARG, "profile_results: no completed run");
+    if (!p || !out) return fail(TAXOR_E_ARG, "profile_results: null argument");
+    if (!p->done) return fail(TAXOR_E_ARG, "profile_results: no completed run");
     *out = p->res;
     return TAXOR_OK;
 }

@@ -16,6 +16,8 @@
 //                  QUERY_LEN and QHASH_COUNT (0 for a "-" read, like profile_parse_range leaves it for a six-column line)
 //   k_ff_counts_by_rank / k_ff_permute   finish: per-read counts gathered by rank, scanned, each read's segment copied
 #include "../../include/taxor_gpu_tools.h"
+#include "device_prims.h"
+#include "hip_host.h"
 #include "profile_host.h"
 
 #include <hip/hip_runtime.h>
@@ -26,7 +28,6 @@
 #include <string>
 #include <vector>
 
-extern "C" __attribute__((visibility("hidden"))) void taxor_set_last_error(const char *msg);
 // api.hip: the device-resident CSR of a searcher's last run (synchronises it), and the reads' lengths in input order
 extern "C" __attribute__((visibility("hidden"))) int taxor_searcher_device_results(taxor_gpu_searcher *s, const uint64_t **d_read_off,
                                                                                    const int64_t **d_user_bin, const uint32_t **d_count,
@@ -40,6 +41,8 @@ extern "C" __attribute__((visibility("hidden"))) int taxor_profile_adopt_device(
 
 namespace {
 
+using namespace taxor;
+
 constexpr int FB = 256;                  // threads per block
 constexpr int FW = FB / 64;              // reads per block pass (one wave each)
 constexpr int F_GRID_CAP = 2048;
@@ -49,29 +52,18 @@ constexpr uint64_t MAX_READS = 1ull << 36;
 
 enum : uint32_t { FF_BAD_BIN = 1u };
 
-__device__ __forceinline__ uint32_t ff_lane() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint64_t ff_first_read() { return (uint64_t)blockIdx.x * FW + (threadIdx.x >> 6); }
 __device__ __forceinline__ uint64_t ff_read_step() { return (uint64_t)gridDim.x * FW; }
-
-__device__ __forceinline__ uint32_t ff_wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const uint32_t t = __shfl_xor(v, d);
-        v = t > v ? t : v;
-    }
-    return v;
-}
 
 // the largest count among tuples [lo, hi) of `count` (indexed from t0); the same in every lane
 __device__ __forceinline__ uint32_t ff_read_max(const uint32_t *__restrict__ count, uint64_t t0, uint64_t lo, uint64_t hi)
 {
     uint32_t mx = 0;
-    for (uint64_t i = lo + ff_lane(); i < hi; i += 64) {
+    for (uint64_t i = lo + lane_id(); i < hi; i += 64) {
         const uint32_t c = count[i - t0];
         mx = c > mx ? c : mx;
     }
-    return ff_wave_max(mx);
+    return wave_max(mx);
 }
 
 // taxor_search.cpp:285, evaluated as written
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(FB) void k_ff_count(const uint64_t *__restrict__ of
         uint64_t n = 0;
         bool bad = false;
         for (uint64_t base = lo; base < hi; base += 64) {
-            const uint64_t i = base + ff_lane();
+            const uint64_t i = base + lane_id();
             bool k = false;
             if (i < hi) {
                 const int64_t b = ub[i - t0];
@@ -97,34 +89,11 @@ __global__ __launch_bounds__(FB) void k_ff_count(const uint64_t *__restrict__ of
             n += (uint64_t)__popcll(__ballot(k));
         }
         if (bad) atomicOr(err, FF_BAD_BIN);
-        if (ff_lane() == 0) kept[r] = n ? n : 1;
+        if (lane_id() == 0) kept[r] = n ? n : 1;
     }
 }
 
 // ---- exclusive scan of in[n] into out[n + 1] (out[n] = the total): tile-local scan and tile sums, the sums by one block, add back
-__device__ __forceinline__ uint64_t ff_block_exclusive(uint64_t v, uint64_t *total)
-{
-    __shared__ uint64_t wave_sum[FW];
-    const uint32_t lane = ff_lane(), w = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t t = __shfl_up(inc, d);
-        if (lane >= (uint32_t)d) inc += t;
-    }
-    __syncthreads();                                   // a previous call's readers are done with wave_sum
-    if (lane == 63) wave_sum[w] = inc;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (int j = 0; j < FW; ++j) {
-        if ((uint32_t)j < w) before += wave_sum[j];
-        all += wave_sum[j];
-    }
-    *total = all;
-    return before + inc - v;
-}
-
 __global__ __launch_bounds__(FB) void k_ff_scan_tiles(const uint64_t *__restrict__ in, uint64_t n, uint64_t *__restrict__ out, uint64_t *__restrict__ sums)
 {
     const uint64_t first = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
@@ -134,8 +103,9 @@ __global__ __launch_bounds__(FB) void k_ff_scan_tiles(const uint64_t *__restrict
         v[j] = first + j < n ? in[first + j] : 0;
         mine += v[j];
     }
+    __shared__ uint64_t sScr[FW];
     uint64_t total;
-    uint64_t run = ff_block_exclusive(mine, &total);
+    uint64_t run = block_excl_add<FW>(mine, sScr, &total);
 #pragma unroll
     for (int j = 0; j < SCAN_ITEMS; ++j) {
         if (first + j < n) out[first + j] = run;
@@ -147,12 +117,13 @@ __global__ __launch_bounds__(FB) void k_ff_scan_tiles(const uint64_t *__restrict
 // one block: sums[n_tiles] -> exclusive, in place; out_total[0] = everything
 __global__ __launch_bounds__(FB) void k_ff_scan_sums(uint64_t *__restrict__ sums, uint64_t n_tiles, uint64_t *__restrict__ out_total)
 {
+    __shared__ uint64_t sScr[FW];
     uint64_t carry = 0;
     for (uint64_t base = 0; base < n_tiles; base += FB) {
         const uint64_t i = base + threadIdx.x;
         const uint64_t v = i < n_tiles ? sums[i] : 0;
         uint64_t total;
-        const uint64_t ex = ff_block_exclusive(v, &total);
+        const uint64_t ex = block_excl_add<FW>(v, sScr, &total);
         if (i < n_tiles) sums[i] = carry + ex;
         carry += total;
     }
@@ -188,7 +159,7 @@ __global__ __launch_bounds__(FB) void k_ff_scatter(const uint64_t *__restrict__ 
         const uint64_t dst0 = base + pos[r];
         uint64_t written = 0;
         for (uint64_t b0 = lo; b0 < hi; b0 += 64) {
-            const uint64_t i = b0 + ff_lane();
+            const uint64_t i = b0 + lane_id();
             uint32_t c = 0;
             int64_t bin = 0;
             bool k = false;
@@ -199,7 +170,7 @@ __global__ __launch_bounds__(FB) void k_ff_scatter(const uint64_t *__restrict__ 
             }
             const uint64_t m = __ballot(k);
             if (k) {
-                const uint64_t d = dst0 + written + (uint64_t)__popcll(m & ((1ull << ff_lane()) - 1ull));
+                const uint64_t d = dst0 + written + (uint64_t)__popcll(m & ((1ull << lane_id()) - 1ull));
                 st.m_ref[d] = ref_of_bin[bin];
                 st.m_ref_len[d] = ref_len_of_bin[bin];
                 st.m_hash_match[d] = c;
@@ -207,7 +178,7 @@ __global__ __launch_bounds__(FB) void k_ff_scatter(const uint64_t *__restrict__ 
             }
             written += (uint64_t)__popcll(m);
         }
-        if (ff_lane() == 0) {
+        if (lane_id() == 0) {
             if (written == 0) {                        // the read's "-" line
                 st.m_ref[dst0] = -1;
                 st.m_ref_len[dst0] = 0;
@@ -236,72 +207,26 @@ __global__ __launch_bounds__(FB) void k_ff_permute(const uint64_t *__restrict__ 
 {
     for (uint64_t r = ff_first_read(); r < n; r += ff_read_step()) {
         const uint64_t k = rank[r], src = st.r_start[r], dst = off[k], c = st.r_count[r];
-        for (uint64_t j = ff_lane(); j < c; j += 64) {
+        for (uint64_t j = lane_id(); j < c; j += 64) {
             o_ref[dst + j] = st.m_ref[src + j];
             o_ref_len[dst + j] = st.m_ref_len[src + j];
             o_hash_match[dst + j] = st.m_hash_match[src + j];
             o_user_bin[dst + j] = st.m_user_bin[src + j];
         }
-        if (ff_lane() == 0) {
+        if (lane_id() == 0) {
             o_query_len[k] = st.r_query_len[r];
             o_hash_count[k] = st.r_hash_count[r];
         }
     }
 }
 
-int ffail(int code, const std::string &msg)
+#define FF_TRY(expr) TAXOR_HIP_TRY_PREFIX("profile_feed", expr, #expr)
+
+// a feed's arrays grow geometrically and keep their first `keep` elements
+template <class T> hipError_t grow(DeviceBuf<T> &b, uint64_t want, uint64_t keep, hipStream_t st)
 {
-    taxor_set_last_error(msg.c_str());
-    return code;
+    return b.grow(want, std::max<uint64_t>({want, b.cap + b.cap / 2, 1024}), keep, st);
 }
-
-#define FF_TRY(expr)                                                                                                         \
-    do {                                                                                                                     \
-        const hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) return ffail(TAXOR_E_HIP, std::string("profile_feed: ") + #expr + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// a device array that grows geometrically and keeps its content
-template <class T> struct FBuf {
-    T *p = nullptr;
-    uint64_t cap = 0;
-    hipError_t grow(uint64_t want, uint64_t keep, hipStream_t st)
-    {
-        if (p && want <= cap) return hipSuccess;
-        const uint64_t c = std::max<uint64_t>({want, cap + cap / 2, 1024});
-        T *q = nullptr;
-        hipError_t e = hipMalloc((void **)&q, c * sizeof(T));
-        if (e != hipSuccess) return e;
-        if (keep) {
-            e = hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) {
-                (void)hipFree(q);
-                return e;
-            }
-        }
-        if (p) (void)hipFree(p);
-        p = q;
-        cap = c;
-        return hipSuccess;
-    }
-    T *take()
-    {
-        T *q = p;
-        p = nullptr;
-        cap = 0;
-        return q;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    ~FBuf() { release(); }
-};
-
-int grid_reads(uint64_t n) { return (int)std::max<uint64_t>(1, std::min<uint64_t>(F_GRID_CAP, (n + FW - 1) / FW)); }
 
 }   // namespace
 
@@ -310,15 +235,15 @@ struct taxor_gpu_profile_feed {
     uint64_t n_bins = 0, n_refs = 0;
     hipStream_t st = nullptr;
     std::mutex mu;                                   // batches may come from several threads
-    FBuf<int32_t> d_ref_of_bin, m_ref, o_ref;
-    FBuf<uint64_t> d_ref_len_of_bin, m_ref_len, m_hash_match, r_start, r_count, r_query_len, r_hash_count;
-    FBuf<int64_t> m_user_bin, o_user_bin;
-    FBuf<uint64_t> b_kept, b_pos, b_sums;            // per batch: kept counts, their scan, the scan's tile sums
-    FBuf<uint32_t> d_err;
+    DeviceBuf<int32_t> d_ref_of_bin, m_ref, o_ref;
+    DeviceBuf<uint64_t> d_ref_len_of_bin, m_ref_len, m_hash_match, r_start, r_count, r_query_len, r_hash_count;
+    DeviceBuf<int64_t> m_user_bin, o_user_bin;
+    DeviceBuf<uint64_t> b_kept, b_pos, b_sums;            // per batch: kept counts, their scan, the scan's tile sums
+    DeviceBuf<uint32_t> d_err;
     // host arrays of add_csr on the device
-    FBuf<uint64_t> c_off, c_qlen;
-    FBuf<int64_t> c_ub;
-    FBuf<uint32_t> c_cnt, c_nh;
+    DeviceBuf<uint64_t> c_off, c_qlen;
+    DeviceBuf<int64_t> c_ub;
+    DeviceBuf<uint32_t> c_cnt, c_nh;
     uint64_t m_used = 0, r_cap_used = 0;
     std::vector<std::pair<uint64_t, uint64_t>> ranges;   // (first_read, n_reads) of every batch
     bool finished = false;
@@ -350,7 +275,7 @@ int scan_counts(taxor_gpu_profile_feed *f, const uint64_t *in, uint64_t n, uint6
         return TAXOR_OK;
     }
     const uint64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    FF_TRY(f->b_sums.grow(tiles, 0, f->st));
+    FF_TRY(grow(f->b_sums, tiles, 0, f->st));
     k_ff_scan_tiles<<<(int)tiles, FB, 0, f->st>>>(in, n, out, f->b_sums.p);
     k_ff_scan_sums<<<1, FB, 0, f->st>>>(f->b_sums.p, tiles, out + n);
     k_ff_scan_add<<<(int)tiles, FB, 0, f->st>>>(out, n, f->b_sums.p);
@@ -364,37 +289,37 @@ int scan_counts(taxor_gpu_profile_feed *f, const uint64_t *in, uint64_t n, uint6
 int add_device(taxor_gpu_profile_feed *f, uint64_t first_read, uint64_t n, const uint64_t *d_off, const int64_t *d_ub, const uint32_t *d_cnt,
                const uint32_t *d_nh, const uint32_t *d_rlen32, const uint64_t *d_qlen64, uint64_t t0, uint32_t flags)
 {
-    if (f->finished) return ffail(TAXOR_E_ARG, "profile_feed_add: the feed is finished");
-    if (flags & ~TAXOR_FEED_KEEP_ALL) return ffail(TAXOR_E_ARG, "profile_feed_add: unknown flag");
-    if (first_read >= MAX_READS || n >= MAX_READS) return ffail(TAXOR_E_ARG, "profile_feed_add: read index beyond 2^36");
+    if (f->finished) return fail(TAXOR_E_ARG, "profile_feed_add: the feed is finished");
+    if (flags & ~TAXOR_FEED_KEEP_ALL) return fail(TAXOR_E_ARG, "profile_feed_add: unknown flag");
+    if (first_read >= MAX_READS || n >= MAX_READS) return fail(TAXOR_E_ARG, "profile_feed_add: read index beyond 2^36");
     if (n == 0) {
         f->ranges.emplace_back(first_read, n);
         return TAXOR_OK;
     }
     const int keep_all = (flags & TAXOR_FEED_KEEP_ALL) ? 1 : 0;
-    FF_TRY(f->b_kept.grow(n, 0, f->st));
-    FF_TRY(f->b_pos.grow(n + 1, 0, f->st));
+    FF_TRY(grow(f->b_kept, n, 0, f->st));
+    FF_TRY(grow(f->b_pos, n + 1, 0, f->st));
     FF_TRY(hipMemsetAsync(f->d_err.p, 0, 4, f->st));
-    k_ff_count<<<grid_reads(n), FB, 0, f->st>>>(d_off, d_ub, d_cnt, t0, n, f->n_bins, keep_all, f->b_kept.p, f->d_err.p);
+    k_ff_count<<<grid_for(n, FW, F_GRID_CAP), FB, 0, f->st>>>(d_off, d_ub, d_cnt, t0, n, f->n_bins, keep_all, f->b_kept.p, f->d_err.p);
     FF_TRY(hipGetLastError());
     uint64_t total = 0;
     uint32_t err = 0;
     FF_TRY(hipMemcpyAsync(&err, f->d_err.p, 4, hipMemcpyDeviceToHost, f->st));
     if (int rc = scan_counts(f, f->b_kept.p, n, f->b_pos.p, &total)) return rc;     // synchronises the stream
     if (err & FF_BAD_BIN)
-        return ffail(TAXOR_E_ARG, "profile_feed_add: a user bin lies outside the feed's table of " + std::to_string(f->n_bins) + " user bins");
+        return fail(TAXOR_E_ARG, "profile_feed_add: a user bin lies outside the feed's table of " + std::to_string(f->n_bins) + " user bins");
     // a batch is never truncated: the stores grow to hold it
     const uint64_t need_m = f->m_used + total, need_r = first_read + n;
-    FF_TRY(f->m_ref.grow(need_m, f->m_used, f->st));
-    FF_TRY(f->m_ref_len.grow(need_m, f->m_used, f->st));
-    FF_TRY(f->m_hash_match.grow(need_m, f->m_used, f->st));
-    FF_TRY(f->m_user_bin.grow(need_m, f->m_used, f->st));
-    FF_TRY(f->r_start.grow(need_r, f->r_cap_used, f->st));
-    FF_TRY(f->r_count.grow(need_r, f->r_cap_used, f->st));
-    FF_TRY(f->r_query_len.grow(need_r, f->r_cap_used, f->st));
-    FF_TRY(f->r_hash_count.grow(need_r, f->r_cap_used, f->st));
+    FF_TRY(grow(f->m_ref, need_m, f->m_used, f->st));
+    FF_TRY(grow(f->m_ref_len, need_m, f->m_used, f->st));
+    FF_TRY(grow(f->m_hash_match, need_m, f->m_used, f->st));
+    FF_TRY(grow(f->m_user_bin, need_m, f->m_used, f->st));
+    FF_TRY(grow(f->r_start, need_r, f->r_cap_used, f->st));
+    FF_TRY(grow(f->r_count, need_r, f->r_cap_used, f->st));
+    FF_TRY(grow(f->r_query_len, need_r, f->r_cap_used, f->st));
+    FF_TRY(grow(f->r_hash_count, need_r, f->r_cap_used, f->st));
     f->r_cap_used = std::max(f->r_cap_used, need_r);
-    k_ff_scatter<<<grid_reads(n), FB, 0, f->st>>>(d_off, d_ub, d_cnt, d_nh, d_rlen32, d_qlen64, t0, n, keep_all, f->b_pos.p, f->m_used, first_read,
+    k_ff_scatter<<<grid_for(n, FW, F_GRID_CAP), FB, 0, f->st>>>(d_off, d_ub, d_cnt, d_nh, d_rlen32, d_qlen64, t0, n, keep_all, f->b_pos.p, f->m_used, first_read,
                                                   f->d_ref_of_bin.p, f->d_ref_len_of_bin.p, store_of(f));
     FF_TRY(hipGetLastError());
     FF_TRY(hipStreamSynchronize(f->st));              // the caller's buffers (a searcher's results) may be reused from here on
@@ -408,21 +333,21 @@ int add_device(taxor_gpu_profile_feed *f, uint64_t first_read, uint64_t n, const
 extern "C" int taxor_gpu_profile_feed_create(int device, uint64_t n_user_bins, const int32_t *ref_of_bin, const uint64_t *ref_len_of_bin, uint64_t n_refs,
                                              taxor_gpu_profile_feed **out)
 {
-    if (!out) return ffail(TAXOR_E_ARG, "profile_feed_create: null argument");
+    if (!out) return fail(TAXOR_E_ARG, "profile_feed_create: null argument");
     *out = nullptr;
-    if (n_user_bins && (!ref_of_bin || !ref_len_of_bin)) return ffail(TAXOR_E_ARG, "profile_feed_create: null array");
-    if (n_refs >= (1ull << 31)) return ffail(TAXOR_E_ARG, "profile_feed_create: more than 2^31 - 1 references");
+    if (n_user_bins && (!ref_of_bin || !ref_len_of_bin)) return fail(TAXOR_E_ARG, "profile_feed_create: null array");
+    if (n_refs >= (1ull << 31)) return fail(TAXOR_E_ARG, "profile_feed_create: more than 2^31 - 1 references");
     for (uint64_t u = 0; u < n_user_bins; ++u)
-        if (ref_of_bin[u] < 0 || (uint64_t)ref_of_bin[u] >= n_refs) return ffail(TAXOR_E_ARG, "profile_feed_create: reference id of user bin " + std::to_string(u) + " out of range");
+        if (ref_of_bin[u] < 0 || (uint64_t)ref_of_bin[u] >= n_refs) return fail(TAXOR_E_ARG, "profile_feed_create: reference id of user bin " + std::to_string(u) + " out of range");
     FF_TRY(hipSetDevice(device));
     auto f = std::make_unique<taxor_gpu_profile_feed>();
     f->device = device;
     f->n_bins = n_user_bins;
     f->n_refs = n_refs;
     FF_TRY(hipStreamCreate(&f->st));
-    FF_TRY(f->d_ref_of_bin.grow(n_user_bins, 0, f->st));
-    FF_TRY(f->d_ref_len_of_bin.grow(n_user_bins, 0, f->st));
-    FF_TRY(f->d_err.grow(1, 0, f->st));
+    FF_TRY(grow(f->d_ref_of_bin, n_user_bins, 0, f->st));
+    FF_TRY(grow(f->d_ref_len_of_bin, n_user_bins, 0, f->st));
+    FF_TRY(grow(f->d_err, 1, 0, f->st));
     if (n_user_bins) {
         FF_TRY(hipMemcpy(f->d_ref_of_bin.p, ref_of_bin, n_user_bins * 4, hipMemcpyHostToDevice));
         FF_TRY(hipMemcpy(f->d_ref_len_of_bin.p, ref_len_of_bin, n_user_bins * 8, hipMemcpyHostToDevice));
@@ -440,14 +365,14 @@ extern "C" void taxor_gpu_profile_feed_destroy(taxor_gpu_profile_feed *f)
 
 extern "C" int taxor_gpu_profile_feed_add_batch(taxor_gpu_profile_feed *f, taxor_gpu_searcher *s, uint64_t first_read, uint32_t flags)
 {
-    if (!f || !s) return ffail(TAXOR_E_ARG, "profile_feed_add_batch: null argument");
+    if (!f || !s) return fail(TAXOR_E_ARG, "profile_feed_add_batch: null argument");
     const uint64_t *d_off = nullptr;
     const int64_t *d_ub = nullptr;
     const uint32_t *d_cnt = nullptr, *d_nh = nullptr, *d_rlen = nullptr;
     uint64_t n = 0, nt = 0;
     int dev = 0;
     if (int rc = taxor_searcher_device_results(s, &d_off, &d_ub, &d_cnt, &d_nh, &n, &nt, &dev)) return rc;
-    if (dev != f->device) return ffail(TAXOR_E_ARG, "profile_feed_add_batch: the searcher runs on device " + std::to_string(dev) + ", the feed on " + std::to_string(f->device));
+    if (dev != f->device) return fail(TAXOR_E_ARG, "profile_feed_add_batch: the searcher runs on device " + std::to_string(dev) + ", the feed on " + std::to_string(f->device));
     if (int rc = taxor_searcher_device_read_lengths(s, &d_rlen)) return rc;
     std::lock_guard<std::mutex> lk(f->mu);
     FF_TRY(hipSetDevice(f->device));
@@ -457,20 +382,20 @@ extern "C" int taxor_gpu_profile_feed_add_batch(taxor_gpu_profile_feed *f, taxor
 extern "C" int taxor_gpu_profile_feed_add_csr(taxor_gpu_profile_feed *f, uint64_t first_read, uint64_t n_reads, const uint64_t *read_off, const int64_t *user_bin,
                                               const uint32_t *count, const uint32_t *n_hashes, const uint64_t *query_len, uint32_t flags)
 {
-    if (!f || !read_off) return ffail(TAXOR_E_ARG, "profile_feed_add_csr: null argument");
-    if (n_reads && (!n_hashes || !query_len)) return ffail(TAXOR_E_ARG, "profile_feed_add_csr: null array");
-    if (n_reads >= MAX_READS) return ffail(TAXOR_E_ARG, "profile_feed_add_csr: read index beyond 2^36");
+    if (!f || !read_off) return fail(TAXOR_E_ARG, "profile_feed_add_csr: null argument");
+    if (n_reads && (!n_hashes || !query_len)) return fail(TAXOR_E_ARG, "profile_feed_add_csr: null array");
+    if (n_reads >= MAX_READS) return fail(TAXOR_E_ARG, "profile_feed_add_csr: read index beyond 2^36");
     for (uint64_t r = 0; r < n_reads; ++r)
-        if (read_off[r + 1] < read_off[r]) return ffail(TAXOR_E_ARG, "profile_feed_add_csr: read_off decreases");
+        if (read_off[r + 1] < read_off[r]) return fail(TAXOR_E_ARG, "profile_feed_add_csr: read_off decreases");
     const uint64_t t0 = read_off[0], nt = read_off[n_reads] - t0;
-    if (nt && (!user_bin || !count)) return ffail(TAXOR_E_ARG, "profile_feed_add_csr: null array");
+    if (nt && (!user_bin || !count)) return fail(TAXOR_E_ARG, "profile_feed_add_csr: null array");
     std::lock_guard<std::mutex> lk(f->mu);
     FF_TRY(hipSetDevice(f->device));
-    FF_TRY(f->c_off.grow(n_reads + 1, 0, f->st));
-    FF_TRY(f->c_ub.grow(nt, 0, f->st));
-    FF_TRY(f->c_cnt.grow(nt, 0, f->st));
-    FF_TRY(f->c_nh.grow(n_reads, 0, f->st));
-    FF_TRY(f->c_qlen.grow(n_reads, 0, f->st));
+    FF_TRY(grow(f->c_off, n_reads + 1, 0, f->st));
+    FF_TRY(grow(f->c_ub, nt, 0, f->st));
+    FF_TRY(grow(f->c_cnt, nt, 0, f->st));
+    FF_TRY(grow(f->c_nh, n_reads, 0, f->st));
+    FF_TRY(grow(f->c_qlen, n_reads, 0, f->st));
     FF_TRY(hipMemcpy(f->c_off.p, read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice));
     if (nt) {
         FF_TRY(hipMemcpy(f->c_ub.p, user_bin + t0, nt * 8, hipMemcpyHostToDevice));
@@ -485,11 +410,11 @@ extern "C" int taxor_gpu_profile_feed_add_csr(taxor_gpu_profile_feed *f, uint64_
 
 extern "C" int taxor_gpu_profile_feed_finish(taxor_gpu_profile_feed *f, const uint64_t *rank_of_read, uint64_t n_reads_total, taxor_gpu_profile **profile)
 {
-    if (!f || !profile) return ffail(TAXOR_E_ARG, "profile_feed_finish: null argument");
+    if (!f || !profile) return fail(TAXOR_E_ARG, "profile_feed_finish: null argument");
     *profile = nullptr;
-    if (n_reads_total && !rank_of_read) return ffail(TAXOR_E_ARG, "profile_feed_finish: null argument");
+    if (n_reads_total && !rank_of_read) return fail(TAXOR_E_ARG, "profile_feed_finish: null argument");
     std::lock_guard<std::mutex> lk(f->mu);
-    if (f->finished) return ffail(TAXOR_E_ARG, "profile_feed_finish: the feed is finished");
+    if (f->finished) return fail(TAXOR_E_ARG, "profile_feed_finish: the feed is finished");
     // the batches' ranges cover [0, n_reads_total) exactly, once
     {
         std::vector<std::pair<uint64_t, uint64_t>> rg;
@@ -499,46 +424,46 @@ extern "C" int taxor_gpu_profile_feed_finish(taxor_gpu_profile_feed *f, const ui
         uint64_t next = 0;
         for (const auto &x : rg) {
             if (x.first > next)
-                return ffail(TAXOR_E_ARG, "profile_feed_finish: reads " + std::to_string(next) + " to " + std::to_string(x.first - 1) + " were never added (a gap between the batches)");
+                return fail(TAXOR_E_ARG, "profile_feed_finish: reads " + std::to_string(next) + " to " + std::to_string(x.first - 1) + " were never added (a gap between the batches)");
             if (x.first < next)
-                return ffail(TAXOR_E_ARG, "profile_feed_finish: read " + std::to_string(x.first) + " was added twice (the batches' ranges overlap)");
+                return fail(TAXOR_E_ARG, "profile_feed_finish: read " + std::to_string(x.first) + " was added twice (the batches' ranges overlap)");
             next = x.first + x.second;
         }
         if (next != n_reads_total)
-            return ffail(TAXOR_E_ARG, "profile_feed_finish: " + std::to_string(next) + " reads were added, " + std::to_string(n_reads_total) + " are to be ranked");
+            return fail(TAXOR_E_ARG, "profile_feed_finish: " + std::to_string(next) + " reads were added, " + std::to_string(n_reads_total) + " are to be ranked");
     }
     const uint64_t R = n_reads_total, M = f->m_used;
     {
         std::vector<uint8_t> seen(R, 0);
         for (uint64_t i = 0; i < R; ++i) {
             const uint64_t k = rank_of_read[i];
-            if (k >= R) return ffail(TAXOR_E_ARG, "profile_feed_finish: rank " + std::to_string(k) + " of read " + std::to_string(i) + " is not below the number of reads");
-            if (seen[k]) return ffail(TAXOR_E_ARG, "profile_feed_finish: rank " + std::to_string(k) + " is used twice (rank_of_read is not a permutation)");
+            if (k >= R) return fail(TAXOR_E_ARG, "profile_feed_finish: rank " + std::to_string(k) + " of read " + std::to_string(i) + " is not below the number of reads");
+            if (seen[k]) return fail(TAXOR_E_ARG, "profile_feed_finish: rank " + std::to_string(k) + " is used twice (rank_of_read is not a permutation)");
             seen[k] = 1;
         }
     }
     FF_TRY(hipSetDevice(f->device));
     hipStream_t st = f->st;
-    FBuf<uint64_t> d_rank, d_by_rank, o_off, o_ref_len, o_hash_match, o_query_len, o_hash_count;
-    FF_TRY(d_rank.grow(R, 0, st));
-    FF_TRY(d_by_rank.grow(R, 0, st));
-    FF_TRY(o_off.grow(R + 1, 0, st));
-    FF_TRY(f->o_ref.grow(M, 0, st));
-    FF_TRY(o_ref_len.grow(M, 0, st));
-    FF_TRY(o_hash_match.grow(M, 0, st));
-    FF_TRY(f->o_user_bin.grow(M, 0, st));
-    FF_TRY(o_query_len.grow(R, 0, st));
-    FF_TRY(o_hash_count.grow(R, 0, st));
+    DeviceBuf<uint64_t> d_rank, d_by_rank, o_off, o_ref_len, o_hash_match, o_query_len, o_hash_count;
+    FF_TRY(grow(d_rank, R, 0, st));
+    FF_TRY(grow(d_by_rank, R, 0, st));
+    FF_TRY(grow(o_off, R + 1, 0, st));
+    FF_TRY(grow(f->o_ref, M, 0, st));
+    FF_TRY(grow(o_ref_len, M, 0, st));
+    FF_TRY(grow(o_hash_match, M, 0, st));
+    FF_TRY(grow(f->o_user_bin, M, 0, st));
+    FF_TRY(grow(o_query_len, R, 0, st));
+    FF_TRY(grow(o_hash_count, R, 0, st));
     if (R) {
         FF_TRY(hipMemcpyAsync(d_rank.p, rank_of_read, R * 8, hipMemcpyHostToDevice, st));
-        k_ff_counts_by_rank<<<(int)std::max<uint64_t>(1, std::min<uint64_t>(F_GRID_CAP, (R + FB - 1) / FB)), FB, 0, st>>>(d_rank.p, f->r_count.p, R, d_by_rank.p);
+        k_ff_counts_by_rank<<<grid_for(R, FB, F_GRID_CAP), FB, 0, st>>>(d_rank.p, f->r_count.p, R, d_by_rank.p);
         FF_TRY(hipGetLastError());
     }
     uint64_t total = 0;
     if (int rc = scan_counts(f, d_by_rank.p, R, o_off.p, &total)) return rc;
-    if (total != M) return ffail(TAXOR_E_INTERNAL, "profile_feed_finish: the reads hold " + std::to_string(total) + " matches, the store " + std::to_string(M));
+    if (total != M) return fail(TAXOR_E_INTERNAL, "profile_feed_finish: the reads hold " + std::to_string(total) + " matches, the store " + std::to_string(M));
     if (R) {
-        k_ff_permute<<<grid_reads(R), FB, 0, st>>>(d_rank.p, R, o_off.p, store_of(f), f->o_ref.p, o_ref_len.p, o_hash_match.p, f->o_user_bin.p, o_query_len.p,
+        k_ff_permute<<<grid_for(R, FW, F_GRID_CAP), FB, 0, st>>>(d_rank.p, R, o_off.p, store_of(f), f->o_ref.p, o_ref_len.p, o_hash_match.p, f->o_user_bin.p, o_query_len.p,
                                                    o_hash_count.p);
         FF_TRY(hipGetLastError());
     }
@@ -586,8 +511,8 @@ extern "C" int taxor_gpu_profile_feed_finish(taxor_gpu_profile_feed *f, const ui
 
 extern "C" int taxor_gpu_profile_feed_matches(const taxor_gpu_profile_feed *f, taxor_profile_csr *csr, const int64_t **user_bin)
 {
-    if (!f || (!csr && !user_bin)) return ffail(TAXOR_E_ARG, "profile_feed_matches: null argument");
-    if (!f->finished) return ffail(TAXOR_E_ARG, "profile_feed_matches: the feed is not finished");
+    if (!f || (!csr && !user_bin)) return fail(TAXOR_E_ARG, "profile_feed_matches: null argument");
+    if (!f->finished) return fail(TAXOR_E_ARG, "profile_feed_matches: the feed is not finished");
     if (csr) {
         csr->n_reads = f->h->query_len.size();
         csr->n_refs = f->n_refs;

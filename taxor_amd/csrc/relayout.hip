@@ -13,6 +13,8 @@
 // load's wall time (profiles/r05/relayout_kernel_stats.txt; the load stays bound by pread + PCIe: 41 GB/s bin-major against 44 GB/s
 // for the search layout at 64 GB).  The search layout itself never comes through here (api.hip index_upload copies it as it is).
 #include "../../include/taxor_gpu_tools.h"
+#include "device_prims.h"
+#include "hip_host.h"
 #include "ixf_layout.h"
 #include "tuning.h"
 
@@ -20,7 +22,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -28,7 +29,6 @@
 #include <thread>
 #include <vector>
 
-extern "C" __attribute__((visibility("hidden"))) void taxor_set_last_error(const char *msg);
 extern "C" __attribute__((visibility("hidden"))) int taxor_index_ixf_info(taxor_gpu_index *idx, uint64_t ixf, uint8_t **data, uint64_t *stride, uint64_t *seg_len,
                                                                           uint64_t *bins, int *device);
 
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void k_bit_sliced(const uint8_t *__restrict__ 
     const uint64_t blk = ic >> 3;
     const uint32_t q = (uint32_t)(ic & 7u);
     const uint64_t w = *reinterpret_cast<const uint64_t *>(stage + blk * 64u + q * 8u);
-    const int lane0 = (int)(threadIdx.x & 63u & ~7u);
+    const int lane0 = (int)(lane_id() & ~7u);
     uint64_t x = 0;
 #pragma unroll
     for (int p = 0; p < 8; ++p) {
@@ -137,12 +137,6 @@ struct Chunk {
     uint64_t b0, nb;      // bin-major only: columns
 };
 
-int rfail(int code, const std::string &m)
-{
-    taxor_set_last_error(m.c_str());
-    return code;
-}
-
 } // namespace
 
 // library-internal (api.hip index_upload): every IXF of `v` -- source bytes under v->ixf_layout / ixf[i].src_stride -- into the
@@ -150,7 +144,7 @@ int rfail(int code, const std::string &m)
 extern "C" __attribute__((visibility("hidden"))) int taxor_index_upload_relayout(taxor_gpu_index *idx, const taxor_hixf_view *v)
 {
     const uint32_t code = v->ixf_layout, kind = ixf_layout_kind(code);
-    if (!ixf_layout_valid(code)) return rfail(TAXOR_E_ARG, "index upload: unknown fingerprint layout code " + std::to_string(code));
+    if (!ixf_layout_valid(code)) return fail(TAXOR_E_ARG, "index upload: unknown fingerprint layout code " + std::to_string(code));
     static const uint64_t piece_bytes = [] { const char *e = tune_env("TAXOR_UPLOAD_PIECE_MB"); const long m = e ? atol(e) : 0; return (uint64_t)(m > 0 ? m : 8) << 20; }();
     struct Ixf { uint8_t *dst; uint64_t stride, seg_len, bins, rows, pitch, groups; };
     std::vector<Ixf> X(v->n_ixf);
@@ -159,11 +153,11 @@ extern "C" __attribute__((visibility("hidden"))) int taxor_index_upload_relayout
     uint64_t stage_bytes = 0;
     for (uint64_t i = 0; i < v->n_ixf; ++i) {
         Ixf &x = X[i];
-        if (taxor_index_ixf_info(idx, i, &x.dst, &x.stride, &x.seg_len, &x.bins, &device) != 0) return rfail(TAXOR_E_ARG, "index upload: view does not match the index");
+        if (taxor_index_ixf_info(idx, i, &x.dst, &x.stride, &x.seg_len, &x.bins, &device) != 0) return fail(TAXOR_E_ARG, "index upload: view does not match the index");
         x.rows = 3 * x.seg_len;
         x.groups = (x.bins + 63) / 64;
         x.pitch = kind == IXF_KIND_BIT_SLICED ? x.groups * 64 : ixf_src_pitch(v->ixf_layout, v->ixf[i].src_stride, x.stride, x.bins);
-        if (x.pitch < x.bins) return rfail(TAXOR_E_ARG, "index upload: IXF " + std::to_string(i) + ": source pitch " + std::to_string(x.pitch) + " below its " + std::to_string(x.bins) + " bins");
+        if (x.pitch < x.bins) return fail(TAXOR_E_ARG, "index upload: IXF " + std::to_string(i) + ": source pitch " + std::to_string(x.pitch) + " below its " + std::to_string(x.bins) + " bins");
         if (!v->source && !v->ixf[i].data) continue;
         if (kind == IXF_KIND_BIN_MAJOR) {
             const uint64_t nr_max = std::max<uint64_t>(128, (piece_bytes / 128) & ~(uint64_t)127);       // rows per strip: 128 columns of them fill a piece
@@ -183,7 +177,7 @@ extern "C" __attribute__((visibility("hidden"))) int taxor_index_upload_relayout
         }
     }
     if (chunks.empty()) return 0;
-    const auto t_begin = std::chrono::steady_clock::now();
+    const double t_begin = now_s();
     stage_bytes = (stage_bytes + 64 + 255) & ~(uint64_t)255;                 // slack: the re-pitch kernel reads whole dwords
     static const int n_threads = [] { const char *e = tune_env("TAXOR_UPLOAD_THREADS"); const int t = e ? atoi(e) : 0; return t >= 1 && t <= 64 ? t : 8; }();
     const int T = (int)std::min<size_t>((size_t)n_threads, chunks.size());
@@ -269,12 +263,12 @@ extern "C" __attribute__((visibility("hidden"))) int taxor_index_upload_relayout
             if (st) (void)hipStreamDestroy(st);
         });
     for (auto &t : th) t.join();
-    if (failed.load()) return rfail(err_code, err);
+    if (failed.load()) return fail(err_code, err);
     if (tune_env("TAXOR_TRACE_UPLOAD")) {
         uint64_t b = 0;
         for (uint64_t i = 0; i < v->n_ixf; ++i)
             if (v->source || v->ixf[i].data) b += ixf_src_bytes(code, X[i].rows, X[i].pitch, X[i].bins);
-        const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+        const double dt = now_s() - t_begin;
         fprintf(stderr, "[upload] %.2f GB in %.3f s = %.1f GB/s (%s, layout code %u transposed on the device, %zu chunks)\n", b / 1e9, dt, b / 1e9 / dt,
                 v->source ? "source reader" : "host pointers", code, chunks.size());
     }

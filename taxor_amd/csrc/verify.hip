@@ -9,6 +9,7 @@
 // right variant scores ~1.0, every other one sits at the 2^-8 false-positive floor.  Not on the search path; a plain kernel
 // (one block per (hash list, variant), a thread per bin).
 #include "../../include/taxor_gpu_tools.h"
+#include "hip_host.h"
 #include "ixf_arith.h"
 #include "ixf_layout.h"
 
@@ -18,8 +19,6 @@
 #include <cstdio>
 #include <string>
 #include <vector>
-
-extern "C" __attribute__((visibility("hidden"))) void taxor_set_last_error(const char *msg);
 
 namespace {
 
@@ -65,28 +64,22 @@ __global__ __launch_bounds__(256) void k_variant_scan(const uint8_t *__restrict_
     if (threadIdx.x == 0) best_ratio[(size_t)vi * n_lists + list] = n ? (float)sBest / (float)n : 0.f;
 }
 
-int vfail(int code, const std::string &msg)
-{
-    taxor_set_last_error(msg.c_str());
-    return code;
-}
-
 } // namespace
 
 extern "C" int taxor_gpu_ixf_variant_scan(int device, const uint8_t *raw, uint64_t raw_len, uint64_t bins, const taxor_ixf_variant *variants, uint32_t n_variants,
                                           const uint64_t *hashes, const uint64_t *hash_off, uint64_t n_lists, float *best_ratio)
 {
     if (!raw || !raw_len || !bins || !variants || !n_variants || !hashes || !hash_off || !n_lists || !best_ratio)
-        return vfail(TAXOR_E_ARG, "ixf_variant_scan: null or empty argument");
+        return fail(TAXOR_E_ARG, "ixf_variant_scan: null or empty argument");
     for (uint32_t i = 0; i < n_variants; ++i)
         if (variants[i].seg_len == 0 || variants[i].stride == 0 || !ixf_layout_valid(variants[i].layout))
-            return vfail(TAXOR_E_ARG, "ixf_variant_scan: variant with zero segment length or stride, or an unknown layout");
+            return fail(TAXOR_E_ARG, "ixf_variant_scan: variant with zero segment length or stride, or an unknown layout");
     // the kernel's "does this shape fit the raw bytes" test multiplies rows by the pitch in 64 bits: bound both here so that it cannot wrap
     // (an index cannot hold more than 2^32 rows or rows wider than 2^20 bytes either, api.hip index_create)
     for (uint32_t i = 0; i < n_variants; ++i)
         if (variants[i].seg_len > (1ull << 31) || variants[i].stride > (1ull << 20))
-            return vfail(TAXOR_E_ARG, "ixf_variant_scan: variant " + std::to_string(i) + " with a segment length above 2^31 or a pitch above 2^20");
-    if (n_lists > 65535 || n_variants > 65535 || bins >= (1ull << 32)) return vfail(TAXOR_E_ARG, "ixf_variant_scan: more than 65535 lists or variants");
+            return fail(TAXOR_E_ARG, "ixf_variant_scan: variant " + std::to_string(i) + " with a segment length above 2^31 or a pitch above 2^20");
+    if (n_lists > 65535 || n_variants > 65535 || bins >= (1ull << 32)) return fail(TAXOR_E_ARG, "ixf_variant_scan: more than 65535 lists or variants");
     const uint64_t nh = hash_off[n_lists];
     uint8_t *d_raw = nullptr;
     taxor_ixf_variant *d_v = nullptr;
@@ -114,7 +107,7 @@ extern "C" int taxor_gpu_ixf_variant_scan(int device, const uint8_t *raw, uint64
     (void)hipFree(d_h);
     (void)hipFree(d_off);
     (void)hipFree(d_out);
-    if (e != hipSuccess) return vfail(TAXOR_E_HIP, std::string("ixf_variant_scan: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(TAXOR_E_HIP, std::string("ixf_variant_scan: ") + hipGetErrorString(e));
     return TAXOR_OK;
 }
 
