@@ -416,6 +416,25 @@ int taxor_gpu_profile_feed_finish(taxor_gpu_profile_feed *f, const uint64_t *ran
 int taxor_gpu_profile_feed_matches(const taxor_gpu_profile_feed *f, taxor_profile_csr *csr, const int64_t **user_bin);
 void taxor_gpu_profile_feed_destroy(taxor_gpu_profile_feed *f);
 
+/* ---- search straight from file bytes (taxor_amd/csrc/fastx_scan.hip): raw[0, n_bytes) holds whole records of one
+ * kind, '>' (FASTA) or '@' (four-line FASTQ) -- what a reader cuts at record boundaries.  The device finds the records, packs their
+ * sequences into the searcher's batch and runs the search; taxor_gpu_search_batch_end follows as after any _begin.  raw may be pageable
+ * or registered with taxor_gpu_host_register, and is free again when the call returns.  The table's pointers stay valid until the next
+ * call on the searcher.  An id is the header line without its first character and without the line terminator.
+ * status TAXOR_FASTX_IRREGULAR (the call returns TAXOR_OK): the bytes are not plain records of that kind -- a blank line between FASTQ
+ * records, a wrapped FASTQ sequence, a quality line of another length, a first non-blank byte that is not the record character.  Nothing
+ * was enqueued and the table is empty: parse the bytes on the host.  A byte outside dna15 in a sequence is TAXOR_E_ALPHABET.  The reads go
+ * through the batch pipeline as one resident batch (sub_batch_reads / sub_batch_bases and the threshold models apply as for any batch; the
+ * lanes for small calls are not used: the bytes are on the device already).  n_bytes >= 2^40 is TAXOR_E_ARG. */
+#define TAXOR_FASTX_IRREGULAR 1u
+typedef struct {
+    uint64_t n_reads;
+    const uint64_t *id_off, *id_len;   /* [n_reads], byte positions inside raw */
+    const uint64_t *read_len;          /* [n_reads] */
+    uint32_t status;                   /* 0, or TAXOR_FASTX_IRREGULAR: nothing was enqueued, parse on the host */
+} taxor_fastx_scan;
+int taxor_gpu_search_fastx_begin(taxor_gpu_searcher *s, const char *raw, uint64_t n_bytes, int kind, taxor_fastx_scan *scan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,14 @@ PROFILE_TRACE = 1
 FEED_KEEP_ALL = 1
 
 
+class FastxScan(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("id_off", C.POINTER(C.c_uint64)), ("id_len", C.POINTER(C.c_uint64)),
+                ("read_len", C.POINTER(C.c_uint64)), ("status", C.c_uint32)]
+
+
+FASTX_IRREGULAR = 1
+
+
 SIGNATURES = {
     "taxor_gpu_last_error": (C.c_char_p, []),
     "taxor_gpu_index_create": (C.c_int, [C.POINTER(HixfView), C.c_int, C.POINTER(_P)]),
@@ -208,6 +216,7 @@ SIGNATURES = {
     "taxor_gpu_host_unregister": (C.c_int, [_P]),
     "taxor_gpu_search_batch_begin": (C.c_int, [_P, _P, _P, C.c_uint64]),
     "taxor_gpu_search_segments_begin": (C.c_int, [_P, C.POINTER(ReadSegment), C.c_uint64]),
+    "taxor_gpu_search_fastx_begin": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(FastxScan)]),
     "taxor_gpu_search_batch_end": (C.c_int, [_P, C.POINTER(Results)]),
     "taxor_gpu_search_batch": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(Results)]),
     "taxor_gpu_batch_upload": (C.c_int, [_P, _P, _P, C.c_uint64]),

@@ -2,6 +2,7 @@
 // the batch pipeline (upload -> syncmers -> level-synchronous HIXF query -> DFS-ordered CSR) and the stage
 // entry points the parity tests use.  No CPU fallback exists: every compute entry point runs HIP kernels.
 #include "../../include/taxor_gpu_tools.h"
+#include "fastx_scan.h"
 #include "hip_host.h"
 #include "ixf_arith.h"
 #include "ixf_layout.h"
@@ -121,6 +122,8 @@ struct taxor_gpu_searcher {
     uint64_t max_slots = 0, max_read_slots = 0;
     uint32_t max_sub_reads = 0;
     uint64_t packed_word_count = 0, packed_in_bytes = 0;
+    FastxScan *fx = nullptr;                // record scanner of taxor_gpu_search_fastx_begin (fastx_scan.hip), made at first use
+    std::vector<uint64_t> fx_off;           // ... and the read offsets it implies
 
     // per-sub-batch scratch
     DeviceBuf<uint64_t> d_cand[2], d_hashes[2];   // double-buffered across sub-batches
@@ -937,6 +940,7 @@ extern "C" void taxor_gpu_searcher_destroy(taxor_gpu_searcher *s)
     s->d_ascii.release(); s->d_aoff.release(); s->d_poff.release(); s->d_hoff.release();
     s->d_packed.release(); s->d_rlen.release(); s->d_hcap.release(); s->d_nh.release(); s->d_thr.release();
     s->d_order.release();
+    if (s->fx) fastx_scan_destroy(s->fx);
     for (int b = 0; b < 2; ++b) { s->d_cand[b].release(); s->d_hashes[b].release(); }
     s->d_sync_cursor.release();
     for (auto ev : s->ev_sync_done) (void)hipEventDestroy(ev);
@@ -2370,6 +2374,42 @@ extern "C" int taxor_gpu_search_segments_begin(taxor_gpu_searcher *s, const taxo
     if (int rc = prepare_batch(s, &nothing, off.data(), n_reads, true)) return rc;
     s->host_spans = std::move(spans);
     return run_pipeline(s, n_reads != 0);
+}
+
+// The raw bytes take the place of the ASCII bases in d_ascii; the scanner (fastx_scan.hip) finds the records, the host lays the
+// batch out from their lengths exactly as for any other batch (prepare_batch), the scanner packs from the raw bytes, and the
+// pipeline runs on a resident batch.
+extern "C" int taxor_gpu_search_fastx_begin(taxor_gpu_searcher *s, const char *raw, uint64_t n_bytes, int kind, taxor_fastx_scan *scan)
+{
+    if (!s || !scan || (n_bytes && !raw)) return fail(TAXOR_E_ARG, "search_fastx_begin: null argument");
+    *scan = taxor_fastx_scan{0, nullptr, nullptr, nullptr, 0};
+    HIP_TRY(hipSetDevice(s->idx->device));
+    if (!s->fx) s->fx = fastx_scan_create();
+    if (reserve(s->d_ascii, n_bytes + 64)) return TAXOR_E_HIP;
+    if (n_bytes) HIP_TRY(hipMemcpyAsync(s->d_ascii.p, raw, n_bytes, hipMemcpyHostToDevice, s->st));
+    FastxTable t{};
+    if (int rc = fastx_scan_records(s->fx, s->d_ascii.p, n_bytes, kind, n_bytes ? (uint8_t)raw[n_bytes - 1] : (uint8_t)'\n', s->st, &t)) return rc;
+    if (t.status) {
+        scan->status = t.status;
+        return TAXOR_OK;
+    }
+    std::vector<uint64_t> &off = s->fx_off;
+    off.resize(t.n_reads + 1);
+    off[0] = 0;
+    for (uint64_t r = 0; r < t.n_reads; ++r) off[r + 1] = off[r] + t.read_len[r];
+    static const char nothing = 0;
+    s->small_active = false;
+    if (int rc = prepare_batch(s, &nothing, off.data(), t.n_reads, false)) return rc;     // d_ascii holds n_bytes >= the bases: it stays
+    if (int rc = fastx_scan_pack(s->fx, s->d_ascii.p, s->d_poff.p, s->d_rlen.p, s->d_packed.p, t.n_reads, s->d_ctr, s->st)) return rc;
+    bool rerun;
+    if (int rc = check_flags(s, &rerun)) return rc;     // synchronises; reports a non-dna15 character (run_pipeline clears the flags)
+    s->host_spans.clear();
+    if (int rc = run_pipeline(s, false)) return rc;
+    scan->n_reads = t.n_reads;
+    scan->id_off = t.id_off;
+    scan->id_len = t.id_len;
+    scan->read_len = t.read_len;
+    return TAXOR_OK;
 }
 
 extern "C" int taxor_gpu_search_batch_end(taxor_gpu_searcher *s, taxor_gpu_results *out) { return taxor_gpu_batch_fetch(s, out); }

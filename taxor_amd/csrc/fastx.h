@@ -141,6 +141,11 @@ struct Batch {
     uint64_t pool_bytes = 0;    // what the CLI's buffer pool has on its books for this batch (search_main.cpp, BatchPool)
     uint32_t fills = 0;         // how often this buffer has been filled by a parser: it is page-locked when it comes round again
     uint64_t feed_first = 0;    // search-to-profile in one run: the index its first read was given in the profile feed
+    // --device-parse: the chunk is a byte range of the file as read (whole records of kind raw_kind, '>' or '@'); the device finds
+    // the records, ids and offsets are filled from its table and bases stays empty.  raw_kind 0: a parsed chunk, as above
+    BaseBuf raw;
+    char raw_kind = 0;
+    void *raw_pinned = nullptr; // raw.data() as page-locked by the range thread that filled it (search_main.cpp); recycled with the chunk
 };
 
 // ---- bzip2 input (seqan3's sequence_file_input reads .bz2 when built with bzip2, which the reference's CMake fetches).

@@ -114,6 +114,14 @@ private:
 // each, so that the pipeline can never starve itself -- a new buffer is made only while the bytes of the existing ones stay
 // within `byte_budget`, and a buffer that comes back while the pool is over budget is released (unregistered and freed)
 // instead of kept.
+// a chunk's page-locked buffers back to pageable memory: before they are freed (a registration over freed memory would be a DMA
+// source the allocator hands out again) -- the pool's trim and the teardown between two index files both come through here
+inline void unpin_buffers(Batch &b)
+{
+    if (b.pinned) { taxor_gpu_host_unregister(b.pinned); b.pinned = nullptr; }
+    if (b.raw_pinned) { taxor_gpu_host_unregister(b.raw_pinned); b.raw_pinned = nullptr; }
+}
+
 struct BatchPool {
     std::mutex mu;
     std::condition_variable cv;
@@ -133,7 +141,7 @@ struct BatchPool {
     void put(std::unique_ptr<Batch> b)
     {
         std::unique_lock<std::mutex> lk(mu);
-        const uint64_t now_bytes = b->bases.capacity();
+        const uint64_t now_bytes = b->bases.capacity() + b->raw.capacity();
         bytes += now_bytes - b->pool_bytes;
         b->pool_bytes = now_bytes;
         peak_bytes = std::max(peak_bytes, bytes);
@@ -142,7 +150,7 @@ struct BatchPool {
             --made;
             ++trimmed;
             lk.unlock();
-            if (b->pinned) { taxor_gpu_host_unregister(b->pinned); b->pinned = nullptr; }
+            unpin_buffers(*b);
             b.reset();
             cv.notify_one();
             return;
@@ -161,6 +169,7 @@ struct Config {                              // taxor_search_configuration.hpp:8
                                                            // file per batch (plain file, parsed in parallel)
     std::string expect_file;    // --expect: a TSV the reference wrote for the same reads and index, compared per read
     bool sequential = false;    // --sequential: one reader thread per file, no byte-range cutting (any legal FASTA/FASTQ)
+    bool device_parse = false;  // --device-parse: byte ranges of plain files go to the device as read; it finds the records
     uint32_t ixf_arith = 0;     // --ixf-arithmetic: the reading of the un-vendored IXF arithmetic the index follows (0 = this library's)
     bool layout_given = false;  // --ixf-layout: how the file stores each IXF's fingerprints (ixf_layout.h); transposed on the device at load
     uint32_t ixf_layout = 0;
@@ -213,6 +222,9 @@ void usage()
             "                           RCCL/xGMI (default), the same staged through host memory, or independent workers\n"
             "  --batch-reads <n>        reads per parsed chunk (default: about 128 MB of query file, 65536 reads for gzip)\n"
             "  --sequential             read every query file front to back on one thread (FASTQ whose records wrap their lines)\n"
+            "  --device-parse           plain FASTA / four-line FASTQ: the byte ranges go to the device as they are read and the records are\n"
+            "                           found there (the host parses a range only where the device reports it irregular); compressed\n"
+            "                           and --sequential input is parsed on the host as without the switch\n"
             "  --group-reads <n>        reads per GPU batch, made of whole chunks (default 131072; --batch-reads if that is given)\n"
             "  --ixf-arithmetic <spec>  search an index whose fingerprints follow another reading of the IXF arithmetic than this\n"
             "                           build's (the spec `taxor verify --variants` prints: kh=..,sm=..,rot=..,red=..,fp=..)\n"
@@ -341,6 +353,32 @@ double produce_batches(const std::string &query, const Config &cfg, bool allow_r
                         bt->seq = seq;
                         bt->may_pin = true;
                         ++bt->fills;
+                        if (cfg.device_parse) {             // the range as it is in the file: the GPU worker hands it to the device's scanner
+                            const size_t len = (size_t)(e - b);
+                            bt->ids.clear();
+                            bt->bases.clear();
+                            bt->offsets.assign(1, 0);
+                            bt->may_pin = false;
+                            // the bytes go to the device from here: the buffer is page-locked once, when it is made or grown, and
+                            // recycled with the chunk like the parsed chunks' sequence buffers (the copy is then DMA, not a staging
+                            // copy on the thread that feeds the GPU)
+                            if (len > bt->raw.capacity()) {
+                                if (bt->raw_pinned) { taxor_gpu_host_unregister(bt->raw_pinned); bt->raw_pinned = nullptr; }
+                                bt->raw.clear();
+                                bt->raw.reserve((len + len / 16 + (2u << 20)) & ~size_t((2u << 20) - 1));
+                            }
+                            bt->raw.clear();
+                            bt->raw.resize(len);
+                            if (!bt->raw_pinned && taxor_gpu_host_register(bt->raw.data(), bt->raw.capacity()) == TAXOR_OK) bt->raw_pinned = bt->raw.data();
+                            for (size_t got = 0; got < len;) {
+                                const ssize_t r = pread(rf.fd, bt->raw.data() + got, len - got, (off_t)(b + got));
+                                if (r <= 0) throw std::runtime_error("query file: read error");
+                                got += (size_t)r;
+                            }
+                            bt->raw_kind = rf.kind;
+                            push(std::move(bt));
+                            continue;
+                        }
                         const size_t need = fastx::bases_bound(e - b, rf.kind);
                         if (need > bt->bases.capacity()) {  // grow before parsing, and only with the old block unpinned
                             if (bt->pinned) { taxor_gpu_host_unregister(bt->pinned); bt->pinned = nullptr; }
@@ -377,6 +415,11 @@ double produce_batches(const std::string &query, const Config &cfg, bool allow_r
         for (auto &t : th) t.join();
         finish();
         return now() - t_begin;
+    }
+    if (cfg.device_parse) {
+        static std::atomic<bool> said{false};
+        if (!said.exchange(true))
+            fprintf(stderr, "--device-parse: %s is compressed or read sequentially: it is parsed on the host\n", query.c_str());
     }
     fastx::FastxReader rd;
     fastx::GzMembers members;
@@ -1254,6 +1297,7 @@ int main(int argc, char **argv)
         else if (k == "--batch-reads") cfg.batch_reads = strtoull(val().c_str(), nullptr, 10);
         else if (k == "--expect") cfg.expect_file = val();
         else if (k == "--sequential") cfg.sequential = true;
+        else if (k == "--device-parse") cfg.device_parse = true;
         else if (k == "--group-reads") cfg.group_reads = strtoull(val().c_str(), nullptr, 10);
         else if (k == "--ixf-arithmetic") {
             const std::string spec = val();
@@ -1666,9 +1710,59 @@ int main(int argc, char **argv)
                 std::lock_guard<std::mutex> lk(stat_mu);
                 ++n_batches;
                 total_reads += n;
-                total_bases += bt->bases.size();
+                total_bases += bt->offsets.back();
             }
             if (r0 != res.n_reads) die("internal: a batch's results do not cover its chunks");
+        };
+        // --device-parse.  A chunk of file bytes is a GPU batch by itself.  scan_begin hands it to the device's scanner: 0 = enqueued on
+        // s, ids and offsets are filled from the scanner's table; 1 = the device reported the bytes irregular (or met a byte outside
+        // dna15, which the parsed path may still repair) and the chunk was parsed here by the reader a range thread would have used
+        // (the same records, the same messages for a malformed file) -- it goes on like any parsed chunk; -1 = err says why
+        std::atomic<uint64_t> n_scanned{0}, n_host_parsed{0}, n_pageable{0};   // n_pageable: chunks whose buffer could not be page-locked
+        auto host_parse = [](Batch &bt) -> std::string {
+            try {
+                fastx::FastxReader rd;
+                std::deque<std::vector<char>> parts;
+                parts.emplace_back(bt.raw.data(), bt.raw.data() + bt.raw.size());
+                rd.open_mem(std::move(parts), bt.raw_kind == '@');
+                bt.ids.clear();
+                bt.bases.clear();
+                bt.bases.reserve(fastx::bases_bound(bt.raw.size(), bt.raw_kind));
+                bt.offsets.assign(1, 0);
+                std::string id;
+                while (rd.next(id, bt.bases)) {
+                    bt.ids.push_back(id);
+                    bt.offsets.push_back(bt.bases.size());
+                }
+            } catch (const std::exception &ex) { return ex.what(); }
+            bt.raw_kind = 0;
+            return std::string();
+        };
+        auto scan_begin = [&](taxor_gpu_searcher *s, Batch &bt, std::string &err) -> int {
+            taxor_fastx_scan sc{};
+            if (!bt.raw_pinned) ++n_pageable;
+            const int rc = taxor_gpu_search_fastx_begin(s, bt.raw.data(), bt.raw.size(), bt.raw_kind, &sc);
+            if (rc != TAXOR_OK && rc != TAXOR_E_ALPHABET) { err = taxor_gpu_last_error(); return -1; }
+            if (rc != TAXOR_OK || sc.status != 0) {
+                err = host_parse(bt);
+                if (!err.empty()) return -1;
+                ++n_host_parsed;
+                return 1;
+            }
+            uint64_t id_bytes = 0;
+            for (uint64_t r = 0; r < sc.n_reads; ++r) id_bytes += sc.id_len[r];
+            bt.ids.clear();
+            bt.ids.reserve(sc.n_reads, id_bytes);
+            bt.offsets.assign(1, 0);
+            bt.offsets.reserve(sc.n_reads + 1);
+            for (uint64_t r = 0; r < sc.n_reads; ++r) {
+                bt.ids.data.append(bt.raw.data() + sc.id_off[r], sc.id_len[r]);
+                bt.ids.off.push_back(bt.ids.data.size());
+                bt.offsets.push_back(bt.offsets.back() + sc.read_len[r]);
+            }
+            bt.raw_kind = 0;
+            ++n_scanned;
+            return 0;
         };
         static const double fill_seconds = [] { const char *e = tune_env("TAXOR_CLI_FILL_MS"); return e ? atof(e) * 1e-3 : 0.020; }();
         // (a third and fourth worker per device that copy their results out and collect the next batch while two "slots" stay taken:
@@ -1689,10 +1783,10 @@ int main(int argc, char **argv)
                 // round run an empty one, so that every searcher has a finished run to gather.
                 std::vector<std::vector<std::unique_ptr<Batch>>> round(ng);
                 std::vector<std::unique_ptr<Batch>> eofs, flat;
-                std::unique_ptr<Batch> b;
+                std::unique_ptr<Batch> b, held;         // held: a chunk of file bytes met while a batch of parsed chunks was being collected
                 const uint64_t zero_off[1] = {0};
                 bool open = true;
-                while (open) {
+                while (open || held) {
                     for (auto &g : round) g.clear();
                     eofs.clear();
                     size_t used = 0;
@@ -1702,14 +1796,18 @@ int main(int argc, char **argv)
                         while ((gr < group_reads || (!cfg.batch_reads && !cfg.group_reads && gb < (1ull << 29) && gr < (1u << 20))) &&
                                gb < (3ull << 30) && round[g].size() < group_max_chunks) {
                             bool got;
-                            if (used == 0 && round[g].empty() && eofs.empty()) { got = q_in.pop(b); if (!got) open = false; }
+                            if (held) { b = std::move(held); got = true; }
+                            else if (used == 0 && round[g].empty() && eofs.empty()) { got = q_in.pop(b); if (!got) open = false; }
                             else got = q_in.try_pop(b);
                             if (!got) break;
                             if (b->end_of_file) { eofs.push_back(std::move(b)); continue; }
+                            if (b->raw_kind && !round[g].empty()) { held = std::move(b); break; }     // file bytes are a batch by themselves
+                            const bool alone = b->raw_kind != 0;
                             gr += b->ids.size();
                             gb += b->bases.size();
                             round[g].push_back(std::move(b));
                             ++used;
+                            if (alone) break;
                         }
                         if (round[g].empty()) break;
                     }
@@ -1727,7 +1825,10 @@ int main(int argc, char **argv)
                                 return;
                             }
                             std::vector<taxor_read_segment> segs;
+                            const bool scanned = round[g][0]->raw_kind && scan_begin(mine[g], *round[g][0], errs[g]) == 0;
+                            if (!errs[g].empty()) return;
                             auto run = [&]() -> int {
+                                if (scanned) return taxor_gpu_batch_sync(mine[g]);
                                 segs.clear();
                                 for (auto &bt : round[g]) segs.push_back({bt->bases.data(), bt->offsets.data(), bt->ids.size()});
                                 const int rc = taxor_gpu_search_segments_begin(mine[g], segs.data(), segs.size());
@@ -1773,19 +1874,22 @@ int main(int argc, char **argv)
                 workers.emplace_back([&, wi] {
                     std::vector<std::unique_ptr<Batch>> group, eofs;
                     std::vector<taxor_read_segment> segs;
-                    std::unique_ptr<Batch> b;
-                    while (q_in.pop(b)) {
+                    std::unique_ptr<Batch> b, held;     // held: a chunk of file bytes met while a batch of parsed chunks was being collected
+                    for (;;) {
+                        if (held) b = std::move(held);
+                        else if (!q_in.pop(b)) break;
                         if (b->end_of_file) { q_fmt.push(std::move(b)); continue; }
                         // one GPU batch = the queued chunks that make up ~group_reads reads: the kernels want >= 10^5 reads in
                         // flight, the parsers want chunks small enough to hand out to many threads
                         group.clear();
                         eofs.clear();
+                        const bool raw = b->raw_kind != 0;      // file bytes: a batch by themselves
                         uint64_t gr = b->ids.size(), gb = b->bases.size();
                         group.push_back(std::move(b));
                         // (short reads: more of them, until the batch holds 2^29 bases -- the library's sub-batches then reach
                         // their full size)
                         const double t_fill0 = now();
-                        while ((gr < group_reads || (!cfg.batch_reads && !cfg.group_reads && gb < (1ull << 29) && gr < (1u << 20))) &&
+                        while (!raw && (gr < group_reads || (!cfg.batch_reads && !cfg.group_reads && gb < (1ull << 29) && gr < (1u << 20))) &&
                                gb < (3ull << 30) && group.size() < group_max_chunks) {
                             if (!q_in.try_pop(b)) {
                                 // nothing queued: the GPU is the faster side right now.  Launching what there is makes the batches
@@ -1796,6 +1900,7 @@ int main(int argc, char **argv)
                                 if (!q_in.pop_for(b, 100e-6)) { if (q_in.done()) break; continue; }
                             }
                             if (b->end_of_file) { eofs.push_back(std::move(b)); continue; }
+                            if (b->raw_kind) { held = std::move(b); break; }
                             gr += b->ids.size();
                             gb += b->bases.size();
                             group.push_back(std::move(b));
@@ -1805,11 +1910,19 @@ int main(int argc, char **argv)
                         for (auto &bt : group) pin(*bt);
                         const double t2 = now();
                         taxor_gpu_results res{};
+                        bool scanned = false;
+                        if (raw) {
+                            std::string err;
+                            scanned = scan_begin(sr[wi], *group[0], err) == 0;
+                            if (!err.empty()) die(err);
+                        }
                         auto run = [&]() -> int {
-                            segs.clear();
-                            for (auto &bt : group) segs.push_back({bt->bases.data(), bt->offsets.data(), bt->ids.size()});
-                            const int rc = taxor_gpu_search_segments_begin(sr[wi], segs.data(), segs.size());
-                            if (rc != TAXOR_OK) return rc;
+                            if (!scanned) {
+                                segs.clear();
+                                for (auto &bt : group) segs.push_back({bt->bases.data(), bt->offsets.data(), bt->ids.size()});
+                                const int rc = taxor_gpu_search_segments_begin(sr[wi], segs.data(), segs.size());
+                                if (rc != TAXOR_OK) return rc;
+                            }
                             // without a TSV nothing on the host reads the tuples: they stay on the device for the profile feed
                             return write_tsv ? taxor_gpu_search_batch_end(sr[wi], &res) : taxor_gpu_batch_sync(sr[wi]);
                         };
@@ -1839,7 +1952,7 @@ int main(int argc, char **argv)
                         if (write_tsv) split_results(group, res);
                         else {
                             std::lock_guard<std::mutex> lk(stat_mu);
-                            for (auto &bt : group) { ++n_batches; total_reads += bt->ids.size(); total_bases += bt->bases.size(); }
+                            for (auto &bt : group) { ++n_batches; total_reads += bt->ids.size(); total_bases += bt->offsets.back(); }
                         }
                         {
                             std::lock_guard<std::mutex> lk(stat_mu);
@@ -1854,6 +1967,9 @@ int main(int argc, char **argv)
                 });
         for (auto &t : workers) t.join();
         trace("GPU workers done");
+        if (cfg.device_parse && tune_env("TAXOR_CLI_TRACE"))
+            fprintf(stderr, "[trace] --device-parse: %llu ranges scanned on the device, %llu parsed on the host; %llu copied from pageable memory\n",
+                    (unsigned long long)n_scanned.load(), (unsigned long long)n_host_parsed.load(), (unsigned long long)n_pageable.load());
         t_search_wall += now() - t_search0;
         if (tune_env("TAXOR_CLI_TRACE")) {
             const CpuMark c1 = cpu_mark();
@@ -1895,8 +2011,7 @@ int main(int argc, char **argv)
             // would only delay the exit (~0.1 s per GB)
             for (auto &b : pool.free_) (void)b.release();
         } else {
-            for (auto &b : pool.free_)
-                if (b->pinned) taxor_gpu_host_unregister(b->pinned);
+            for (auto &b : pool.free_) unpin_buffers(*b);
         }
         pool.free_.clear();
         if (tune_env("TAXOR_CLI_TRACE"))

@@ -66,6 +66,15 @@ class SearchResults:
         return [(int(a), int(b)) for a, b in zip(self.user_bin[lo:hi], self.count[lo:hi])]
 
 
+@dataclass
+class FastxResults:
+    """search_fastx: status 0 and the reads' results, ids and lengths -- or status FASTX_IRREGULAR and nothing else"""
+    status: int
+    results: SearchResults = None
+    ids: list = None            # bytes per read: the header line without its first character and its terminator
+    read_len: np.ndarray = None  # uint64[n_reads]
+
+
 def _results(res: _lib.Results, copy=True) -> SearchResults:
     """copy=False: views of the library's own result arrays, valid until the next call on that searcher (the C ABI's
     convention; what a C++ host sees) -- for callers that time the library and not numpy's memcpy of 100 MB of tuples"""
@@ -333,6 +342,23 @@ class Searcher:
         res = _lib.Results()
         check(_lib.lib().taxor_gpu_search_batch_end(self._h, C.byref(res)))
         return _results(res)
+
+    def search_fastx(self, raw: bytes, kind) -> FastxResults:
+        """one batch straight from file bytes: whole records of one kind, '>' (FASTA) or '@' (four-line FASTQ); the device
+        finds the records (taxor_gpu_search_fastx_begin)"""
+        buf = np.frombuffer(bytes(raw), dtype=np.uint8)
+        k = kind if isinstance(kind, int) else ord(kind)
+        sc = _lib.FastxScan()
+        check(_lib.lib().taxor_gpu_search_fastx_begin(self._h, _p(buf) if buf.size else None, buf.size, k, C.byref(sc)))
+        if sc.status:
+            return FastxResults(int(sc.status))
+        n = int(sc.n_reads)
+        arr = lambda p: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+        id_off, id_len, read_len = arr(sc.id_off), arr(sc.id_len), arr(sc.read_len)
+        res = _lib.Results()
+        check(_lib.lib().taxor_gpu_search_batch_end(self._h, C.byref(res)))
+        ids = [buf[int(a):int(a + l)].tobytes() for a, l in zip(id_off, id_len)]
+        return FastxResults(0, _results(res), ids, read_len)
 
     def search_batch_end(self) -> SearchResults:
         res = _lib.Results()
