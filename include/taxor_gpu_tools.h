@@ -83,6 +83,14 @@ typedef struct taxor_build_stats {
     double seconds_upload;    /* keys from host memory to the device (allocation + copy; 0 when they were there already); in seconds_total */
     double seconds_alloc;     /* hipMalloc / hipFree of the peeling scratch (in seconds_total; the driver's time, erratic for GB-sized blocks) */
     uint64_t keys_counted_in_lds; /* of keys_inserted: keys whose bin's degree words were built in LDS (no global atomic adds for them) */
+    /* taxor_gpu_index_build_hixf_stream only (0 after any other build) */
+    uint32_t stream_groups;   /* groups of IXFs whose keys were uploaded and built together */
+    uint32_t stream_ranges;   /* bin ranges of an IXF larger than the budget (the last attempt's) */
+    uint32_t stream_restarts; /* attempts of such an IXF thrown away because a bin did not peel under the seed */
+    uint32_t reserved2;
+    uint64_t stream_bytes_uploaded;       /* key bytes sent to the device, thrown-away attempts and unions read again included */
+    double seconds_stream_upload;         /* ranged path: time the uploads of the bin ranges took (on their own thread and stream) */
+    double seconds_stream_upload_wait;    /* of it: time the peeling waited for an upload (the rest was hidden behind peeling) */
 } taxor_build_stats;
 int taxor_gpu_index_build_ixf_ex(taxor_gpu_index *idx, uint64_t ixf, const uint64_t *keys, int keys_on_device,
                                  const uint64_t *key_off, uint64_t seed0, uint64_t *seed_out, taxor_build_stats *stats);
@@ -96,6 +104,37 @@ int taxor_gpu_index_build_hixf_ex(taxor_gpu_index *idx, const uint64_t *keys, in
 int taxor_gpu_index_build_hixf_gen(taxor_gpu_index *idx, const uint64_t *keys, int keys_on_device, const uint64_t *key_off,
                                    const uint64_t *gen_first, const uint64_t *gen_count, uint64_t gen_salt, uint64_t seed0,
                                    taxor_build_stats *stats);
+/* ---- construction with the keys in HOST memory and a bounded part of them on the device ("Beyond device
+ * memory").  The columns of an IXF are a function of its bins' key SETS and its seed alone, so what these build is byte-identical
+ * to taxor_gpu_index_build_hixf on the same keys and seed0, whatever the budget.
+ * taxor_gpu_keys_union: the duplicate-free union of n_lists key lists (host memory, or device memory with lists_on_device; the
+ * lists need not be sorted nor free of duplicates themselves), with KeyUnion's device set (keyset.hip: its slot rule, and the
+ * empty marker 2^64 - 1 kept aside and counted once).  *n_out = the union's exact size; with `out` != NULL the union itself, sorted
+ * ascending, goes to out[0, *n_out) (device memory with out_on_device) -- TAXOR_E_ARG when out_cap is smaller. */
+int taxor_gpu_keys_union(int device, const uint64_t *const *lists, const uint64_t *counts, uint64_t n_lists, int lists_on_device,
+                         uint64_t *out, int out_on_device, uint64_t out_cap, uint64_t *n_out);
+/* Bins [bin0, bin1) of one IXF under the seed GIVEN: no reseeding in here.  key_off[bins + 1] indexes `keys` for the IXF's bins
+ * (only the entries bin0 .. bin1 are read); *ok = 1 when every bin of the range peeled and its columns are written, 0 when one did
+ * not (nothing of this call is written then: the caller starts the IXF again from bin 0 under another seed).  flags:
+ * TAXOR_BINS_CLEAR the whole IXF is set to 0 first (the first call of an attempt at an IXF all of whose bins have keys);
+ * TAXOR_BINS_CLEARED it was, earlier in this attempt; neither: the range's columns are cleared one by one and bins without keys
+ * keep their content.  A bin of 2^32 - 1 keys or more is TAXOR_E_ARG before anything is read.  On ok the index carries `seed`. */
+#define TAXOR_BINS_CLEAR 1u
+#define TAXOR_BINS_CLEARED 2u
+int taxor_gpu_index_build_ixf_bins(taxor_gpu_index *idx, uint64_t ixf, uint64_t bin0, uint64_t bin1, const uint64_t *keys,
+                                   int keys_on_device, const uint64_t *key_off, uint64_t seed, uint32_t flags, int *ok);
+/* The whole hierarchy like taxor_gpu_index_build_hixf, with at most budget_bytes of keys on the device at a time: the IXFs of a
+ * level in groups whose leaf keys and child unions fit the budget, every IXF's union written back to host memory for the level
+ * above; an IXF whose own keys exceed the budget -- the root of a large index -- in bin ranges that fit, range r + 1 uploading into
+ * a second buffer of the same size while range r peels, and from bin 0 again under the next seed when a bin does not peel (32
+ * attempts).  TAXOR_E_ARG, naming it, for a child IXF whose keys alone exceed the budget and for a bin that does.  The peeling
+ * scratch and the union table are the builder's own, beside the budget.
+ * _ranges is the same with bin g's keys at host_keys[key_first[g], key_first[g] + key_count[g]): bins may lie in any order
+ * (a build front end's store holds them in user bin order, the index wants them in its own). */
+int taxor_gpu_index_build_hixf_stream(taxor_gpu_index *idx, const uint64_t *host_keys, const uint64_t *key_off, uint64_t seed0,
+                                      uint64_t budget_bytes, taxor_build_stats *stats);
+int taxor_gpu_index_build_hixf_stream_ranges(taxor_gpu_index *idx, const uint64_t *host_keys, const uint64_t *key_first,
+                                             const uint64_t *key_count, uint64_t seed0, uint64_t budget_bytes, taxor_build_stats *stats);
 /* Synthetic key sets for the build bench and tests: key i = a bijection of (i + salt) (distinct without a table);
  * taxor_gpu_synth_keys writes keys first .. first + n - 1 to the DEVICE array d_out, taxor_synth_key is the same
  * function on the host.  taxor_gpu_malloc / _free / _memcpy_to_host / _from_host: plain device memory for such arrays. */

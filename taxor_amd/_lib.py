@@ -111,7 +111,9 @@ class BuildStats(C.Structure):
                 ("chunks", C.c_uint32), ("reserved", C.c_uint32), ("seconds_peel", C.c_double), ("seconds_assign", C.c_double),
                 ("seconds_union", C.c_double), ("seconds_total", C.c_double), ("seconds_release", C.c_double),
                 ("seconds_count", C.c_double), ("seconds_rounds", C.c_double), ("seconds_upload", C.c_double),
-                ("seconds_alloc", C.c_double), ("keys_counted_in_lds", C.c_uint64)]
+                ("seconds_alloc", C.c_double), ("keys_counted_in_lds", C.c_uint64),
+                ("stream_groups", C.c_uint32), ("stream_ranges", C.c_uint32), ("stream_restarts", C.c_uint32), ("reserved2", C.c_uint32),
+                ("stream_bytes_uploaded", C.c_uint64), ("seconds_stream_upload", C.c_double), ("seconds_stream_upload_wait", C.c_double)]
 
 
 class KeyerParams(C.Structure):
@@ -148,6 +150,7 @@ class ProfileResults(C.Structure):
                 ("iter_ref_nts", C.POINTER(C.c_uint64)), ("seconds_filter", C.c_double), ("seconds_em", C.c_double)]
 
 
+BINS_CLEAR, BINS_CLEARED = 1, 2
 PROFILE_TRACE = 1
 FEED_KEEP_ALL = 1
 
@@ -168,6 +171,10 @@ SIGNATURES = {
     "taxor_gpu_index_build_ixf_ex": (C.c_int, [_P, C.c_uint64, _P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(BuildStats)]),
     "taxor_gpu_index_build_hixf_ex": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, C.POINTER(BuildStats)]),
     "taxor_gpu_index_build_hixf_gen": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(BuildStats)]),
+    "taxor_gpu_keys_union": (C.c_int, [C.c_int, _P, _P, C.c_uint64, C.c_int, _P, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "taxor_gpu_index_build_ixf_bins": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, _P, C.c_int, _P, C.c_uint64, C.c_uint32, C.POINTER(C.c_int)]),
+    "taxor_gpu_index_build_hixf_stream": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(BuildStats)]),
+    "taxor_gpu_index_build_hixf_stream_ranges": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint64, C.POINTER(BuildStats)]),
     "taxor_gpu_keyer_create": (C.c_int, [C.c_int, C.POINTER(KeyerParams), C.POINTER(_P)]),
     "taxor_gpu_keyer_add": (C.c_int, [_P, _P, _P, _P, C.c_uint64]),
     "taxor_gpu_keyer_finish": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint64))]),

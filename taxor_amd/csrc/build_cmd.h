@@ -7,6 +7,9 @@
 //   layout                                                 -- taxor_build_layout over the exact counts (DESIGN.md "taxor build")
 //   geometry, construction, store                          -- exact merged-bin unions, taxor_gpu_index_build_hixf_ex with the keys
 //                                                            on the device, taxor_hixf_store
+//   keys beyond device memory                              -- the genomes are keyed in waves into a host store (key_store.h) and the index is
+//                                                            constructed with a bounded part of the keys on the device
+//                                                            (taxor_gpu_index_build_hixf_stream_ranges)
 // Errors print "[TAXOR BUILD ERROR] ..." and return -1 like the reference (:560-564,585-589).
 
 struct BuildConfig {
@@ -16,7 +19,19 @@ struct BuildConfig {
     bool use_syncmer = false, verbose = false, debug = false;
     int device = 0;
     uint64_t tmax = 0;            // hidden: force one t_max (0 = choose, taxor_build.cpp:168-233)
+    uint64_t key_budget_mib = 0;  // hidden: MiB of distinct keys on the device at a time (0 = an eighth of the free device memory)
+    uint64_t host_memory_mib = 0; // hidden: the host memory the key store is held against (0 = MemAvailable)
 };
+
+const char *const BUILD_ADVANCED_HELP =
+    "taxor build - advanced options\n"
+    "    --tmax <n>                  force one t_max, the largest number of bins of an IXF, in [2,1048576] (default: chosen from the\n"
+    "                                candidates 64 .. 4096 and the square root of the number of genomes)\n"
+    "    --device-key-budget <MiB>   at most this many MiB of distinct keys (8 bytes each) on the device at a time, in [1,16777216].\n"
+    "                                Genomes whose keys may exceed it are keyed in waves into host memory and the index is built\n"
+    "                                from there, byte-identical to a build with every key resident (default: such a build is chosen\n"
+    "                                when the keys may not fit the free device memory, with an eighth of it as the budget)\n"
+    "    --host-memory-mib <MiB>     host memory the key store of such a build may take, in [1,1073741824] (default: MemAvailable)\n";
 
 struct BuildSpecies {
     std::string accession, taxid, organism, taxnames, taxids, file_stem, path;
@@ -123,11 +138,13 @@ int build_command(int argc, char **argv)
         const std::string &o = args[i];
         std::string err;
         const bool has_v = i + 1 < args.size();
-        if (o == "--use-syncmer") c.use_syncmer = true;
+        if (o == "--advanced-help" || o == "-hh") { fputs(BUILD_ADVANCED_HELP, stdout); return 0; }
+        else if (o == "--use-syncmer") c.use_syncmer = true;
         else if (o == "--output-verbose-statistics") c.verbose = true;
         else if (o == "--debug") c.debug = true;
         else if (o == "--input-file" || o == "--input-sequence-dir" || o == "--output-filename" || o == "--kmer-size" || o == "--syncmer-size" ||
-                 o == "--window-size" || o == "--scaling" || o == "--threads" || o == "--gpu" || o == "--tmax") {
+                 o == "--window-size" || o == "--scaling" || o == "--threads" || o == "--gpu" || o == "--tmax" || o == "--device-key-budget" ||
+                 o == "--host-memory-mib") {
             if (!has_v) return build_error("Missing value for option " + o);
             const std::string v = args[++i];
             long tmp = 0;
@@ -141,6 +158,8 @@ int build_command(int argc, char **argv)
             else if (o == "--threads" && !number(o, v, 1, 32, &c.threads, err)) return build_error(err);
             else if (o == "--gpu") { if (!number(o, v, 0, 1023, &tmp, err)) return build_error(err); c.device = (int)tmp; }
             else if (o == "--tmax") { if (!number(o, v, 2, 1 << 20, &tmp, err)) return build_error(err); c.tmax = (uint64_t)tmp; }
+            else if (o == "--device-key-budget") { if (!number(o, v, 1, 1 << 24, &tmp, err)) return build_error(err); c.key_budget_mib = (uint64_t)tmp; }
+            else if (o == "--host-memory-mib") { if (!number(o, v, 1, 1 << 30, &tmp, err)) return build_error(err); c.host_memory_mib = (uint64_t)tmp; }
         } else
             return build_error("Unknown option " + o + ". In case this is meant to be a non-option/argument/parameter, please specify the start of "
                                "non-options with '--'. See -h/--help for program information.");
@@ -192,26 +211,40 @@ int build_command(int argc, char **argv)
         std::error_code ec;
         file_bytes += std::filesystem::file_size(sp.path, ec);
     }
-    // ---- scope: every distinct key (8 B) next to the index in device memory.  Up front: the selection's density bound on the
-    //      genome files' bytes (compressed files hold more bases than bytes: x4)
-    {
+    // ---- scope.  Up front: the selection's density bound on the genome files' bytes.  Every distinct key (8 B), its sorted copy and
+    //      the builder's index beside them in device memory: the resident build.  Else, or when the keys may exceed --device-key-budget:
+    //      waves into a host store and a construction that keeps a bounded part of the keys on the device.  The refusals that numbers
+    //      alone decide come before any HIP call.
+    std::vector<uint64_t> key_bound(n);
+    uint64_t bound_total = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        std::error_code ec;
+        const uint64_t b = std::filesystem::file_size(orgs[i].path, ec);
+        const std::string ext = std::filesystem::path(orgs[i].path).extension().string();
+        key_bound[i] = taxor::key_bound_of_file(b, ext == ".gz" || ext == ".bz2", c.use_syncmer, k, s, t);
+        bound_total += key_bound[i];
+    }
+    uint64_t budget_bytes = c.key_budget_mib << 20;
+    bool stream = c.key_budget_mib && bound_total * 8 > budget_bytes;
+    if (!stream) {
         uint64_t fr = 0, tot = 0;
         if (taxor_gpu_device_memory(c.device, &fr, &tot) != TAXOR_OK) return build_error(taxor_gpu_last_error());
-        uint64_t bases_bound = 0;
-        for (const BuildSpecies &sp : orgs) {
-            std::error_code ec;
-            const uint64_t b = std::filesystem::file_size(sp.path, ec);
-            const std::string ext = std::filesystem::path(sp.path).extension().string();
-            bases_bound += (ext == ".gz" || ext == ".bz2") ? 4 * b : b;
+        if ((double)bound_total * 8.0 * 3.0 > (double)fr) {      // keys, their sorted copy and the builder's index beside them
+            stream = true;
+            if (!budget_bytes) budget_bytes = fr / 8;
         }
-        const double per_base = c.use_syncmer ? 1.0 / std::max(1, std::min(t, k - s + 1 - t + 1)) : 1.0;
-        const double need = (double)bases_bound * per_base * 8.0 * 3.0;   // keys, their sorted copy and the builder's index beside them
-        if (need > (double)fr)
-            return build_error("the distinct keys of these genomes may not fit in device memory next to the index (up to " +
-                               std::to_string((uint64_t)(need / 1e9)) + " GB needed, " + std::to_string(fr / 1000000000ull) +
-                               " GB free); builds larger than device memory are not supported");
     }
-    // ---- keys: parser threads read whole genome files, the device keys batches of them
+    std::vector<uint64_t> wave_first{0, n};
+    if (stream) {
+        const int64_t big = taxor::cut_waves(key_bound, budget_bytes / 8, wave_first);
+        if (big >= 0)
+            return build_error("the distinct keys of " + orgs[big].path + " alone (up to " + std::to_string(key_bound[big] * 8 >> 20) +
+                               " MiB) may exceed the device key budget of " + std::to_string(budget_bytes >> 20) + " MiB");
+        const std::string no = taxor::host_store_refusal(bound_total, c.host_memory_mib ? c.host_memory_mib << 20 : taxor::host_memory_available());
+        if (!no.empty()) return build_error(no);
+    }
+    // ---- keys: parser threads read whole genome files, the device keys batches of them.  One wave = the genomes [g0, g1) through a keyer
+    //      of their own, whose bins are numbered from g0
     const double t_key0 = now();
     taxor_keyer_params kp{};
     kp.kmer_size = (uint32_t)k;
@@ -220,66 +253,91 @@ int build_command(int argc, char **argv)
     kp.use_syncmer = c.use_syncmer ? 1 : 0;
     kp.window_size = (uint64_t)c.window_size;
     kp.scaling = (uint32_t)c.scaling;
-    kp.n_bins = n;
-    taxor_gpu_keyer *kr = nullptr;
-    if (taxor_gpu_keyer_create(c.device, &kp, &kr) != TAXOR_OK) return build_error(taxor_gpu_last_error());
-    std::unique_ptr<taxor_gpu_keyer, void (*)(taxor_gpu_keyer *)> kr_guard(kr, taxor_gpu_keyer_destroy);
-    std::atomic<uint64_t> next_file{0};
-    BoundedQueue<std::unique_ptr<GenomeChunk>> ready((size_t)std::max<long>(2, 2 * c.threads));
-    std::vector<std::thread> parsers;
-    std::atomic<int> alive{(int)c.threads};
-    for (long th = 0; th < c.threads; ++th)
-        parsers.emplace_back([&] {
-            for (;;) {
-                const uint64_t i = next_file.fetch_add(1);
-                if (i >= n) break;
-                auto g = std::make_unique<GenomeChunk>();
-                g->bin = (uint32_t)i;
-                try {
-                    fastx::FastxReader rd;
-                    if (!rd.open(orgs[i].path)) g->error = "cannot open " + orgs[i].path;
-                    std::string id;
-                    while (g->error.empty() && rd.next(id, g->bases)) g->off.push_back(g->bases.size());
-                } catch (const std::exception &e) { g->error = orgs[i].path + ": " + e.what(); }
-                ready.push(std::move(g));
-            }
-            if (--alive == 0) ready.close();
-        });
-    const uint64_t batch_bases = (uint64_t)256 << 20;
-    std::string err;
     uint64_t n_bases = 0;
-    {
-        std::string bases;
-        std::vector<uint64_t> off{0};
-        std::vector<uint32_t> bin;
-        auto flush = [&]() {
-            if (bin.empty() || !err.empty()) return;
-            if (taxor_gpu_keyer_add(kr, bases.data(), off.data(), bin.data(), bin.size()) != TAXOR_OK) err = taxor_gpu_last_error();
-            bases.clear();
-            off.assign(1, 0);
-            bin.clear();
-        };
-        std::unique_ptr<GenomeChunk> g;
-        while (ready.pop(g)) {
-            if (!g->error.empty()) { if (err.empty()) err = g->error; continue; }
-            uint64_t len = 0;
-            for (size_t r = 0; r + 1 < g->off.size(); ++r) {
-                bases.append(g->bases, g->off[r], g->off[r + 1] - g->off[r]);
-                off.push_back(bases.size());
-                bin.push_back(g->bin);
-                len += g->off[r + 1] - g->off[r];
+    auto key_wave = [&](uint64_t g0, uint64_t g1, taxor_gpu_keyer *kr) -> std::string {
+        std::atomic<uint64_t> next_file{g0};
+        BoundedQueue<std::unique_ptr<GenomeChunk>> ready((size_t)std::max<long>(2, 2 * c.threads));
+        std::vector<std::thread> parsers;
+        std::atomic<int> alive{(int)c.threads};
+        for (long th = 0; th < c.threads; ++th)
+            parsers.emplace_back([&] {
+                for (;;) {
+                    const uint64_t i = next_file.fetch_add(1);
+                    if (i >= g1) break;
+                    auto g = std::make_unique<GenomeChunk>();
+                    g->bin = (uint32_t)(i - g0);
+                    try {
+                        fastx::FastxReader rd;
+                        if (!rd.open(orgs[i].path)) g->error = "cannot open " + orgs[i].path;
+                        std::string id;
+                        while (g->error.empty() && rd.next(id, g->bases)) g->off.push_back(g->bases.size());
+                    } catch (const std::exception &e) { g->error = orgs[i].path + ": " + e.what(); }
+                    ready.push(std::move(g));
+                }
+                if (--alive == 0) ready.close();
+            });
+        const uint64_t batch_bases = (uint64_t)256 << 20;
+        std::string err;
+        {
+            std::string bases;
+            std::vector<uint64_t> off{0};
+            std::vector<uint32_t> bin;
+            auto flush = [&]() {
+                if (bin.empty() || !err.empty()) return;
+                if (taxor_gpu_keyer_add(kr, bases.data(), off.data(), bin.data(), bin.size()) != TAXOR_OK) err = taxor_gpu_last_error();
+                bases.clear();
+                off.assign(1, 0);
+                bin.clear();
+            };
+            std::unique_ptr<GenomeChunk> g;
+            while (ready.pop(g)) {
+                if (!g->error.empty()) { if (err.empty()) err = g->error; continue; }
+                uint64_t len = 0;
+                for (size_t r = 0; r + 1 < g->off.size(); ++r) {
+                    bases.append(g->bases, g->off[r], g->off[r + 1] - g->off[r]);
+                    off.push_back(bases.size());
+                    bin.push_back(g->bin);
+                    len += g->off[r + 1] - g->off[r];
+                }
+                orgs[g0 + g->bin].seq_len = len;                          // sum of the file's record lengths (:522-526)
+                n_bases += len;
+                g.reset();
+                if (bases.size() >= batch_bases) flush();
             }
-            orgs[g->bin].seq_len = len;                               // sum of the file's record lengths (:522-526)
-            n_bases += len;
-            g.reset();
-            if (bases.size() >= batch_bases) flush();
+            flush();
         }
-        flush();
-    }
-    for (auto &th : parsers) th.join();
-    if (!err.empty()) return build_error(err);
+        for (auto &th : parsers) th.join();
+        return err;
+    };
+    taxor_gpu_keyer *kr = nullptr;
+    std::unique_ptr<taxor_gpu_keyer, void (*)(taxor_gpu_keyer *)> kr_guard(nullptr, taxor_gpu_keyer_destroy);
+    taxor::KeyStore store;
+    taxor_keyer_stats ks{};
     const uint64_t *bin_off = nullptr, *d_keys = nullptr;
-    if (taxor_gpu_keyer_finish(kr, &bin_off, nullptr, &d_keys) != TAXOR_OK) return build_error(taxor_gpu_last_error());
+    const uint64_t n_waves = wave_first.size() - 1;
+    if (stream && !store.reserve(bound_total)) return build_error("no address space for a key store of " + std::to_string(bound_total * 8 >> 20) + " MiB");
+    for (uint64_t w = 0; w < n_waves; ++w) {
+        const uint64_t g0 = wave_first[w], g1 = wave_first[w + 1];
+        kp.n_bins = g1 - g0;
+        if (taxor_gpu_keyer_create(c.device, &kp, &kr) != TAXOR_OK) return build_error(taxor_gpu_last_error());
+        kr_guard.reset(kr);
+        const std::string err = key_wave(g0, g1, kr);
+        if (!err.empty()) return build_error(err);
+        if (!stream) {
+            if (taxor_gpu_keyer_finish(kr, &bin_off, nullptr, &d_keys) != TAXOR_OK) return build_error(taxor_gpu_last_error());
+            break;                                                        // (the resident keyer lives until the index is built)
+        }
+        // the wave's sorted, distinct keys per bin: into the store, and the keyer goes before the next one comes
+        const uint64_t *w_off = nullptr, *w_keys = nullptr;
+        if (taxor_gpu_keyer_finish(kr, &w_off, &w_keys, nullptr) != TAXOR_OK) return build_error(taxor_gpu_last_error());
+        if (!store.append(w_keys, w_off, g1 - g0)) return build_error("the key store is full: the genomes hold more distinct keys than their density bound");
+        taxor_keyer_stats wks{};
+        (void)taxor_gpu_keyer_stats(kr, &wks);
+        ks.seconds_device += wks.seconds_device;
+        kr_guard.reset();
+        kr = nullptr;
+    }
+    if (stream) bin_off = store.bin_off();
     const double t_key1 = now();
     // ---- layout over the exact counts
     std::vector<uint64_t> counts(n);
@@ -302,6 +360,7 @@ int build_command(int argc, char **argv)
     std::vector<taxor_ixf_view> views(n_ixf);
     std::vector<std::vector<int64_t>> nx(n_ixf), fn(n_ixf);
     std::vector<uint64_t> key_off{0}, first, count;
+    std::vector<uint64_t> bin_first_key, bin_key_count;      // per technical bin, where its keys lie in the store (merged bins: none)
     taxor_ixf_schema schema;
     taxor_ixf_schema_default(&schema);
     uint32_t depth = lay->depth;
@@ -312,15 +371,35 @@ int build_command(int argc, char **argv)
             uint64_t sz = 0, f0 = 0;
             if (lay->fname_idx[b] >= 0) {
                 const uint64_t ub = (uint64_t)lay->fname_idx[b], m = counts[ub], p = lay->parts[b], j = lay->part[b];
-                f0 = bin_off[ub] + m * j / p;                           // contiguous parts of the sorted keys
-                sz = bin_off[ub] + m * (j + 1) / p - f0;
+                taxor::key_part_range(bin_off[ub], m, p, j, &f0, &sz);   // contiguous parts of the sorted keys
                 first.push_back(f0);
                 count.push_back(sz);
             } else {
                 const auto &ub = below[lay->next_ixf[b]];
-                if (taxor_gpu_keyer_union_size(kr, ub.data(), ub.size(), &sz) != TAXOR_OK) return build_error(taxor_gpu_last_error());
+                if (!stream) {
+                    if (taxor_gpu_keyer_union_size(kr, ub.data(), ub.size(), &sz) != TAXOR_OK) return build_error(taxor_gpu_last_error());
+                } else {
+                    // no keyer holds these bins any more: their lists go up from the store.  (What a child brings to the device again
+                    // when it is built; a subtree that does not fit the budget is refused here, by the name the builder would use.)
+                    std::vector<const uint64_t *> lists;
+                    std::vector<uint64_t> lens;
+                    uint64_t sum = 0;
+                    for (uint32_t u : ub) {
+                        lists.push_back(store.keys() + bin_off[u]);
+                        lens.push_back(counts[u]);
+                        sum += counts[u];
+                    }
+                    if (sum * 8 > budget_bytes / 2)
+                        return build_error("the subtree of IXF " + std::to_string(lay->next_ixf[b]) + " brings " + std::to_string(sum) + " keys (" +
+                                           std::to_string(sum * 8 >> 20) + " MiB), more than half the device key budget of " +
+                                           std::to_string(budget_bytes >> 20) + " MiB; a smaller --tmax keeps subtrees smaller");
+                    if (taxor_gpu_keys_union(c.device, lists.data(), lens.data(), lists.size(), 0, nullptr, 0, 0, &sz) != TAXOR_OK)
+                        return build_error(taxor_gpu_last_error());
+                }
             }
             key_off.push_back(key_off.back() + (lay->fname_idx[b] >= 0 ? sz : 0));
+            bin_first_key.push_back(lay->fname_idx[b] >= 0 ? f0 : 0);
+            bin_key_count.push_back(lay->fname_idx[b] >= 0 ? sz : 0);
             mx = std::max(mx, sz);
             nx[i].push_back(lay->next_ixf[b]);
             fn[i].push_back(lay->fname_idx[b]);
@@ -337,7 +416,7 @@ int build_command(int argc, char **argv)
     }
     const double t_lay = now();
     const uint64_t *d_arranged = nullptr;
-    if (taxor_gpu_keyer_arrange(kr, first.data(), count.data(), first.size(), &d_arranged) != TAXOR_OK) return build_error(taxor_gpu_last_error());
+    if (!stream && taxor_gpu_keyer_arrange(kr, first.data(), count.data(), first.size(), &d_arranged) != TAXOR_OK) return build_error(taxor_gpu_last_error());
     // ---- construction on the device
     taxor_hixf_view hv{};
     hv.n_ixf = n_ixf;
@@ -356,8 +435,14 @@ int build_command(int argc, char **argv)
     for (uint64_t i = 0; i < n_ixf; ++i)
         if (taxor_gpu_index_fill_random(idx, i, schema.default_seed + i) != TAXOR_OK) return build_error(taxor_gpu_last_error());
     taxor_build_stats bst{};
-    if (taxor_gpu_index_build_hixf_ex(idx, d_arranged, 1, key_off.data(), schema.default_seed, &bst) != TAXOR_OK)
-        return build_error(taxor_gpu_last_error());
+    if (!stream) {
+        if (taxor_gpu_index_build_hixf_ex(idx, d_arranged, 1, key_off.data(), schema.default_seed, &bst) != TAXOR_OK) return build_error(taxor_gpu_last_error());
+    } else {
+        // a part is a range of the store: nothing is arranged, every technical bin says where its keys lie.  Half the budget: an IXF
+        // larger than it is built from two buffers of that size, one peeling while the other fills
+        if (taxor_gpu_index_build_hixf_stream_ranges(idx, store.keys(), bin_first_key.data(), bin_key_count.data(), schema.default_seed, budget_bytes / 2, &bst) != TAXOR_OK)
+            return build_error(taxor_gpu_last_error());
+    }
     printf("done!\n");
     printf("building HIXF index ... ");
     fflush(stdout);
@@ -371,8 +456,7 @@ int build_command(int argc, char **argv)
         views[i].seed = taxor_gpu_index_ixf_seed(idx, i);
         index_bytes += data[i].size();
     }
-    taxor_keyer_stats ks{};
-    (void)taxor_gpu_keyer_stats(kr, &ks);
+    if (!stream) (void)taxor_gpu_keyer_stats(kr, &ks);
     kr_guard.reset();
     idx_guard.reset();
     std::vector<taxor_species> sp(n);
@@ -402,9 +486,11 @@ int build_command(int argc, char **argv)
     for (uint64_t b = 0; b < n; ++b) n_keys += counts[b];
     fprintf(stderr,
             "taxor build: %llu genomes, %llu bases (%llu file bytes), %llu distinct keys, %llu IXFs, depth %u, %llu index bytes, t_max %llu; "
-            "seconds: read+key %.3f (keyer on the device %.3f), layout %.3f, construction %.3f, store %.3f, total %.3f\n",
+            "seconds: read+key %.3f (keyer on the device %.3f), layout %.3f, construction %.3f, store %.3f, total %.3f; "
+            "path %s: %llu waves, %u groups, %u bin ranges, %u restarts, key uploads %.3f s of which %.3f s were waited for\n",
             (unsigned long long)n, (unsigned long long)n_bases, (unsigned long long)file_bytes, (unsigned long long)n_keys,
             (unsigned long long)n_ixf, depth, (unsigned long long)index_bytes, (unsigned long long)lay->t_max, t_key1 - t_key0, ks.seconds_device, t_lay - t_key1,
-            t_build - t_lay, t_end - t_build, t_end - t_start);
+            t_build - t_lay, t_end - t_build, t_end - t_start, stream ? "stream" : "resident", (unsigned long long)n_waves, bst.stream_groups, bst.stream_ranges,
+            bst.stream_restarts, bst.seconds_upload + bst.seconds_stream_upload, bst.seconds_upload + bst.seconds_stream_upload_wait);
     return 0;
 }

@@ -799,6 +799,29 @@ constexpr uint64_t NO_GEN = ~0ull;
 
 uint64_t next_seed(uint64_t s) { return s * 6364136223846793005ull + 1442695040888963407ull; }
 
+// the bins [b0, b1) of `p` that have keys -> jobs of the chunk's IXF `group`
+void add_bin_jobs(const IxfPlan &p, uint32_t arith, uint32_t group, uint64_t b0, uint64_t b1, std::vector<BinJob> &jobs)
+{
+    for (uint64_t b = b0; b < b1; ++b) {
+        if (!p.n[b]) continue;
+        BinJob j{};
+        j.keys = p.keys[b];
+        j.gen_first = p.gen_first[b] == NO_GEN ? 0 : p.gen_first[b];
+        j.gen_salt = p.gen_salt;
+        j.keep = p.keep[b];
+        j.n_keys = p.n[b];
+        j.n_kept = p.kept[b];
+        j.data = p.data;
+        j.stride = p.stride;
+        j.seed = p.seed;
+        j.seg_len = (uint32_t)p.seg_len;
+        j.arith = arith;
+        j.bin = (uint32_t)b;
+        j.group = group;
+        jobs.push_back(j);
+    }
+}
+
 // construct the IXFs of `plans` (one level of a hierarchy, or a single IXF): as many as fit go into one chunk; an IXF that
 // does not peel is redone with a redrawn seed; an IXF larger than a chunk is built from several chunks of its bins
 int build_plans(Engine &eng, taxor_gpu_index *idx, std::vector<IxfPlan> &plans)
@@ -807,26 +830,7 @@ int build_plans(Engine &eng, taxor_gpu_index *idx, std::vector<IxfPlan> &plans)
     std::vector<size_t> todo;
     for (size_t i = 0; i < plans.size(); ++i)
         if (plans[i].total) todo.push_back(i);
-    auto add_jobs = [&](const IxfPlan &p, uint32_t group, uint64_t b0, uint64_t b1, std::vector<BinJob> &jobs) {
-        for (uint64_t b = b0; b < b1; ++b) {
-            if (!p.n[b]) continue;
-            BinJob j{};
-            j.keys = p.keys[b];
-            j.gen_first = p.gen_first[b] == NO_GEN ? 0 : p.gen_first[b];
-            j.gen_salt = p.gen_salt;
-            j.keep = p.keep[b];
-            j.n_keys = p.n[b];
-            j.n_kept = p.kept[b];
-            j.data = p.data;
-            j.stride = p.stride;
-            j.seed = p.seed;
-            j.seg_len = (uint32_t)p.seg_len;
-            j.arith = arith;
-            j.bin = (uint32_t)b;
-            j.group = group;
-            jobs.push_back(j);
-        }
-    };
+    auto add_jobs = [&](const IxfPlan &p, uint32_t group, uint64_t b0, uint64_t b1, std::vector<BinJob> &jobs) { add_bin_jobs(p, arith, group, b0, b1, jobs); };
     for (size_t q : todo) eng.fit_bin(3 * plans[q].seg_len, plans[q].max_bin >= WIDE_KEYS);
     while (!todo.empty()) {
         std::vector<BinJob> jobs;
@@ -1340,4 +1344,395 @@ extern "C" int taxor_gpu_index_build_hixf_gen(taxor_gpu_index *idx, const uint64
                                               const uint64_t *gen_first, const uint64_t *gen_count, uint64_t gen_salt, uint64_t seed0, taxor_build_stats *stats)
 {
     return build_hixf_impl(idx, keys, keys_on_device, key_off, seed0, nullptr, stats, gen_first, gen_count, gen_salt);
+}
+
+// ---- construction with a bounded part of the keys on the device (include/taxor_gpu_tools.h; DESIGN.md section 9, "Beyond device memory")
+
+// Bins [bin0, bin1) of `p` under p.seed: build_plans' walk over an IXF larger than a chunk (chunks of bins that fit the peeling
+// scratch), made callable.  cleared: the IXF's array was set to 0 in this attempt (else the columns are cleared one by one).  A bin
+// that cannot be placed is an error, not another turn of the loop.
+static int build_bin_range(Engine &eng, uint32_t arith, const IxfPlan &p, uint64_t bin0, uint64_t bin1, bool cleared, bool *all_ok)
+{
+    *all_ok = true;
+    const uint64_t per_bin = 3 * p.seg_len;
+    bool wide = false, any = false;
+    for (uint64_t b = bin0; b < bin1; ++b) {
+        if (p.n[b] >= 0xFFFFFFFFull)
+            return fail(TAXOR_E_ARG, "build: bin %llu of IXF %llu holds %llu keys, more than 2^32 - 2", (unsigned long long)b, (unsigned long long)p.ixf, (unsigned long long)p.n[b]);
+        wide |= p.n[b] >= WIDE_KEYS;
+        any |= p.n[b] != 0;
+    }
+    if (!any) return TAXOR_OK;
+    eng.fit_bin(per_bin, wide);
+    const uint64_t budget = eng.slot_budget(wide);
+    if (per_bin > budget) return fail(TAXOR_E_NOMEM, "build: one bin of IXF " + std::to_string(p.ixf) + " does not fit the peeling scratch");
+    std::vector<BinJob> jobs;
+    std::vector<uint8_t> full, ok;
+    for (uint64_t b0 = bin0; b0 < bin1 && *all_ok;) {
+        uint64_t b1 = b0, s = 0, k = 0;
+        while (b1 < bin1 && (p.n[b1] == 0 || (s + per_bin <= budget && k + p.n[b1] < (1ull << 32)))) {
+            if (p.n[b1]) { s += per_bin; k += p.n[b1]; }
+            ++b1;
+        }
+        if (b1 == b0) return fail(TAXOR_E_INTERNAL, "build: bin %llu of IXF %llu fits no chunk", (unsigned long long)b0, (unsigned long long)p.ixf);
+        jobs.clear();
+        add_bin_jobs(p, arith, 0, b0, b1, jobs);
+        full.assign(1, cleared ? 2 : 0);
+        const int rc = eng.run(jobs, 1, ok, full);
+        if (rc != TAXOR_OK) return rc;
+        if (!ok[0]) *all_ok = false;
+        b0 = b1;
+    }
+    return TAXOR_OK;
+}
+
+extern "C" int taxor_gpu_index_build_ixf_bins(taxor_gpu_index *idx, uint64_t ixf, uint64_t bin0, uint64_t bin1, const uint64_t *keys, int keys_on_device,
+                                              const uint64_t *key_off, uint64_t seed, uint32_t flags, int *ok_out)
+{
+    IxfPlan p;
+    int device = 0;
+    if (!idx || !key_off || !ok_out) return fail(TAXOR_E_ARG, "build_ixf_bins: null argument");
+    *ok_out = 0;
+    int rc = plan_ixf(idx, ixf, p, &device);
+    if (rc != TAXOR_OK) return rc;
+    if (bin0 > bin1 || bin1 > p.bins) return fail(TAXOR_E_ARG, "build_ixf_bins: bins [%llu, %llu) of an IXF of %llu", (unsigned long long)bin0, (unsigned long long)bin1, (unsigned long long)p.bins);
+    for (uint64_t b = bin0; b < bin1; ++b) {
+        if (key_off[b + 1] < key_off[b]) return fail(TAXOR_E_ARG, "build_ixf_bins: key_off not monotone");
+        if (key_off[b + 1] - key_off[b] >= 0xFFFFFFFFull)
+            return fail(TAXOR_E_ARG, "build_ixf_bins: bin %llu of IXF %llu holds %llu keys, more than 2^32 - 2", (unsigned long long)b, (unsigned long long)ixf,
+                        (unsigned long long)(key_off[b + 1] - key_off[b]));
+    }
+    const uint64_t total = key_off[bin1] - key_off[bin0];
+    if (total && !keys) return fail(TAXOR_E_ARG, "build_ixf_bins: null keys");
+    if (hipSetDevice(device) != hipSuccess) return fail(TAXOR_E_HIP, "build_ixf_bins: hipSetDevice failed");
+    DeviceBuf<uint64_t> own;
+    const uint64_t *d_keys = keys ? keys + key_off[bin0] : nullptr;
+    if (total && !keys_on_device) {
+        if (own.alloc(total) != hipSuccess) return fail(TAXOR_E_NOMEM, "build_ixf_bins: no device memory for the keys");
+        if (upload_keys(device, own.p, keys + key_off[bin0], total) != hipSuccess) return fail(TAXOR_E_HIP, "build_ixf_bins: key upload failed");
+        d_keys = own.p;
+    }
+    for (uint64_t b = bin0; b < bin1; ++b) {
+        p.keys[b] = d_keys ? d_keys + (key_off[b] - key_off[bin0]) : nullptr;
+        p.n[b] = p.kept[b] = key_off[b + 1] - key_off[b];
+    }
+    p.seed = seed;
+    BuildCtx *ctx = build_ctx_of(idx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    Engine &eng = ctx->eng;
+    eng.stats = taxor_build_stats{};
+    rc = eng.open(device);
+    if (rc != TAXOR_OK) return rc;
+    if ((flags & TAXOR_BINS_CLEAR) && hipMemsetAsync(p.data, 0, 3 * p.seg_len * p.stride, eng.st) != hipSuccess) return fail(TAXOR_E_HIP, "build: clearing an IXF failed");
+    bool all_ok = false;
+    rc = build_bin_range(eng, taxor_index_arith(idx), p, bin0, bin1, (flags & (TAXOR_BINS_CLEAR | TAXOR_BINS_CLEARED)) != 0, &all_ok);
+    if (rc == TAXOR_OK && hipStreamSynchronize(eng.st) != hipSuccess) rc = fail(TAXOR_E_HIP, "build_ixf_bins: the builder's stream failed");
+    if (rc != TAXOR_OK) return rc;
+    if (all_ok) taxor_index_set_seed(idx, ixf, seed);
+    *ok_out = all_ok ? 1 : 0;
+    return TAXOR_OK;
+}
+
+namespace {
+
+// one run of keys in host memory that goes to the device in one piece
+struct HostRun { const uint64_t *src; uint64_t n, dst; };      // dst: position (in keys) inside the device buffer
+
+// the bins' host key lists -> runs (lists that follow one another in memory travel together) and the bins' device positions
+void plan_runs(const std::vector<const uint64_t *> &src, const std::vector<uint64_t> &n, uint64_t b0, uint64_t b1, uint64_t *pos, std::vector<HostRun> &runs,
+               std::vector<uint64_t> &bin_pos)
+{
+    for (uint64_t b = b0; b < b1; ++b) {
+        bin_pos[b] = *pos;
+        if (!n[b]) continue;
+        if (!runs.empty() && runs.back().src + runs.back().n == src[b] && runs.back().dst + runs.back().n == *pos) runs.back().n += n[b];
+        else runs.push_back(HostRun{src[b], n[b], *pos});
+        *pos += n[b];
+    }
+}
+
+// the runs into d_buf: large ones through upload_keys' page-locked pipeline, the others on `st`; everything has arrived on return
+hipError_t upload_runs(int device, uint64_t *d_buf, const std::vector<HostRun> &runs, hipStream_t st, uint64_t *bytes)
+{
+    hipError_t e = hipSetDevice(device);
+    for (size_t r = 0; r < runs.size() && e == hipSuccess; ++r) {
+        const HostRun &u = runs[r];
+        if (u.n * 8 >= (256ull << 20)) e = upload_keys(device, d_buf + u.dst, u.src, u.n);
+        else e = hipMemcpyAsync(d_buf + u.dst, u.src, u.n * 8, hipMemcpyHostToDevice, st);
+        *bytes += u.n * 8;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e;
+}
+
+int build_hixf_stream_impl(taxor_gpu_index *idx, const uint64_t *host_keys, const uint64_t *key_first, const uint64_t *key_count, uint64_t seed0,
+                           uint64_t budget_bytes, taxor_build_stats *stats_out)
+{
+    uint64_t n_ixf = 0;
+    const uint32_t *bin_base = nullptr, *binfo = nullptr;
+    if (!idx || !key_first || !key_count || taxor_index_tree(idx, &n_ixf, &bin_base, &binfo)) return fail(TAXOR_E_ARG, "build_hixf_stream: bad index");
+    if (stats_out) *stats_out = taxor_build_stats{};
+    const uint64_t budget_keys = budget_bytes / 8;
+    if (!budget_keys) return fail(TAXOR_E_ARG, "build_hixf_stream: a budget of %llu bytes holds no key", (unsigned long long)budget_bytes);
+    std::vector<IxfPlan> plan(n_ixf);
+    int device = 0;
+    for (uint64_t i = 0; i < n_ixf; ++i) {
+        const int rc = plan_ixf(idx, i, plan[i], &device);
+        if (rc != TAXOR_OK) return rc;
+        plan[i].seed = seed0 + 0x9E3779B97F4A7C15ull * i;
+    }
+    bool any_keys = false;
+    for (uint64_t i = 0; i < n_ixf; ++i)
+        for (uint64_t b = 0; b < plan[i].bins; ++b) {
+            const uint64_t g = bin_base[i] + b, n = key_count[g];
+            if ((binfo[g] & BINFO_MERGED) && n) return fail(TAXOR_E_ARG, "build_hixf_stream: a merged bin must not bring keys of its own (they come from its child)");
+            if (n >= 0xFFFFFFFFull)
+                return fail(TAXOR_E_ARG, "build_hixf_stream: bin %llu of IXF %llu holds %llu keys, more than 2^32 - 2", (unsigned long long)b, (unsigned long long)i, (unsigned long long)n);
+            if (n > budget_keys)
+                return fail(TAXOR_E_ARG, "build_hixf_stream: bin %llu of IXF %llu holds %llu keys, the device key budget %llu", (unsigned long long)b, (unsigned long long)i,
+                            (unsigned long long)n, (unsigned long long)budget_keys);
+            any_keys |= n != 0;
+        }
+    if (any_keys && !host_keys) return fail(TAXOR_E_ARG, "build_hixf_stream: null keys");
+    if (hipSetDevice(device) != hipSuccess) return fail(TAXOR_E_HIP, "build_hixf_stream: hipSetDevice failed");
+    const double t0 = now_s();
+    std::vector<int> depth(n_ixf, -1);
+    int max_depth = 0;
+    {
+        std::vector<uint64_t> stack{0};
+        depth[0] = 0;
+        while (!stack.empty()) {
+            const uint64_t i = stack.back();
+            stack.pop_back();
+            for (uint64_t b = 0; b < plan[i].bins; ++b) {
+                const uint32_t bi = binfo[bin_base[i] + b];
+                if (!(bi & BINFO_MERGED)) continue;
+                const uint64_t c = bi & 0x3FFFFFFFu;
+                if (c >= n_ixf || depth[c] >= 0) return fail(TAXOR_E_ARG, "build_hixf_stream: the hierarchy is not a tree");
+                depth[c] = depth[i] + 1;
+                max_depth = std::max(max_depth, depth[c]);
+                stack.push_back(c);
+            }
+        }
+    }
+    BuildCtx *ctx = build_ctx_of(idx);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    Engine &eng = ctx->eng;
+    eng.stats = taxor_build_stats{};
+    int rc = eng.open(device);
+    if (rc != TAXOR_OK) return rc;
+    const uint32_t arith = taxor_index_arith(idx);
+    KeyUnion &unioner = ctx->unioner;
+    std::vector<std::vector<uint64_t>> uni(n_ixf);          // the host arena: every built child's key set, until its parent is built
+    DeviceBuf<uint64_t> buf[2];
+    hipStream_t up_st = nullptr;
+    hipEvent_t up_ev[2] = {nullptr, nullptr};
+    auto cleanup = [&] {
+        for (auto &e : up_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+        if (up_st) (void)hipStreamDestroy(up_st);
+        up_st = nullptr;
+        buf[0].release();
+        buf[1].release();
+    };
+    auto room = [&](int k, uint64_t n) -> int {
+        const double ta = now_s();
+        const hipError_t e = buf[k].reserve(n, n);
+        eng.stats.seconds_alloc += now_s() - ta;
+        return e == hipSuccess ? TAXOR_OK : fail(TAXOR_E_NOMEM, "build_hixf_stream: no device memory for %llu keys", (unsigned long long)n);
+    };
+    // where bin b of IXF i has its keys in host memory: its own list, or the set of the child below it
+    std::vector<std::vector<const uint64_t *>> src(n_ixf);
+    for (int d = max_depth; d >= 0 && rc == TAXOR_OK; --d) {
+        std::vector<uint64_t> ids;
+        for (uint64_t i = 0; i < n_ixf; ++i) {
+            if (depth[i] != d) continue;
+            IxfPlan &p = plan[i];
+            src[i].assign(p.bins, nullptr);
+            for (uint64_t b = 0; b < p.bins; ++b) {
+                const uint64_t g = bin_base[i] + b;
+                if (binfo[g] & BINFO_MERGED) {
+                    const std::vector<uint64_t> &u = uni[binfo[g] & 0x3FFFFFFFu];
+                    src[i][b] = u.data();
+                    p.n[b] = p.kept[b] = u.size();
+                } else {
+                    src[i][b] = host_keys ? host_keys + key_first[g] : nullptr;
+                    p.n[b] = p.kept[b] = key_count[g];
+                }
+                if (p.n[b] > budget_keys)
+                    rc = fail(TAXOR_E_ARG, "build_hixf_stream: bin %llu of IXF %llu holds %llu keys, the device key budget %llu", (unsigned long long)b, (unsigned long long)i,
+                              (unsigned long long)p.n[b], (unsigned long long)budget_keys);
+            }
+            plan_totals(p);
+            if (rc == TAXOR_OK && d > 0 && p.total > budget_keys)
+                rc = fail(TAXOR_E_ARG, "build_hixf_stream: the subtree of IXF %llu brings %llu keys (%llu MiB), the device key budget is %llu MiB", (unsigned long long)i,
+                          (unsigned long long)p.total, (unsigned long long)(p.total * 8 >> 20), (unsigned long long)(budget_bytes >> 20));
+            if (rc == TAXOR_OK && d > 0 && p.total >= 0xFFFFFFFFull) rc = fail(TAXOR_E_ARG, "build_hixf_stream: more than 2^32 - 2 keys below one merged bin");
+            ids.push_back(i);
+        }
+        if (rc != TAXOR_OK) break;
+        if (d == 0 && plan[0].total > budget_keys) {
+            // ---- the root in bin ranges that fit: range r + 1 is uploaded by a thread of its own, on a stream of its own, into
+            //      the buffer that range r does not use.  That buffer is free: the peel that read it has been waited for
+            //      (Engine::run returns after its stream).  The builder's stream waits for the upload's event.
+            IxfPlan &p = plan[0];
+            std::vector<uint64_t> r_first{0}, r_keys;
+            {
+                uint64_t k = 0;
+                for (uint64_t b = 0; b < p.bins; ++b) {
+                    if (k + p.n[b] > budget_keys) { r_first.push_back(b); r_keys.push_back(k); k = 0; }
+                    k += p.n[b];
+                }
+                r_first.push_back(p.bins);
+                r_keys.push_back(k);
+            }
+            const size_t n_ranges = r_keys.size();
+            const uint64_t largest = *std::max_element(r_keys.begin(), r_keys.end());
+            if ((rc = room(0, largest)) != TAXOR_OK || (rc = room(1, largest)) != TAXOR_OK) break;
+            if (hipStreamCreateWithFlags(&up_st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&up_ev[0], hipEventDisableTiming) != hipSuccess ||
+                hipEventCreateWithFlags(&up_ev[1], hipEventDisableTiming) != hipSuccess) { rc = fail(TAXOR_E_HIP, "build_hixf_stream: no stream for the uploads"); break; }
+            std::vector<std::vector<HostRun>> runs(n_ranges);
+            std::vector<uint64_t> bin_pos(p.bins, 0);
+            for (size_t r = 0; r < n_ranges; ++r) {
+                uint64_t pos = 0;
+                plan_runs(src[0], p.n, r_first[r], r_first[r + 1], &pos, runs[r], bin_pos);
+            }
+            const bool all_bins = p.n_with_keys == p.bins;
+            std::thread up_thread;
+            hipError_t up_err = hipSuccess;
+            double up_seconds = 0.0;
+            uint64_t up_bytes = 0;
+            auto start_upload = [&](size_t r) {
+                up_thread = std::thread([&, r] {
+                    const double tu = now_s();
+                    up_err = upload_runs(device, buf[r & 1].p, runs[r], up_st, &up_bytes);
+                    if (up_err == hipSuccess) up_err = hipEventRecord(up_ev[r & 1], up_st);
+                    up_seconds = now_s() - tu;
+                });
+            };
+            bool built = false;
+            while (!built && rc == TAXOR_OK) {
+                built = true;
+                const uint64_t inserted_before = eng.stats.keys_inserted, lds_before = eng.stats.keys_counted_in_lds;
+                if (all_bins && hipMemsetAsync(p.data, 0, 3 * p.seg_len * p.stride, eng.st) != hipSuccess) { rc = fail(TAXOR_E_HIP, "build: clearing an IXF failed"); break; }
+                start_upload(0);
+                for (size_t r = 0; r < n_ranges && built && rc == TAXOR_OK; ++r) {
+                    const double tw = now_s();
+                    up_thread.join();
+                    eng.stats.seconds_stream_upload_wait += now_s() - tw;
+                    eng.stats.seconds_stream_upload += up_seconds;
+                    eng.stats.stream_bytes_uploaded += up_bytes;
+                    up_bytes = 0;
+                    if (up_err != hipSuccess) { rc = fail(TAXOR_E_HIP, std::string("build_hixf_stream: key upload failed: ") + hipGetErrorString(up_err)); break; }
+                    if (hipStreamWaitEvent(eng.st, up_ev[r & 1], 0) != hipSuccess) { rc = fail(TAXOR_E_HIP, "build_hixf_stream: waiting for an upload failed"); break; }
+                    if (r + 1 < n_ranges) start_upload(r + 1);
+                    for (uint64_t b = r_first[r]; b < r_first[r + 1]; ++b) p.keys[b] = buf[r & 1].p + bin_pos[b];
+                    bool ok = false;
+                    rc = build_bin_range(eng, arith, p, r_first[r], r_first[r + 1], all_bins, &ok);
+                    if (rc == TAXOR_OK && !ok) built = false;
+                }
+                if (up_thread.joinable()) {          // an upload that nobody will use: let it finish before its buffer goes
+                    up_thread.join();
+                    eng.stats.seconds_stream_upload += up_seconds;
+                    eng.stats.stream_bytes_uploaded += up_bytes;
+                    up_bytes = 0;
+                }
+                if (rc != TAXOR_OK) break;
+                if (!built) {
+                    eng.stats.keys_inserted = inserted_before;
+                    eng.stats.keys_counted_in_lds = lds_before;
+                    ++eng.stats.stream_restarts;
+                    if (++p.attempts >= 32) { rc = fail(TAXOR_E_INTERNAL, "build: no seed peeled every bin of IXF " + std::to_string(p.ixf) + " in 32 attempts (duplicate keys inside a bin?)"); break; }
+                    p.seed = next_seed(p.seed);
+                }
+            }
+            if (rc != TAXOR_OK) break;
+            eng.stats.stream_ranges = (uint32_t)n_ranges;
+            taxor_index_set_seed(idx, p.ixf, p.seed);
+            break;
+        }
+        // ---- the level's IXFs in groups whose keys fit the budget
+        for (size_t q0 = 0; q0 < ids.size() && rc == TAXOR_OK;) {
+            size_t q1 = q0;
+            uint64_t group_keys = 0;
+            while (q1 < ids.size() && (q1 == q0 || group_keys + plan[ids[q1]].total <= budget_keys)) group_keys += plan[ids[q1++]].total;
+            ++eng.stats.stream_groups;
+            std::vector<HostRun> runs;
+            std::vector<uint64_t> ixf_pos(q1 - q0, 0);
+            uint64_t pos = 0;
+            std::vector<std::vector<uint64_t>> bin_pos(q1 - q0);
+            for (size_t q = q0; q < q1; ++q) {
+                const IxfPlan &p = plan[ids[q]];
+                ixf_pos[q - q0] = pos;
+                bin_pos[q - q0].assign(p.bins, 0);
+                plan_runs(src[ids[q]], p.n, 0, p.bins, &pos, runs, bin_pos[q - q0]);
+            }
+            if (group_keys && (rc = room(0, group_keys)) != TAXOR_OK) break;
+            const double tu = now_s();
+            uint64_t bytes = 0;
+            const hipError_t e = upload_runs(device, buf[0].p, runs, eng.st, &bytes);
+            eng.stats.seconds_upload += now_s() - tu;
+            eng.stats.stream_bytes_uploaded += bytes;
+            if (e != hipSuccess) { rc = fail(TAXOR_E_HIP, std::string("build_hixf_stream: key upload failed: ") + hipGetErrorString(e)); break; }
+            std::vector<IxfPlan> level;
+            for (size_t q = q0; q < q1; ++q) {
+                IxfPlan &p = plan[ids[q]];
+                for (uint64_t b = 0; b < p.bins; ++b) p.keys[b] = p.n[b] ? buf[0].p + bin_pos[q - q0][b] : nullptr;
+                level.push_back(p);
+            }
+            rc = build_plans(eng, idx, level);
+            if (rc != TAXOR_OK) break;
+            for (size_t q = q0; q < q1; ++q) plan[ids[q]].seed = level[q - q0].seed;
+            if (d > 0) {
+                // every IXF's key set, each key once, back to host memory for the level above.  The set is written over the IXF's own
+                // keys (they are built; the table holds them when the compaction starts)
+                const double tn = now_s();
+                for (size_t q = q0; q < q1 && rc == TAXOR_OK; ++q) {
+                    const IxfPlan &p = plan[ids[q]];
+                    if (!p.total) continue;
+                    uint64_t *d_in = buf[0].p + ixf_pos[q - q0], n_out = 0;
+                    hipError_t eu = unioner.unique(d_in, p.total, d_in, &n_out, eng.st);
+                    if (eu == hipSuccess) {
+                        uni[ids[q]].resize(n_out);
+                        eu = hipMemcpy(uni[ids[q]].data(), d_in, n_out * 8, hipMemcpyDeviceToHost);
+                    }
+                    if (eu != hipSuccess) rc = fail(TAXOR_E_HIP, std::string("build_hixf_stream: key union failed: ") + hipGetErrorString(eu));
+                }
+                eng.stats.seconds_union += now_s() - tn;
+            }
+            q0 = q1;
+        }
+        // the sets of the level below have been read
+        for (uint64_t i = 0; i < n_ixf; ++i)
+            if (depth[i] == d + 1) std::vector<uint64_t>().swap(uni[i]);
+    }
+    eng.stats.seconds_total = now_s() - t0;
+    const double t_rel = now_s();
+    cleanup();
+    eng.stats.seconds_release = now_s() - t_rel;
+    if (rc != TAXOR_OK) return rc;
+    if (stats_out) *stats_out = eng.stats;
+    return TAXOR_OK;
+}
+
+} // namespace
+
+extern "C" int taxor_gpu_index_build_hixf_stream_ranges(taxor_gpu_index *idx, const uint64_t *host_keys, const uint64_t *key_first, const uint64_t *key_count,
+                                                        uint64_t seed0, uint64_t budget_bytes, taxor_build_stats *stats)
+{
+    return build_hixf_stream_impl(idx, host_keys, key_first, key_count, seed0, budget_bytes, stats);
+}
+
+extern "C" int taxor_gpu_index_build_hixf_stream(taxor_gpu_index *idx, const uint64_t *host_keys, const uint64_t *key_off, uint64_t seed0, uint64_t budget_bytes,
+                                                 taxor_build_stats *stats)
+{
+    uint64_t n_ixf = 0;
+    const uint32_t *bin_base = nullptr, *binfo = nullptr;
+    if (!idx || !key_off || taxor_index_tree(idx, &n_ixf, &bin_base, &binfo)) return fail(TAXOR_E_ARG, "build_hixf_stream: bad index");
+    const uint64_t total_bins = bin_base[n_ixf];
+    std::vector<uint64_t> count(total_bins);
+    for (uint64_t g = 0; g < total_bins; ++g) {
+        if (key_off[g + 1] < key_off[g]) return fail(TAXOR_E_ARG, "build_hixf_stream: key_off not monotone");
+        count[g] = key_off[g + 1] - key_off[g];
+    }
+    return build_hixf_stream_impl(idx, host_keys, key_off, count.data(), seed0, budget_bytes, stats);
 }

@@ -10,6 +10,11 @@
 // constructs depend on the key SET only, builder.hip).
 #include "keyset.h"
 
+#include "../../include/taxor_gpu_tools.h"
+#include "hip_host.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
+
 #include <algorithm>
 
 namespace taxor {
@@ -175,3 +180,47 @@ hipError_t keyset_count_distinct(const uint64_t *d_in, uint64_t n, uint64_t *n_o
 }
 
 } // namespace taxor
+
+// The union of key lists that no resident keyer holds (include/taxor_gpu_tools.h): the lists are gathered into one device array,
+// KeyUnion::unique drops the duplicates (the marker 2^64 - 1 kept aside and appended once, as for the builder), and a caller that
+// wants the keys gets them sorted -- the table's order depends on which lane came first.
+extern "C" int taxor_gpu_keys_union(int device, const uint64_t *const *lists, const uint64_t *counts, uint64_t n_lists, int lists_on_device,
+                                    uint64_t *out, int out_on_device, uint64_t out_cap, uint64_t *n_out)
+{
+    using namespace taxor;
+    if (!n_out || (n_lists && (!lists || !counts))) return fail(TAXOR_E_ARG, "keys_union: null argument");
+    *n_out = 0;
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n_lists; ++i) {
+        if (counts[i] && !lists[i]) return fail(TAXOR_E_ARG, "keys_union: list %llu is null", (unsigned long long)i);
+        if (counts[i] > (1ull << 40) || (total += counts[i]) > (1ull << 40)) return fail(TAXOR_E_ARG, "keys_union: more than 2^40 keys");
+    }
+    if (!total) return TAXOR_OK;
+    if (hipSetDevice(device) != hipSuccess) return fail(TAXOR_E_HIP, "keys_union: hipSetDevice failed");
+    DeviceBuf<uint64_t> in, uni, sorted;
+    DeviceBuf<char> tmp;
+    if (in.alloc(total) != hipSuccess || uni.alloc(total) != hipSuccess) return fail(TAXOR_E_NOMEM, "keys_union: no device memory for %llu keys", (unsigned long long)total);
+    uint64_t o = 0;
+    for (uint64_t i = 0; i < n_lists; ++i) {
+        if (!counts[i]) continue;
+        if (hipMemcpy(in.p + o, lists[i], counts[i] * 8, lists_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess)
+            return fail(TAXOR_E_HIP, "keys_union: copying list %llu failed", (unsigned long long)i);
+        o += counts[i];
+    }
+    KeyUnion u;
+    uint64_t n = 0;
+    hipError_t e = u.unique(in.p, total, uni.p, &n, nullptr);
+    if (e != hipSuccess) return fail(TAXOR_E_HIP, std::string("keys_union: key union failed: ") + hipGetErrorString(e));
+    *n_out = n;
+    if (!out) return TAXOR_OK;
+    if (out_cap < n) return fail(TAXOR_E_ARG, "keys_union: the union holds %llu keys, the output has room for %llu", (unsigned long long)n, (unsigned long long)out_cap);
+    size_t tmp_bytes = 0;
+    uint64_t *dst = out_on_device ? out : in.p;                  // (the gathered input is not needed any more)
+    e = rocprim::radix_sort_keys(nullptr, tmp_bytes, uni.p, dst, (size_t)n, 0, 64, (hipStream_t) nullptr);
+    if (e == hipSuccess) e = tmp.alloc(tmp_bytes ? tmp_bytes : 8);
+    if (e == hipSuccess) e = rocprim::radix_sort_keys((void *)tmp.p, tmp_bytes, uni.p, dst, (size_t)n, 0, 64, (hipStream_t) nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess && !out_on_device) e = hipMemcpy(out, dst, n * 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(TAXOR_E_HIP, std::string("keys_union: sorting the union failed: ") + hipGetErrorString(e));
+    return TAXOR_OK;
+}

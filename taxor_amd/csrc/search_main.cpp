@@ -7,6 +7,7 @@
 #include "tuning.h"
 #include "ixf_arith.h"
 #include "ixf_layout.h"
+#include "key_store.h"
 using taxor::tune_env;
 extern char **environ;
 

@@ -66,6 +66,47 @@ class GenomeKeyer:
     __del__ = close
 
 
+def keys_union(lists, device=0, want_keys=True, on_device=False):
+    """taxor_gpu_keys_union: the duplicate-free union of uint64 key lists through the device set -> (size, sorted keys or None).
+    on_device: the lists are first put into device memory and handed over as device pointers, and the union comes back from a
+    device buffer (the path a caller with resident keys takes)."""
+    L = _lib.lib()
+    arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in lists]
+    counts = np.array([a.size for a in arrs], dtype=np.uint64)
+    total = int(counts.sum())
+    ptrs = (C.c_void_p * max(1, len(arrs)))()
+    dev = []
+    try:
+        for i, a in enumerate(arrs):
+            if on_device:
+                d = C.c_void_p()
+                check(L.taxor_gpu_malloc(device, a.size * 8, C.byref(d)))
+                dev.append(d)
+                if a.size:
+                    check(L.taxor_gpu_memcpy_from_host(d, _p(a), a.size * 8))
+                ptrs[i] = d.value
+            else:
+                ptrs[i] = a.ctypes.data if a.size else None
+        n = C.c_uint64(0)
+        if not want_keys:
+            check(L.taxor_gpu_keys_union(device, ptrs, _p(counts), len(arrs), 1 if on_device else 0, None, 0, 0, C.byref(n)))
+            return int(n.value), None
+        out = np.empty(max(1, total), dtype=np.uint64)
+        if on_device:
+            d_out = C.c_void_p()
+            check(L.taxor_gpu_malloc(device, out.size * 8, C.byref(d_out)))
+            dev.append(d_out)
+            check(L.taxor_gpu_keys_union(device, ptrs, _p(counts), len(arrs), 1, d_out, 1, total, C.byref(n)))
+            if n.value:
+                check(L.taxor_gpu_memcpy_to_host(_p(out), d_out, int(n.value) * 8))
+        else:
+            check(L.taxor_gpu_keys_union(device, ptrs, _p(counts), len(arrs), 0, _p(out), 0, total, C.byref(n)))
+        return int(n.value), out[:int(n.value)].copy()
+    finally:
+        for d in dev:
+            L.taxor_gpu_free(d)
+
+
 def build_layout(counts, t_max=0):
     """taxor_build_layout: the IXF tree for these per-user-bin distinct key counts.  Returns a dict with t_max, depth,
     bytes_per_hash, index_bytes and ixfs: [{bins, next_ixf, fname_idx, part, parts}] (IXF 0 = root)."""

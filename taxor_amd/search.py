@@ -271,6 +271,25 @@ class GpuIndex:
         check(_lib.lib().taxor_gpu_index_build_hixf_ex(self._h, _p(k) if k.size else None, 0, _p(o), int(seed0), C.byref(st)))
         return {kk: getattr(st, kk) for kk, _ in _lib.BuildStats._fields_ if kk != "reserved"}
 
+    def build_hixf_stream(self, keys, off, budget_bytes, seed0=1):
+        """taxor_gpu_index_build_hixf_stream: the whole hierarchy from keys in HOST memory with at most budget_bytes of them on the
+        device at a time (keys, off as for build_hixf_host_keys).  Byte-identical to build_hixf on the same keys and seed0."""
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        st = _lib.BuildStats()
+        check(_lib.lib().taxor_gpu_index_build_hixf_stream(self._h, _p(k) if k.size else None, _p(o), int(seed0), int(budget_bytes), C.byref(st)))
+        return {kk: getattr(st, kk) for kk, _ in _lib.BuildStats._fields_ if not kk.startswith("reserved")}
+
+    def build_ixf_bins(self, ixf, bin0, bin1, keys, off, seed, flags=0):
+        """taxor_gpu_index_build_ixf_bins: bins [bin0, bin1) of one IXF under `seed` (keys in host memory, off[bins + 1] for the
+        IXF's bins; keys may be None when only the offsets are to be judged) -> True when every bin of the range peeled"""
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        k = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint64)
+        ok = C.c_int(0)
+        check(_lib.lib().taxor_gpu_index_build_ixf_bins(self._h, ixf, int(bin0), int(bin1), _p(k) if k is not None and k.size else None, 0, _p(o),
+                                                        int(seed), int(flags), C.byref(ok)))
+        return bool(ok.value)
+
     def ixf_seed(self, ixf):
         return int(_lib.lib().taxor_gpu_index_ixf_seed(self._h, ixf))
 
