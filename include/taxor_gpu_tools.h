@@ -205,6 +205,61 @@ typedef struct {
 int taxor_build_layout(const uint64_t *counts, uint64_t n, uint64_t t_max, taxor_layout **out);
 void taxor_layout_free(taxor_layout *l);
 
+/* ---- search of an index that does not fit the device ("Search beyond device memory").  A child IXF is reached
+ * only through one merged bin of its parent, so the root stays resident and the SUBTREES -- one merged bin of the root with everything
+ * below it -- are brought in group by group: every read is searched once per pass against "root + this pass's group", and per read the
+ * passes' result lists are merged by DFS key.
+ * taxor_index_plan_passes (host only, no HIP call): subtrees in root-bin order, packed greedily into groups.  Two groups are on the
+ * device while one uploads behind the other, so root + group g + group g+1 <= budget_bytes for every g: a group is closed when the next
+ * subtree would take it past HALF of what the root leaves (a larger subtree is a group of its own) or past what the group before it
+ * leaves.  An index without a merged root bin, or one that fits the budget whole, is one pass.  Bytes are the slab's: every IXF rounded
+ * up to 4 KiB, and the slab's 4-KiB tail pad counted with the root.  TAXOR_E_ARG with a named message (taxor_gpu_last_error) before any
+ * work: "root-exceeds-budget" when the root alone exceeds the budget, "subtree-exceeds-budget" when one subtree exceeds what the root
+ * (and the group before it) leaves -- that message names the root bin and the child IXF and says that a smaller --tmax at build time helps.
+ * pass_of_ixf [n_ixf] (may be NULL): the pass an IXF is resident in, TAXOR_PASS_ROOT for the root; pass_bytes [n_ixf] (may be NULL): the
+ * first n_passes entries receive the groups' bytes. */
+#define TAXOR_PASS_ROOT 0xFFFFFFFFu
+typedef struct {
+    uint32_t n_passes, n_subtrees;
+    uint64_t root_bytes;    /* root IXF + tail pad */
+    uint64_t slab_bytes;    /* root_bytes + the largest pair of neighbouring groups: what a paged index allocates */
+    uint64_t index_bytes;   /* root_bytes + every subtree */
+} taxor_pass_plan;
+int taxor_index_plan_passes(const taxor_hixf_view *view, uint64_t budget_bytes, taxor_pass_plan *plan, uint32_t *pass_of_ixf, uint64_t *pass_bytes);
+/* An index whose slab is plan.slab_bytes <= budget_bytes: every table for the whole hierarchy, the root resident, every other IXF at a
+ * fixed place of its group's half of the slab (even groups from the root upwards, odd groups from the end downwards), NO group loaded:
+ * taxor_gpu_index_load_pass(idx, view, 0) comes before the first search.  taxor_gpu_index_data_bytes reports what is resident.  The
+ * builders and taxor_gpu_index_download_ixf are not for such an index. */
+int taxor_gpu_index_create_paged(const taxor_hixf_view *view, int device, uint64_t budget_bytes, taxor_gpu_index **out);
+/* 0 for an ordinary index */
+uint32_t taxor_gpu_index_passes(const taxor_gpu_index *idx);
+/* Makes group `pass` the searched one: waits until it is resident (uploads it if nothing did), marks the children of every other
+ * subtree absent -- a merged bin whose child is absent is counted and pruned as usual and nothing is enqueued for it -- and starts the
+ * upload of group pass + 1 on a thread and streams of its own, into the half of the slab that pass - 1 used.  `view` is the one the
+ * index was created from and stays valid until the next load_pass or the index's destruction.  pass is the one after the last loaded,
+ * or 0 (start over); every search of the pass before must have ENDED (taxor_gpu_search_batch_end / _batch_sync) on every searcher of
+ * the index: both are checked, TAXOR_E_ARG otherwise. */
+int taxor_gpu_index_load_pass(taxor_gpu_index *idx, const taxor_hixf_view *view, uint32_t pass);
+/* seconds taxor_gpu_index_load_pass has spent waiting for uploads so far (the rest of them was hidden behind the pass before) */
+double taxor_gpu_index_upload_wait_seconds(const taxor_gpu_index *idx);
+/* One earlier pass's results for the reads of the searcher's last batch, in host memory: the CSR as taxor_gpu_results gives it and the
+ * tuples' DFS keys (taxor_gpu_results_keys). */
+typedef struct {
+    uint64_t n_reads, n_tuples;
+    const uint64_t *read_off; /* [n_reads + 1] */
+    const int64_t *user_bin;  /* [n_tuples] */
+    const uint32_t *count;    /* [n_tuples] */
+    const uint32_t *key;      /* [n_tuples] ascending within a read */
+} taxor_gpu_prior;
+/* After taxor_gpu_search_batch_end (or _batch_sync) of the LAST pass: merges, per read, the n_prior lists with the searcher's own by DFS
+ * key on the device (one wavefront per read).  A key present in several lists is kept once -- a leaf bin of the root is found again in
+ * every pass, with the same count; a differing count is TAXOR_E_INTERNAL.  Afterwards the searcher's device-resident CSR is the complete
+ * one: taxor_gpu_batch_fetch, _batch_export_device, the communicator's gather and taxor_gpu_profile_feed_add_batch see it. */
+int taxor_gpu_search_merge_prior(taxor_gpu_searcher *s, const taxor_gpu_prior *prior, uint32_t n_prior);
+/* the DFS keys of the last results' tuples, [n_tuples] in host memory, valid until the next call on the searcher.  A call of a few
+ * thousand reads keeps its keys only on a searcher of a paged index (TAXOR_E_ARG otherwise). */
+int taxor_gpu_results_keys(taxor_gpu_searcher *s, const uint32_t **key);
+
 /* ---- taxor_gpu_search_batch split into its three phases so that a caller can keep a batch resident in HBM
  * (upload once, run many times) and overlap transfers with compute:
  *   upload : H2D of the ASCII bases + on-device dna4 mapping and 2-bit packing

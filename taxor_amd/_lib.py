@@ -163,10 +163,30 @@ class FastxScan(C.Structure):
 FASTX_IRREGULAR = 1
 
 
+class PassPlan(C.Structure):
+    _fields_ = [("n_passes", C.c_uint32), ("n_subtrees", C.c_uint32), ("root_bytes", C.c_uint64), ("slab_bytes", C.c_uint64),
+                ("index_bytes", C.c_uint64)]
+
+
+class Prior(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_tuples", C.c_uint64), ("read_off", C.c_void_p), ("user_bin", C.c_void_p),
+                ("count", C.c_void_p), ("key", C.c_void_p)]
+
+
+PASS_ROOT = 0xFFFFFFFF
+
+
 SIGNATURES = {
     "taxor_gpu_last_error": (C.c_char_p, []),
     "taxor_gpu_index_create": (C.c_int, [C.POINTER(HixfView), C.c_int, C.POINTER(_P)]),
     "taxor_gpu_index_destroy": (None, [_P]),
+    "taxor_index_plan_passes": (C.c_int, [C.POINTER(HixfView), C.c_uint64, C.POINTER(PassPlan), _P, _P]),
+    "taxor_gpu_index_create_paged": (C.c_int, [C.POINTER(HixfView), C.c_int, C.c_uint64, C.POINTER(_P)]),
+    "taxor_gpu_index_passes": (C.c_uint32, [_P]),
+    "taxor_gpu_index_load_pass": (C.c_int, [_P, C.POINTER(HixfView), C.c_uint32]),
+    "taxor_gpu_index_upload_wait_seconds": (C.c_double, [_P]),
+    "taxor_gpu_search_merge_prior": (C.c_int, [_P, C.POINTER(Prior), C.c_uint32]),
+    "taxor_gpu_results_keys": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_uint32))]),
     "taxor_gpu_index_build_hixf": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint32)]),
     "taxor_gpu_index_build_ixf_ex": (C.c_int, [_P, C.c_uint64, _P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(BuildStats)]),
     "taxor_gpu_index_build_hixf_ex": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, C.POINTER(BuildStats)]),

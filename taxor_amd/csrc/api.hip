@@ -67,6 +67,24 @@ struct taxor_gpu_index {
     // hipMalloc / hipFree of GB-sized blocks takes the driver anything between nothing and a second -- and released with the index
     void *build_ctx = nullptr;
     void (*build_ctx_free)(void *) = nullptr;
+    // paged index (taxor_gpu_index_create_paged): the root and at most two groups of subtrees are in the slab; d_binfo is the PASS's
+    // table (children that are not resident have id 0), d_binfo_full the whole hierarchy's
+    uint32_t n_passes = 0;                       // 0 = an ordinary index
+    std::vector<uint32_t> pass_of_ixf;           // TAXOR_PASS_ROOT for the root (and for an IXF no bin leads to)
+    std::vector<uint64_t> pass_data_bytes;       // fingerprint bytes of every group
+    uint64_t root_data_bytes = 0;
+    uint32_t *d_binfo_full = nullptr;
+    uint8_t *d_resident = nullptr;
+    int cur_pass = -1;                           // the group searches see, -1 = none yet
+    int up_group = -1;                           // the group the upload thread brings (or has brought) in
+    std::thread up_thread;
+    int up_rc = 0;
+    std::string up_err;
+    std::vector<uint8_t> up_select;              // per IXF: part of the upload in progress; upload_select points at it, or is null (= all)
+    const uint8_t *upload_select = nullptr;
+    double upload_wait_s = 0;                    // time load_pass spent waiting for uploads, summed
+    std::mutex searchers_mu;
+    std::vector<taxor_gpu_searcher *> searchers; // the index's searchers (lanes not listed): load_pass checks that none has a run in flight
 };
 
 struct SubBatch {
@@ -176,6 +194,8 @@ struct taxor_gpu_searcher {
     // pages while the other's bytes are on the wire -- the runtime serialises pageable copies process-wide; the helper's first
     // copy returned after both of the caller's, 350 us into a 390-us enqueue.)
     bool dev_results_stale = false;         // ... and not (yet) in the device-resident CSR that export_device / the communicator read
+    bool keep_keys = false;                 // searcher of a paged index: a call that goes through the lanes keeps its tuples' DFS keys (h_key)
+    std::vector<uint32_t> h_key;            // taxor_gpu_results_keys
 
     // timing
     std::vector<hipEvent_t> ev;
@@ -259,6 +279,7 @@ static int index_upload(taxor_gpu_index *idx, const taxor_hixf_view *v, void (*p
         const uint64_t bytes = idx->rows[i] * idx->h_ixf[i].stride;
         const uint64_t next = i + 1 < n ? idx->slab_off[i + 1] : idx->slab_bytes;
         if (!v->source && !v->ixf[i].data) continue;                     // left to fill_random / upload_bin / the builder
+        if (idx->upload_select && !idx->upload_select[i]) continue;      // paged index: not part of this upload
         const uint64_t step = v->source ? piece_bytes : (1ull << 30);
         for (uint64_t o = 0; o < bytes; o += step) {
             const uint64_t len = std::min(step, bytes - o);
@@ -391,7 +412,7 @@ static int index_upload(taxor_gpu_index *idx, const taxor_hixf_view *v, void (*p
 
 // upload = false: everything but the fingerprint bytes (the slab is allocated, its rows are left as they are) -- for a
 // replica that receives them over RCCL, or through a pipelined upload (comm.hip)
-static int index_create_impl(const taxor_hixf_view *v, int device, bool upload, taxor_gpu_index **out)
+static int index_create_impl(const taxor_hixf_view *v, int device, bool upload, taxor_gpu_index **out, uint64_t paged_budget = 0)
 {
     runtime_env_once();
     if (!v || !out || v->n_ixf == 0 || !v->ixf) return fail(TAXOR_E_ARG, "index_create: empty view");
@@ -559,6 +580,38 @@ static int index_create_impl(const taxor_hixf_view *v, int device, bool upload, 
         }
     }
 
+    if (paged_budget) {
+        // the plan's groups -> fixed places: the root first, even groups upwards from it, odd groups downwards from the tail pad; two
+        // neighbouring groups never overlap (slab = root + the largest pair), so group g + 1 uploads while group g is searched
+        taxor_pass_plan plan{};
+        idx->pass_of_ixf.resize(n);
+        std::vector<uint64_t> gbytes(n);
+        if (int rc = taxor_index_plan_passes(v, paged_budget, &plan, idx->pass_of_ixf.data(), gbytes.data())) {
+            delete idx;
+            return rc;
+        }
+        idx->n_passes = plan.n_passes;
+        idx->slab_bytes = plan.slab_bytes;
+        idx->pass_data_bytes.assign(plan.n_passes, 0);
+        const uint64_t root_end = round_up(idx->rows[0] * idx->h_ixf[0].stride, 4096);
+        std::vector<uint64_t> cur(plan.n_passes);
+        for (uint32_t g = 0; g < plan.n_passes; ++g) cur[g] = (g & 1u) ? plan.slab_bytes - 4096 - gbytes[g] : root_end;
+        idx->root_data_bytes = idx->rows[0] * idx->h_ixf[0].stride;
+        slab_off[0] = 0;
+        for (uint64_t i = 1; i < n; ++i) {
+            const uint32_t g = idx->pass_of_ixf[i];
+            const uint64_t b = round_up(idx->rows[i] * idx->h_ixf[i].stride, 4096);
+            if (g == TAXOR_PASS_ROOT) { slab_off[i] = 0; continue; }       // no bin leads to it: never searched, never uploaded
+            slab_off[i] = cur[g];
+            cur[g] += b;
+            idx->pass_data_bytes[g] += idx->rows[i] * idx->h_ixf[i].stride;
+            if (cur[g] + 4096 > plan.slab_bytes) {
+                delete idx;
+                return fail(TAXOR_E_INTERNAL, "index_create_paged: IXF %llu placed outside the slab", (unsigned long long)i);
+            }
+        }
+        idx->data_bytes = idx->root_data_bytes;
+    }
     hipError_t e = hipMalloc((void **)&idx->d_slab, idx->slab_bytes);
     if (e != hipSuccess) {
         delete idx;
@@ -567,6 +620,11 @@ static int index_create_impl(const taxor_hixf_view *v, int device, bool upload, 
     }
     for (uint64_t i = 0; i < n; ++i) idx->h_ixf[i].data = idx->d_slab + slab_off[i];
     idx->slab_off = slab_off;
+    if (paged_budget) {                          // the root alone; taxor_gpu_index_load_pass brings the groups
+        idx->up_select.assign(n, 0);
+        idx->up_select[0] = 1;
+        idx->upload_select = idx->up_select.data();
+    }
     if (upload)
         if (int rc = index_upload(idx, v, nullptr, nullptr)) {
             taxor_gpu_index_destroy(idx);
@@ -584,6 +642,21 @@ static int index_create_impl(const taxor_hixf_view *v, int device, bool upload, 
         taxor_gpu_index_destroy(idx);
         return fail(TAXOR_E_HIP, "index_create: table upload failed");
     }
+    if (paged_budget) {
+        std::vector<uint8_t> res(n, 0);
+        res[0] = 1;
+        ok = hipMalloc((void **)&idx->d_binfo_full, tb * sizeof(uint32_t)) == hipSuccess && hipMalloc((void **)&idx->d_resident, n) == hipSuccess &&
+             hipMemcpy(idx->d_binfo_full, binfo.data(), tb * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(idx->d_resident, res.data(), n, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) {
+            launch_binfo_pass(idx->d_binfo_full, idx->d_resident, idx->d_binfo, (uint32_t)tb, (uint32_t)n, nullptr);
+            ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+        }
+        if (!ok) {
+            taxor_gpu_index_destroy(idx);
+            return fail(TAXOR_E_HIP, "index_create_paged: residency tables failed");
+        }
+    }
     idx->h_ubin = std::move(ubin);
     idx->h_dfs = std::move(dfs);
     *out = idx;
@@ -594,6 +667,81 @@ extern "C" int taxor_gpu_index_create(const taxor_hixf_view *v, int device, taxo
 {
     return index_create_impl(v, device, true, out);
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// paged index ("Search beyond device memory"): every IXF has a fixed place in a slab of root + two groups;
+// which children the traversal may enter is decided by the pass's bin info table alone, so an IXF's descriptor never changes and a
+// stale child id could only ever lead into the slab
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int taxor_gpu_index_create_paged(const taxor_hixf_view *v, int device, uint64_t budget_bytes, taxor_gpu_index **out)
+{
+    if (!budget_bytes) return fail(TAXOR_E_ARG, "index_create_paged: the budget is 0");
+    return index_create_impl(v, device, true, out, budget_bytes);
+}
+
+extern "C" uint32_t taxor_gpu_index_passes(const taxor_gpu_index *idx) { return idx ? idx->n_passes : 0; }
+
+static void paged_select(taxor_gpu_index *idx, uint32_t group)
+{
+    for (size_t i = 0; i < idx->up_select.size(); ++i) idx->up_select[i] = idx->pass_of_ixf[i] == group;
+    idx->upload_select = idx->up_select.data();
+}
+
+extern "C" int taxor_gpu_index_load_pass(taxor_gpu_index *idx, const taxor_hixf_view *v, uint32_t pass)
+{
+    if (!idx || !v || v->n_ixf != idx->h_ixf.size()) return fail(TAXOR_E_ARG, "load_pass: view does not match the index");
+    if (!idx->n_passes) return fail(TAXOR_E_ARG, "load_pass: not a paged index (taxor_gpu_index_create_paged)");
+    if (pass >= idx->n_passes) return fail(TAXOR_E_ARG, "load_pass: pass %u of %u", pass, idx->n_passes);
+    if (pass != 0 && (int)pass != idx->cur_pass + 1)
+        return fail(TAXOR_E_ARG, "load_pass: out of order: pass %u asked for after pass %d (the next one, or 0 to start over)", pass, idx->cur_pass);
+    {
+        std::lock_guard<std::mutex> lk(idx->searchers_mu);
+        for (const taxor_gpu_searcher *s : idx->searchers)
+            if (s->ran && !s->synced)
+                return fail(TAXOR_E_ARG, "load_pass: a search of the pass before has not ended (taxor_gpu_search_batch_end comes first): its kernels may still read the "
+                                         "part of the slab the next upload writes");
+    }
+    HIP_TRY(hipSetDevice(idx->device));
+    const double t0 = now_s();
+    if (idx->up_thread.joinable()) idx->up_thread.join();
+    if (idx->up_rc) {
+        const int rc = idx->up_rc;
+        idx->up_rc = 0;
+        idx->up_group = -1;
+        return fail(rc, "load_pass: upload of group %u: %s", pass, idx->up_err.c_str());
+    }
+    if (idx->up_group != (int)pass) {            // the first pass, or a start over: nothing brought it in
+        paged_select(idx, pass);
+        if (int rc = index_upload(idx, v, nullptr, nullptr)) return rc;
+    }
+    idx->upload_wait_s += now_s() - t0;
+    idx->up_group = -1;
+    const size_t n = idx->h_ixf.size();
+    std::vector<uint8_t> res(n);
+    for (size_t i = 0; i < n; ++i) res[i] = i == 0 || idx->pass_of_ixf[i] == pass;
+    HIP_TRY(hipMemcpy(idx->d_resident, res.data(), n, hipMemcpyHostToDevice));
+    launch_binfo_pass(idx->d_binfo_full, idx->d_resident, idx->d_binfo, (uint32_t)idx->total_bins, (uint32_t)n, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    idx->cur_pass = (int)pass;
+    idx->data_bytes = idx->root_data_bytes + idx->pass_data_bytes[pass];
+    if (pass + 1 < idx->n_passes) {              // the next group, into the half the pass before this one used
+        paged_select(idx, pass + 1);
+        idx->up_group = (int)pass + 1;
+        idx->up_thread = std::thread([idx, v] {
+            int rc = hipSetDevice(idx->device) == hipSuccess ? 0 : fail(TAXOR_E_HIP, "hipSetDevice failed");
+            if (!rc) rc = index_upload(idx, v, nullptr, nullptr);
+            if (rc) {
+                idx->up_err = taxor_gpu_last_error();      // (this thread's message; the join orders it before load_pass reads it)
+                idx->up_rc = rc;
+            }
+        });
+    }
+    return TAXOR_OK;
+}
+
+// seconds taxor_gpu_index_load_pass has spent waiting for uploads so far (the CLI's figures)
+extern "C" double taxor_gpu_index_upload_wait_seconds(const taxor_gpu_index *idx) { return idx ? idx->upload_wait_s : 0.0; }
 
 // library-internal (comm.hip): an index on `device` with every table in place and an allocated but unwritten slab
 extern "C" __attribute__((visibility("hidden"))) int taxor_index_create_empty(const taxor_hixf_view *v, int device, taxor_gpu_index **out)
@@ -635,7 +783,10 @@ extern "C" __attribute__((visibility("hidden"))) void taxor_index_set_build_ctx(
 extern "C" void taxor_gpu_index_destroy(taxor_gpu_index *idx)
 {
     if (!idx) return;
+    if (idx->up_thread.joinable()) idx->up_thread.join();
     (void)hipSetDevice(idx->device);
+    if (idx->d_binfo_full) (void)hipFree(idx->d_binfo_full);
+    if (idx->d_resident) (void)hipFree(idx->d_resident);
     if (idx->build_ctx && idx->build_ctx_free) idx->build_ctx_free(idx->build_ctx);
     idx->build_ctx = nullptr;
     if (idx->d_slab) (void)hipFree(idx->d_slab);
@@ -682,7 +833,11 @@ extern "C" __attribute__((visibility("hidden"))) uint32_t taxor_index_arith(cons
     return idx && !idx->h_ixf.empty() ? idx->h_ixf[0].arith : 0u;
 }
 
-extern "C" uint64_t taxor_gpu_index_data_bytes(const taxor_gpu_index *idx) { return idx ? idx->data_bytes : 0; }
+extern "C" uint64_t taxor_gpu_index_data_bytes(const taxor_gpu_index *idx) { return idx ? idx->data_bytes : 0; }   // paged: the root + the loaded group
+extern "C" __attribute__((visibility("hidden"))) int taxor_index_upload_wanted(const taxor_gpu_index *idx, uint64_t ixf)   // relayout.hip
+{
+    return !idx->upload_select || idx->upload_select[ixf];
+}
 extern "C" uint64_t taxor_gpu_index_ixf_seed(const taxor_gpu_index *idx, uint64_t ixf)
 {
     return idx && ixf < idx->h_ixf.size() ? idx->h_ixf[ixf].seed : 0;
@@ -915,6 +1070,11 @@ static int searcher_create_impl(taxor_gpu_index *idx, const taxor_gpu_search_par
             s->grid_query_small[l] = query_grid_small(idx->device, s->lds_query_small[l]);
         }
     }
+    s->keep_keys = idx->n_passes > 0;
+    if (!lane_stream) {
+        std::lock_guard<std::mutex> lk(idx->searchers_mu);
+        idx->searchers.push_back(s);
+    }
     *out = s;
     return TAXOR_OK;
 }
@@ -922,6 +1082,11 @@ static int searcher_create_impl(taxor_gpu_index *idx, const taxor_gpu_search_par
 extern "C" void taxor_gpu_searcher_destroy(taxor_gpu_searcher *s)
 {
     if (!s) return;
+    {
+        std::lock_guard<std::mutex> lk(s->idx->searchers_mu);
+        auto &v = s->idx->searchers;
+        v.erase(std::remove(v.begin(), v.end(), s), v.end());
+    }
     (void)hipSetDevice(s->idx->device);
     for (auto &L : s->lanes) {
         if (L.c) { (void)hipStreamSynchronize(L.c->st); taxor_gpu_searcher_destroy(L.c); }
@@ -1995,6 +2160,14 @@ int small_harvest_one(taxor_gpu_searcher *s)
     memcpy(s->h_nh.data() + pc.first, nh, pc.n * 4);
     s->h_ub.insert(s->h_ub.end(), ub, ub + nt);
     s->h_cnt.insert(s->h_cnt.end(), cnt, cnt + nt);
+    if (s->keep_keys) {
+        // the piece's keys are in the lane's scratch (either pipeline's d_out_key); the one-block finalize leaves those of a read of up
+        // to 64 tuples in arrival order -- it moves user bins and counts only -- so every read's keys are put in order here
+        const size_t k0 = s->h_key.size();
+        s->h_key.resize(k0 + nt);
+        if (nt) HIP_TRY(hipMemcpy(s->h_key.data() + k0, L.c->d_out_key.p, nt * 4, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < pc.n; ++i) std::sort(s->h_key.begin() + k0 + ro[i], s->h_key.begin() + k0 + ro[i + 1]);
+    }
     s->small_tbase += nt;
     ++s->small_harvested;
     return 0;
@@ -2016,6 +2189,7 @@ int small_begin(taxor_gpu_searcher *s, const char *bases, const uint64_t *offset
     s->h_nh.resize(n_reads);
     s->h_ub.clear();
     s->h_cnt.clear();
+    s->h_key.clear();
     s->h_read_off[0] = 0;
     s->stats = taxor_gpu_run_stats{};
     // Pieces.  A blocking copy of pageable bases costs ~35 us beyond its bytes (the runtime page-locks the caller's pages around it)
@@ -2322,6 +2496,144 @@ extern "C" int taxor_gpu_batch_fetch(taxor_gpu_searcher *s, taxor_gpu_results *o
     out->user_bin = s->h_ub.data();
     out->count = s->h_cnt.data();
     out->n_hashes = s->h_nh.data();
+    return TAXOR_OK;
+}
+
+extern "C" int taxor_gpu_results_keys(taxor_gpu_searcher *s, const uint32_t **key)
+{
+    if (!s || !key) return fail(TAXOR_E_ARG, "results_keys: null argument");
+    if (!s->synced)
+        if (int rc = taxor_gpu_batch_sync(s)) return rc;
+    const uint64_t nt = s->h_ctr.tuple_total;
+    if (s->small_active) {
+        if (!s->keep_keys) return fail(TAXOR_E_ARG, "results_keys: a call of a few thousand reads keeps its keys only on a searcher of a paged index");
+        if (s->h_key.size() != nt) return fail(TAXOR_E_INTERNAL, "results_keys: %llu keys for %llu tuples", (unsigned long long)s->h_key.size(), (unsigned long long)nt);
+    } else {
+        HIP_TRY(hipSetDevice(s->idx->device));
+        s->h_key.resize(nt);
+        if (nt) HIP_TRY(hipMemcpyAsync(s->h_key.data(), s->d_out_key.p, nt * 4, hipMemcpyDeviceToHost, s->st));
+        HIP_TRY(hipStreamSynchronize(s->st));
+    }
+    *key = s->h_key.data();
+    return TAXOR_OK;
+}
+
+extern "C" int taxor_gpu_search_merge_prior(taxor_gpu_searcher *s, const taxor_gpu_prior *prior, uint32_t n_prior)
+{
+    if (!s || (n_prior && !prior)) return fail(TAXOR_E_ARG, "merge_prior: null argument");
+    if (!s->ran) return fail(TAXOR_E_ARG, "merge_prior: no batch to merge into");
+    if (!s->synced)
+        if (int rc = taxor_gpu_batch_sync(s)) return rc;
+    if (n_prior == 0) return TAXOR_OK;
+    if (n_prior >= 4096) return fail(TAXOR_E_ARG, "merge_prior: %u lists", n_prior);
+    const uint64_t nr = s->n_reads;
+    if (nr >= (1ull << 32)) return fail(TAXOR_E_ARG, "merge_prior: too many reads");
+    uint64_t total = s->h_ctr.tuple_total;
+    for (uint32_t j = 0; j < n_prior; ++j) {     // what the kernels rely on: offsets that stay inside the arrays, keys ascending within a read
+        const taxor_gpu_prior &p = prior[j];
+        if (p.n_reads != nr || !p.read_off || (p.n_tuples && (!p.user_bin || !p.count || !p.key)))
+            return fail(TAXOR_E_ARG, "merge_prior: list %u holds %llu reads, the batch %llu (or a null array)", j, (unsigned long long)p.n_reads, (unsigned long long)nr);
+        if (p.read_off[0] != 0 || p.read_off[nr] != p.n_tuples) return fail(TAXOR_E_ARG, "merge_prior: list %u: offsets do not span its %llu tuples", j, (unsigned long long)p.n_tuples);
+        for (uint64_t r = 0; r < nr; ++r) {
+            if (p.read_off[r + 1] < p.read_off[r] || p.read_off[r + 1] > p.n_tuples) return fail(TAXOR_E_ARG, "merge_prior: list %u: offsets not monotone at read %llu", j, (unsigned long long)r);
+            for (uint64_t i = p.read_off[r] + 1; i < p.read_off[r + 1]; ++i)
+                if (p.key[i] <= p.key[i - 1]) return fail(TAXOR_E_ARG, "merge_prior: list %u: keys of read %llu not ascending", j, (unsigned long long)r);
+        }
+        total += p.n_tuples;
+    }
+    HIP_TRY(hipSetDevice(s->idx->device));
+    if (s->small_active) {                       // the lanes left the call's results on the host: CSR, keys and read lengths go to the device
+        if (!s->keep_keys) return fail(TAXOR_E_ARG, "merge_prior: a call of a few thousand reads keeps its keys only on a searcher of a paged index");
+        const uint64_t nt = s->h_ctr.tuple_total;
+        if (s->h_key.size() != nt) return fail(TAXOR_E_INTERNAL, "merge_prior: %llu keys for %llu tuples", (unsigned long long)s->h_key.size(), (unsigned long long)nt);
+        s->dev_results_stale = true;
+        if (int rc = small_device_results(s)) return rc;
+        if (reserve(s->d_out_key, nt + 1)) return TAXOR_E_HIP;
+        if (nt) HIP_TRY(hipMemcpy(s->d_out_key.p, s->h_key.data(), nt * 4, hipMemcpyHostToDevice));
+        const uint32_t *unused;
+        if (int rc = taxor_searcher_device_read_lengths(s, &unused)) return rc;
+    }
+    const uint32_t nl = n_prior + 1;
+    std::vector<DeviceBuf<uint64_t>> d_off(n_prior);
+    std::vector<DeviceBuf<int64_t>> d_ub(n_prior);
+    std::vector<DeviceBuf<uint32_t>> d_cnt(n_prior), d_key(n_prior);
+    std::vector<MergeList> lists(nl);
+    for (uint32_t j = 0; j < n_prior; ++j) {
+        const taxor_gpu_prior &p = prior[j];
+        HIP_TRY(d_off[j].alloc(nr + 1));
+        HIP_TRY(d_ub[j].alloc(p.n_tuples + 1));
+        HIP_TRY(d_cnt[j].alloc(p.n_tuples + 1));
+        HIP_TRY(d_key[j].alloc(p.n_tuples + 1));
+        HIP_TRY(hipMemcpy(d_off[j].p, p.read_off, (nr + 1) * 8, hipMemcpyHostToDevice));
+        if (p.n_tuples) {
+            HIP_TRY(hipMemcpy(d_ub[j].p, p.user_bin, p.n_tuples * 8, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_cnt[j].p, p.count, p.n_tuples * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_key[j].p, p.key, p.n_tuples * 4, hipMemcpyHostToDevice));
+        }
+        lists[j] = MergeList{d_off[j].p, d_ub[j].p, d_cnt[j].p, d_key[j].p};
+    }
+    lists[n_prior] = MergeList{s->d_read_off.p, s->d_out_ub.p, s->d_out_cnt.p, s->d_out_key.p};   // the last pass stands last, as it ran last
+    DeviceBuf<MergeList> d_lists;
+    DeviceBuf<uint32_t> sk, sc, n_out, flag;
+    DeviceBuf<int64_t> su;
+    DeviceBuf<uint64_t> out_off;
+    HIP_TRY(d_lists.alloc(nl));
+    HIP_TRY(sk.alloc(total + 1));
+    HIP_TRY(sc.alloc(total + 1));
+    HIP_TRY(su.alloc(total + 1));
+    HIP_TRY(n_out.alloc(nr + 1));
+    HIP_TRY(flag.alloc(1));
+    HIP_TRY(out_off.alloc(std::max<uint64_t>(nr + 1, s->d_read_off.cap)));
+    HIP_TRY(hipMemcpy(d_lists.p, lists.data(), nl * sizeof(MergeList), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(flag.p, 0, 4, s->st));
+    MergeArgs a{};
+    a.lists = d_lists.p;
+    a.n_lists = nl;
+    a.n_reads = (uint32_t)nr;
+    a.s_key = sk.p;
+    a.s_cnt = sc.p;
+    a.s_ub = su.p;
+    a.scratch_cap = total;
+    a.n_out = n_out.p;
+    a.out_off = out_off.p;
+    a.flag = flag.p;
+    uint64_t merged = 0;
+    uint32_t f = 0;
+    if (nr) {
+        launch_merge_place(a, s->st);
+        launch_merge_count(a, s->st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&merged, out_off.p + nr, 8, hipMemcpyDeviceToHost, s->st));
+    } else
+        HIP_TRY(hipMemsetAsync(out_off.p, 0, 8, s->st));
+    HIP_TRY(hipMemcpyAsync(&f, flag.p, 4, hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipStreamSynchronize(s->st));
+    if (merged > total) f |= 2u;
+    DeviceBuf<int64_t> o_ub;
+    DeviceBuf<uint32_t> o_cnt, o_key;
+    if (!f) {
+        HIP_TRY(o_ub.alloc(std::max<uint64_t>(merged + 1, s->d_out_ub.cap)));
+        HIP_TRY(o_cnt.alloc(std::max<uint64_t>(merged + 1, s->d_out_cnt.cap)));
+        HIP_TRY(o_key.alloc(std::max<uint64_t>(merged + 1, s->d_out_key.cap)));
+        a.out_ub = o_ub.p;
+        a.out_cnt = o_cnt.p;
+        a.out_key = o_key.p;
+        a.out_cap = merged;
+        if (nr) launch_merge_write(a, s->st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&f, flag.p, 4, hipMemcpyDeviceToHost, s->st));
+        HIP_TRY(hipStreamSynchronize(s->st));
+    }
+    if (f & 2u) return fail(TAXOR_E_INTERNAL, "merge_prior: a tuple fell outside its array");
+    if (f & 1u) return fail(TAXOR_E_INTERNAL, "merge_prior: one bin of a read was counted differently in two passes");
+    s->d_read_off = std::move(out_off);
+    s->d_out_ub = std::move(o_ub);
+    s->d_out_cnt = std::move(o_cnt);
+    s->d_out_key = std::move(o_key);
+    s->h_ctr.tuple_total = merged;
+    s->stats.n_tuples = merged;
+    s->small_active = false;                     // the results are the device's now: fetch, export and the feed read them there
+    s->dev_results_stale = false;
     return TAXOR_OK;
 }
 

@@ -5,6 +5,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdarg>
+#include <cstdio>
 #include <cstring>
 #include <queue>
 #include <set>
@@ -514,6 +516,123 @@ int taxor_build_layout(const uint64_t *counts, uint64_t n, uint64_t t_max, taxor
 void taxor_layout_free(taxor_layout *l)
 {
     delete reinterpret_cast<LayoutOwned *>(l);   // pub is the first member
+}
+
+// ---- taxor_index_plan_passes: which IXFs a search of an index larger than the device holds together (DESIGN.md section 9,
+// "Search beyond device memory").  Host only.
+extern "C" __attribute__((visibility("hidden"))) void taxor_set_last_error(const char *msg);
+
+namespace {
+
+__attribute__((format(printf, 2, 3))) int plan_fail(int code, const char *fmt, ...)
+{
+    char buf[768];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    taxor_set_last_error(buf);
+    return code;
+}
+
+inline uint64_t slab_round(uint64_t x) { return (x + 4095) / 4096 * 4096; }
+
+} // namespace
+
+int taxor_index_plan_passes(const taxor_hixf_view *v, uint64_t budget_bytes, taxor_pass_plan *plan, uint32_t *pass_of_ixf, uint64_t *pass_bytes)
+{
+    if (!v || !plan || v->n_ixf == 0 || !v->ixf || v->n_ixf >= (1u << 30)) return plan_fail(TAXOR_E_ARG, "plan_passes: empty view");
+    const uint64_t n = v->n_ixf;
+    std::vector<uint64_t> bytes(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        const taxor_ixf_view &f = v->ixf[i];
+        if (f.bins == 0 || f.stride < f.bins || f.stride % 64 != 0 || f.seg_len == 0 || !f.next_ixf || !f.fname_idx || 3 * f.seg_len >= (1ull << 32) ||
+            f.stride > (1u << 20))
+            return plan_fail(TAXOR_E_ARG, "plan_passes: IXF %llu malformed (bins=%llu stride=%llu seg_len=%llu)", (unsigned long long)i,
+                             (unsigned long long)f.bins, (unsigned long long)f.stride, (unsigned long long)f.seg_len);
+        bytes[i] = slab_round(3 * f.seg_len * f.stride);
+    }
+    // the subtrees: one per merged bin of the root, in root-bin order, each with everything below it
+    struct Subtree { uint64_t root_bin, child, bytes; };
+    std::vector<Subtree> sub;
+    std::vector<uint32_t> owner(n, TAXOR_PASS_ROOT);      // subtree index first, pass number at the end
+    std::vector<uint8_t> seen(n, 0);
+    seen[0] = 1;
+    struct Edge { uint64_t parent, bin; int64_t child; };
+    std::vector<Edge> stack;
+    for (uint64_t b = 0; b < v->ixf[0].bins; ++b) {
+        if (v->ixf[0].fname_idx[b] >= 0) continue;
+        Subtree st{b, (uint64_t)v->ixf[0].next_ixf[b], 0};
+        stack.assign(1, Edge{0, b, v->ixf[0].next_ixf[b]});
+        while (!stack.empty()) {
+            const Edge e = stack.back();
+            stack.pop_back();
+            if (e.child <= 0 || (uint64_t)e.child >= n)
+                return plan_fail(TAXOR_E_ARG, "plan_passes: IXF %llu bin %llu: bad child %lld", (unsigned long long)e.parent, (unsigned long long)e.bin, (long long)e.child);
+            const uint64_t c = (uint64_t)e.child;
+            if (seen[c]) return plan_fail(TAXOR_E_ARG, "plan_passes: IXF %llu is referenced twice (not a tree)", (unsigned long long)c);
+            seen[c] = 1;
+            owner[c] = (uint32_t)sub.size();
+            st.bytes += bytes[c];
+            const taxor_ixf_view &f = v->ixf[c];
+            for (uint64_t x = 0; x < f.bins; ++x)
+                if (f.fname_idx[x] < 0) stack.push_back(Edge{c, x, f.next_ixf[x]});
+        }
+        sub.push_back(st);
+    }
+    const uint64_t root_bytes = bytes[0] + 4096;       // the slab's tail pad is the root's: it is resident in every pass
+    uint64_t total = 0;
+    for (const Subtree &s : sub) total += s.bytes;
+    std::vector<uint64_t> gbytes;
+    std::vector<uint32_t> gof(sub.size(), 0);
+    if (root_bytes > budget_bytes)
+        return plan_fail(TAXOR_E_ARG, "search: the root IXF alone needs %llu bytes on the device, the index budget is %llu (root-exceeds-budget): it stays resident in every pass, "
+                                      "so this index cannot be searched under this budget", (unsigned long long)root_bytes, (unsigned long long)budget_bytes);
+    const uint64_t avail = budget_bytes - root_bytes;
+    if (sub.empty() || total <= avail) gbytes.push_back(total);
+    else {
+        // greedy in root-bin order.  Two groups are on the device at a time -- one searched, the next one uploading -- so every pair of
+        // neighbours has to fit beside the root; a group is closed when the next subtree would take it past half of what the root
+        // leaves (a subtree larger than that is a group of its own) or past what the group before it leaves
+        const uint64_t half = avail / 2;
+        uint64_t cur = 0, prev = 0;
+        bool open = false;
+        for (size_t j = 0; j < sub.size(); ++j) {
+            const Subtree &s = sub[j];
+            if (s.bytes > avail)
+                return plan_fail(TAXOR_E_ARG, "search: the subtree under root bin %llu (child IXF %llu) needs %llu bytes, the root leaves %llu of the index budget of %llu "
+                                              "(subtree-exceeds-budget); a smaller --tmax at build time gives smaller subtrees",
+                                 (unsigned long long)s.root_bin, (unsigned long long)s.child, (unsigned long long)s.bytes, (unsigned long long)avail, (unsigned long long)budget_bytes);
+            if (open && (cur + s.bytes > half || prev + cur + s.bytes > avail)) {
+                gbytes.push_back(cur);
+                prev = cur;
+                cur = 0;
+                open = false;
+            }
+            if (prev + cur + s.bytes > avail)
+                return plan_fail(TAXOR_E_ARG, "search: the subtree under root bin %llu (child IXF %llu) needs %llu bytes, the root and the group before it (%llu bytes, on the device "
+                                              "while this one uploads) leave %llu of the index budget of %llu (subtree-exceeds-budget; this is the greedy packing's refusal, not proof that no grouping "
+                                              "exists: a somewhat larger budget is searched); a smaller --tmax at build time gives smaller subtrees",
+                                 (unsigned long long)s.root_bin, (unsigned long long)s.child, (unsigned long long)s.bytes, (unsigned long long)prev,
+                                 (unsigned long long)(avail - prev), (unsigned long long)budget_bytes);
+            cur += s.bytes;
+            open = true;
+            gof[j] = (uint32_t)gbytes.size();
+        }
+        gbytes.push_back(cur);
+    }
+    uint64_t pair = 0;
+    for (size_t g = 0; g < gbytes.size(); ++g) pair = std::max(pair, gbytes[g] + (g + 1 < gbytes.size() ? gbytes[g + 1] : 0));
+    plan->n_passes = (uint32_t)gbytes.size();
+    plan->n_subtrees = (uint32_t)sub.size();
+    plan->root_bytes = root_bytes;
+    plan->slab_bytes = root_bytes + pair;
+    plan->index_bytes = root_bytes + total;
+    if (pass_of_ixf)
+        for (uint64_t i = 0; i < n; ++i) pass_of_ixf[i] = owner[i] == TAXOR_PASS_ROOT ? TAXOR_PASS_ROOT : gof[owner[i]];   // (an IXF no bin leads to: never searched, never uploaded)
+    if (pass_bytes)
+        for (size_t g = 0; g < gbytes.size(); ++g) pass_bytes[g] = gbytes[g];
+    return TAXOR_OK;
 }
 
 } // extern "C"

@@ -219,4 +219,30 @@ uint64_t launch_gather_ceiling(const uint8_t *data, uint64_t rows, uint32_t stri
 void launch_scatter_column(uint8_t *data, uint64_t stride, uint64_t bin, const uint8_t *col, uint64_t rows,
                            hipStream_t st);
 
+// the pass's bin info table of a paged index: binfo[i] = full[i] with the child id of a merged bin cleared when resident[child] == 0
+void launch_binfo_pass(const uint32_t *full, const uint8_t *resident, uint32_t *binfo, uint32_t n_bins, uint32_t n_ixf, hipStream_t st);
+
+// merge of per-read result lists sorted by DFS key (taxor_gpu_search_merge_prior); all pointers are device pointers
+struct MergeList {
+    const uint64_t *read_off;   // [n_reads + 1]
+    const int64_t *ub;
+    const uint32_t *cnt, *key;
+};
+struct MergeArgs {
+    const MergeList *lists;
+    uint32_t n_lists, n_reads;
+    uint32_t *s_key, *s_cnt;    // scratch: the merge with duplicates, scratch_cap = sum of the lists' tuples
+    int64_t *s_ub;
+    uint64_t scratch_cap;
+    uint32_t *n_out;            // [n_reads] tuples kept per read
+    uint64_t *out_off;          // [n_reads + 1]
+    int64_t *out_ub;
+    uint32_t *out_cnt, *out_key;
+    uint64_t out_cap;
+    uint32_t *flag;             // bit 0: one key with two counts; bit 1: an entry outside its array (internal)
+};
+void launch_merge_place(const MergeArgs &a, hipStream_t st);
+void launch_merge_count(const MergeArgs &a, hipStream_t st);   // n_out and out_off
+void launch_merge_write(const MergeArgs &a, hipStream_t st);
+
 } // namespace taxor

@@ -1570,7 +1570,7 @@ __global__ __launch_bounds__(BS) void k_query_level(const QueryArgs a)
                 info = sInfo[b];
                 if (info & BINFO_MERGED) {
                     sum = sC[b];                                   // merged bins are runs of their own
-                    push_child = (uint64_t)sum >= thr;             // :321
+                    push_child = (uint64_t)sum >= thr && (info & 0x3FFFFFFFu) != 0u;   // :321; child id 0 = the child is not on the device in this pass of a paged index (api.hip: the root is nobody's child)
                 } else if (info & BINFO_END) {
                     int bb = (int)b;
                     sum = sC[bb];
@@ -2229,6 +2229,156 @@ void launch_scatter_column(uint8_t *data, uint64_t stride, uint64_t bin, const u
     uint64_t grid = (rows + BLK - 1) / BLK;
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(k_scatter_column, dim3((uint32_t)grid), dim3(BLK), 0, st, data, stride, bin, col, rows);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// paged index (api.hip, taxor_gpu_index_load_pass): the pass's copy of the bin info table -- a merged bin whose child IXF is not
+// resident keeps its flags and loses its child id, which the traversal reads as "nothing to enqueue"
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_binfo_pass(const uint32_t *__restrict__ full, const uint8_t *__restrict__ resident, uint32_t *__restrict__ binfo, uint32_t n_bins,
+                                                    uint32_t n_ixf)
+{
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_bins; i += gridDim.x * 256u) {
+        uint32_t info = full[i];
+        if (info & BINFO_MERGED) {
+            const uint32_t ch = info & 0x3FFFFFFFu;
+            if (ch >= n_ixf || !resident[ch]) info &= ~0x3FFFFFFFu;
+        }
+        binfo[i] = info;
+    }
+}
+
+void launch_binfo_pass(const uint32_t *full, const uint8_t *resident, uint32_t *binfo, uint32_t n_bins, uint32_t n_ixf, hipStream_t st)
+{
+    if (!n_bins) return;
+    hipLaunchKernelGGL(k_binfo_pass, dim3(std::min<uint32_t>(4096u, (n_bins + 255u) / 256u)), dim3(256), 0, st, full, resident, binfo, n_bins, n_ixf);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// merge of the passes' result lists (taxor_gpu_search_merge_prior): per read, n_lists lists sorted by DFS key -> one list, a key
+// that several lists hold kept once.  One wavefront per read, every list taken 64 entries at a time, whatever its length.
+//   k_merge_place : entry i of list l goes to slot  i + sum over the other lists m of #{keys of m below it}  (m < l: below or equal, so
+//                   equal keys stand in list order) of the read's stretch of the scratch -- the merge WITH duplicates; a read's stretch
+//                   starts at the sum of the lists' offsets, so no scan is needed for it
+//   k_merge_emit  : over the stretch 64 at a time: an entry is kept unless its predecessor has its key (then the counts must agree);
+//                   <false> counts what is kept, <true> writes it at the read's offset (k_merge_scan in between)
+// ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t merge_count_below(const uint32_t *__restrict__ k, uint32_t n, uint32_t key, bool or_equal)
+{
+    uint32_t lo = 0, hi = n;                      // first position whose key is not below (or equal to) `key`
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const uint32_t x = k[mid];
+        if (x < key || (or_equal && x == key)) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_merge_place(const MergeArgs a)
+{
+    const uint32_t l = lane_id();
+    for (uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6; r < a.n_reads; r += gridDim.x * 4u) {
+        uint64_t base = 0;
+        for (uint32_t m = 0; m < a.n_lists; ++m) base += a.lists[m].read_off[r];
+        for (uint32_t li = 0; li < a.n_lists; ++li) {
+            const MergeList L = a.lists[li];
+            const uint64_t lo = L.read_off[r];
+            const uint32_t n = (uint32_t)(L.read_off[r + 1] - lo);
+            for (uint32_t i = l; i < n; i += 64u) {
+                const uint32_t key = L.key[lo + i];
+                uint64_t rank = i;
+                for (uint32_t m = 0; m < a.n_lists; ++m) {
+                    if (m == li) continue;
+                    const MergeList M = a.lists[m];
+                    const uint64_t mlo = M.read_off[r];
+                    rank += merge_count_below(M.key + mlo, (uint32_t)(M.read_off[r + 1] - mlo), key, m < li);
+                }
+                const uint64_t o = base + rank;
+                if (o < a.scratch_cap) { a.s_key[o] = key; a.s_ub[o] = L.ub[lo + i]; a.s_cnt[o] = L.cnt[lo + i]; }
+                else atomicOr(a.flag, 2u);
+            }
+        }
+    }
+}
+
+template <bool WRITE> __global__ __launch_bounds__(256) void k_merge_emit(const MergeArgs a)
+{
+    const uint32_t l = lane_id();
+    for (uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6; r < a.n_reads; r += gridDim.x * 4u) {
+        uint64_t base = 0, total = 0;
+        for (uint32_t m = 0; m < a.n_lists; ++m) {
+            const uint64_t lo = a.lists[m].read_off[r];
+            base += lo;
+            total += a.lists[m].read_off[r + 1] - lo;
+        }
+        if (base + total > a.scratch_cap) { if (l == 0) atomicOr(a.flag, 2u); total = 0; }
+        const uint64_t out0 = WRITE ? a.out_off[r] : 0ull;
+        uint32_t kept = 0;
+        for (uint64_t i0 = 0; i0 < total; i0 += 64u) {                 // wave-uniform bounds: the ballot below is taken by all lanes
+            const uint64_t i = i0 + l;
+            bool keep = false;
+            uint32_t key = 0, cnt = 0;
+            if (i < total) {
+                key = a.s_key[base + i];
+                cnt = a.s_cnt[base + i];
+                keep = i == 0 || a.s_key[base + i - 1] != key;
+                if (!keep && a.s_cnt[base + i - 1] != cnt) atomicOr(a.flag, 1u);
+            }
+            const unsigned long long mask = __ballot(keep);
+            if (WRITE && keep) {
+                const uint64_t o = out0 + kept + (uint32_t)__popcll(mask & ((1ull << l) - 1ull));
+                if (o < a.out_cap) { a.out_key[o] = key; a.out_cnt[o] = cnt; a.out_ub[o] = a.s_ub[base + i]; }
+                else atomicOr(a.flag, 2u);
+            }
+            kept += (uint32_t)__popcll(mask);
+        }
+        if (!WRITE && l == 0) a.n_out[r] = kept;
+    }
+}
+
+// exclusive scan of n_out -> out_off[0 .. n_reads], one block (the pattern of k_scan_totals: wave scans, a carry between rounds)
+__global__ __launch_bounds__(1024) void k_merge_scan(const MergeArgs a)
+{
+    __shared__ uint64_t sW[16];
+    __shared__ uint64_t sCarry;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) sCarry = 0;
+    for (uint32_t r0 = 0; r0 < a.n_reads; r0 += 1024u) {
+        __syncthreads();
+        const uint32_t r = r0 + tid;
+        const uint64_t v = r < a.n_reads ? a.n_out[r] : 0u;
+        const uint64_t incl = wave_incl_add(v);
+        if (lane_id() == 63) sW[tid >> 6] = incl;
+        __syncthreads();
+        uint64_t off = sCarry, tot = 0;
+        for (uint32_t w = 0; w < 16; ++w) {
+            const uint64_t x = sW[w];
+            if (w < (tid >> 6)) off += x;
+            tot += x;
+        }
+        if (r < a.n_reads) a.out_off[r] = off + incl - v;
+        __syncthreads();
+        if (tid == 0) sCarry += tot;
+    }
+    __syncthreads();
+    if (tid == 0) a.out_off[a.n_reads] = sCarry;
+}
+
+static int merge_grid(uint32_t n_reads) { return (int)std::max<uint32_t>(1u, std::min<uint32_t>(4096u, (n_reads + 3u) / 4u)); }
+
+void launch_merge_place(const MergeArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_merge_place, dim3(merge_grid(a.n_reads)), dim3(256), 0, st, a);
+}
+void launch_merge_count(const MergeArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_merge_emit<false>, dim3(merge_grid(a.n_reads)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_merge_scan, dim3(1), dim3(1024), 0, st, a);
+}
+void launch_merge_write(const MergeArgs &a, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_merge_emit<true>, dim3(merge_grid(a.n_reads)), dim3(256), 0, st, a);
 }
 
 } // namespace taxor

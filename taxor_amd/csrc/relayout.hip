@@ -29,6 +29,7 @@
 #include <thread>
 #include <vector>
 
+extern "C" __attribute__((visibility("hidden"))) int taxor_index_upload_wanted(const taxor_gpu_index *idx, uint64_t ixf);   // api.hip: 0 = a paged index leaves this IXF out of the upload in progress
 extern "C" __attribute__((visibility("hidden"))) int taxor_index_ixf_info(taxor_gpu_index *idx, uint64_t ixf, uint8_t **data, uint64_t *stride, uint64_t *seg_len,
                                                                           uint64_t *bins, int *device);
 
@@ -159,6 +160,7 @@ extern "C" __attribute__((visibility("hidden"))) int taxor_index_upload_relayout
         x.pitch = kind == IXF_KIND_BIT_SLICED ? x.groups * 64 : ixf_src_pitch(v->ixf_layout, v->ixf[i].src_stride, x.stride, x.bins);
         if (x.pitch < x.bins) return fail(TAXOR_E_ARG, "index upload: IXF " + std::to_string(i) + ": source pitch " + std::to_string(x.pitch) + " below its " + std::to_string(x.bins) + " bins");
         if (!v->source && !v->ixf[i].data) continue;
+        if (!taxor_index_upload_wanted(idx, i)) continue;           // paged index: not part of this upload
         if (kind == IXF_KIND_BIN_MAJOR) {
             const uint64_t nr_max = std::max<uint64_t>(128, (piece_bytes / 128) & ~(uint64_t)127);       // rows per strip: 128 columns of them fill a piece
             for (uint64_t b0 = 0; b0 < x.bins; b0 += 128)

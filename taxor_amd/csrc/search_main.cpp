@@ -175,6 +175,7 @@ struct Config {                              // taxor_search_configuration.hpp:8
     bool layout_given = false;  // --ixf-layout: how the file stores each IXF's fingerprints (ixf_layout.h); transposed on the device at load
     uint32_t ixf_layout = 0;
     uint64_t group_reads = 0;   // reads per GPU batch, made of queued chunks (0: 131072, or --batch-reads when that is given)
+    uint64_t index_budget_mib = 0;   // hidden --device-index-budget: fingerprint bytes on the device at a time; the index is searched in resident passes
     std::string gather;         // several devices: "rccl" | "host" (taxor_gpu_comm transports) | "none" (independent workers, each
                                 // fetching its own results); empty = rccl when the devices are distinct, host when one repeats
 };
@@ -1296,6 +1297,11 @@ int main(int argc, char **argv)
             profile_mode = true;
         }
         else if (k == "--batch-reads") cfg.batch_reads = strtoull(val().c_str(), nullptr, 10);
+        else if (k == "--device-index-budget") {
+            const long long n = atoll(val().c_str());
+            if (n < 1 || n > (1ll << 24)) die("Validation failed for option --device-index-budget: Value not in range [1,16777216].");
+            cfg.index_budget_mib = (uint64_t)n;
+        }
         else if (k == "--expect") cfg.expect_file = val();
         else if (k == "--sequential") cfg.sequential = true;
         else if (k == "--device-parse") cfg.device_parse = true;
@@ -1313,7 +1319,18 @@ int main(int argc, char **argv)
             cfg.gather = val();
             if (cfg.gather != "rccl" && cfg.gather != "host" && cfg.gather != "none") die("Validation failed for option --gather: Value not in {rccl, host, none}.");
         }
-        else if (k == "-h" || k == "--help" || k == "-hh" || k == "--advanced-help") { usage(); return 0; }
+        else if (k == "-hh" || k == "--advanced-help") {
+            usage();
+            fprintf(stderr, "advanced:\n"
+                            "  --device-index-budget <MiB> at most this many MiB of the index's fingerprints on the device at a time, in [1,16777216]: the root\n"
+                            "                           IXF stays resident, the subtrees under its merged bins are searched group by group (one pass\n"
+                            "                           over the query file per group, the file is parsed -- a .gz inflated -- once per pass) and every\n"
+                            "                           read's results are merged on the device.  Taken by itself when the index exceeds the device's\n"
+                            "                           free memory.  ONE device, a query file that can be read again (no pipe); the output is\n"
+                            "                           byte-identical to the resident search.\n");
+            return 0;
+        }
+        else if (k == "-h" || k == "--help") { usage(); return 0; }
         else die("Unknown option " + k + ". In case this is meant to be a non-option/argument/parameter, please specify the start of non-options with '--'.");
     }
     if (profile_mode) {            // like `taxor profile` (profile_cmd.h), and before any HIP call
@@ -1425,6 +1442,147 @@ int main(int argc, char **argv)
         default: printf("use frac minhash\n"); break;
         }
         const size_t ng = cfg.gpus.size();
+
+        // ---- an index that does not fit the device (or --device-index-budget): searched in resident passes (DESIGN.md section 9,
+        // "Search beyond device memory").  The outer loop runs over the passes, the inner one over the query file, cut into the SAME
+        // batches in every pass (the sequential reader cuts at exactly --batch-reads records); a pass's CSR is kept per batch in host
+        // memory with its DFS keys, the last pass merges them on the device and writes / feeds the profile as the resident route does.
+        {
+            taxor_pass_plan whole{};
+            if (taxor_index_plan_passes(view, ~0ull >> 1, &whole, nullptr, nullptr) != TAXOR_OK) die(taxor_gpu_last_error());
+            uint64_t budget = cfg.index_budget_mib << 20;
+            char why[256] = "";
+            if (budget) snprintf(why, sizeof why, "--device-index-budget %llu MiB", (unsigned long long)cfg.index_budget_mib);
+            else if (whole.index_bytes >= (1ull << 30)) {
+                // (asked only for an index of a gigabyte or more: the question starts the HIP runtime on this thread, before the reader
+                // threads exist, and a reader that dies on a malformed file then ends the process while the runtime is up -- its exit
+                // handlers ran into this thread's index upload.  A smaller index on a device that is full fails as before, and the
+                // message names the option)
+                uint64_t fr = 0, tot = 0;
+                if (taxor_gpu_device_memory(cfg.gpus[0], &fr, &tot) != TAXOR_OK) die(taxor_gpu_last_error());
+                if (whole.index_bytes > fr) {
+                    budget = fr - std::min<uint64_t>(4ull << 30, fr / 4);       // the searcher's own buffers live beside the index
+                    snprintf(why, sizeof why, "the index needs %llu MiB on the device, %llu MiB are free", (unsigned long long)(whole.index_bytes >> 20), (unsigned long long)(fr >> 20));
+                }
+            }
+            if (budget) {
+                if (ng > 1) die("paging an index through device memory (" + std::string(why) + ") runs on ONE device; give --gpu <id> instead of " + gpus_option + ".");
+                uint64_t query_bytes = 0;
+                for (const auto &q : queries) {
+                    struct stat sb;
+                    if (stat(q.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode))
+                        die("paging an index through device memory (" + std::string(why) + ") reads the query once per pass: " + q + " is not a regular file and cannot be read again "
+                            "(a pipe, standard input); write it to a file first.");
+                    const bool packed = q.size() > 3 && (q.compare(q.size() - 3, 3, ".gz") == 0 || q.compare(q.size() - 4, 4, ".bz2") == 0);
+                    query_bytes += (uint64_t)sb.st_size * (packed ? 4 : 1);
+                }
+                taxor_gpu_index *idx = nullptr;
+                if (taxor_gpu_index_create_paged(view, cfg.gpus[0], budget, &idx) != TAXOR_OK) die(taxor_gpu_last_error());
+                const uint32_t passes = taxor_gpu_index_passes(idx);
+                fprintf(stderr, "taxor search: the index is searched in %u resident pass%s over the query (%s)\n", passes, passes == 1 ? "" : "es", why);
+                // host memory for the earlier passes' results: per pass 8 B per read (offsets) and 16 B per tuple (user bin, count, key).
+                // Bound: reads at one per 200 bytes of (inflated: x 4) query file, tuples at the 12 per read the library sizes a batch for
+                {
+                    const uint64_t bound = (uint64_t)(passes - 1) * (query_bytes / 200 + 1) * (8 + 16 * 12), avail = taxor::host_memory_available();
+                    if (passes > 1 && avail && bound > avail)
+                        die("the results of " + std::to_string(passes - 1) + " passes are kept in host memory until the last one merges them: up to " + std::to_string(bound) +
+                            " bytes (8 per read and 16 per tuple and pass), MemAvailable is " + std::to_string(avail) + " bytes.");
+                }
+                taxor_gpu_searcher *s = nullptr;
+                if (taxor_gpu_searcher_create(idx, &prm, &s) != TAXOR_OK) die(taxor_gpu_last_error());
+                if (profile_mode) fused.begin(view, taxor_hixf_get_meta(h), prof.device);
+                t_index += now() - t0;
+                struct Saved { std::vector<uint64_t> ro; std::vector<int64_t> ub; std::vector<uint32_t> cnt, key; };
+                std::vector<std::vector<Saved>> store;          // [batch][pass]
+                uint64_t stored = 0;
+                Config seq_cfg = cfg;
+                if (!seq_cfg.batch_reads) seq_cfg.batch_reads = 131072;
+                BatchPool pool;
+                std::vector<const char *> idp;
+                std::vector<uint64_t> idl, rl;
+                std::vector<char> text;
+                std::vector<taxor_gpu_prior> pri;
+                const double t_search0 = now();
+                for (uint32_t p = 0; p < passes; ++p) {
+                    const double tl = now();
+                    if (taxor_gpu_index_load_pass(idx, view, p) != TAXOR_OK) die(taxor_gpu_last_error());
+                    t_index += now() - tl;
+                    const bool last_pass = p + 1 == passes;
+                    size_t bi = 0;
+                    for (size_t f = 0; f < queries.size(); ++f)
+                        t_reads += produce_batches(queries[f], seq_cfg, false, pool, [&](std::unique_ptr<Batch> b) {
+                            if (b->end_of_file) return;
+                            Batch &bt = *b;
+                            const uint64_t n = bt.ids.size();
+                            const double t1 = now();
+                            taxor_gpu_results res{};
+                            auto run = [&] { return taxor_gpu_search_batch(s, bt.bases.data(), bt.offsets.data(), n, &res); };
+                            int rc = run();
+                            if (rc == TAXOR_E_ALPHABET && strip_space_and_digits(bt)) rc = run();
+                            if (rc != TAXOR_OK) die(taxor_gpu_last_error());
+                            if (store.size() <= bi) store.resize(bi + 1);
+                            if (!last_pass) {
+                                const uint32_t *key = nullptr;
+                                if (taxor_gpu_results_keys(s, &key) != TAXOR_OK) die(taxor_gpu_last_error());
+                                const uint64_t need = (n + 1) * 8 + res.n_tuples * 16, avail = taxor::host_memory_available();
+                                if (avail && need + (1ull << 28) > avail)
+                                    die("the passes' results no longer fit host memory: " + std::to_string(stored + need) + " bytes kept so far, MemAvailable is " + std::to_string(avail) + " bytes.");
+                                stored += need;
+                                Saved sv;
+                                sv.ro.assign(res.read_off, res.read_off + n + 1);
+                                sv.ub.assign(res.user_bin, res.user_bin + res.n_tuples);
+                                sv.cnt.assign(res.count, res.count + res.n_tuples);
+                                sv.key.assign(key, key + res.n_tuples);
+                                store[bi].push_back(std::move(sv));
+                            } else {
+                                if (store[bi].size() != passes - 1) die("internal: the query file was cut into other batches than in the pass before");
+                                pri.clear();
+                                for (const Saved &sv : store[bi]) {
+                                    if (sv.ro.size() != n + 1) die("internal: the query file was cut into other batches than in the pass before");
+                                    pri.push_back(taxor_gpu_prior{n, (uint64_t)sv.ub.size(), sv.ro.data(), sv.ub.data(), sv.cnt.data(), sv.key.data()});
+                                }
+                                if (taxor_gpu_search_merge_prior(s, pri.data(), (uint32_t)pri.size()) != TAXOR_OK) die(taxor_gpu_last_error());
+                                std::vector<Saved>().swap(store[bi]);
+                                if (profile_mode) {
+                                    bt.feed_first = fused.next_read.fetch_add(n);
+                                    fused.take_ids(bt);
+                                    const double f0 = now();
+                                    if (taxor_gpu_profile_feed_add_batch(fused.feed, s, bt.feed_first, 0) != TAXOR_OK) die(taxor_gpu_last_error());
+                                    fused.t_feed += now() - f0;
+                                }
+                                if (write_tsv) {
+                                    if (taxor_gpu_batch_fetch(s, &res) != TAXOR_OK) die(taxor_gpu_last_error());
+                                    idp.resize(n); idl.resize(n); rl.resize(n);
+                                    for (uint64_t r = 0; r < n; ++r) { idp[r] = bt.ids.ptr(r); idl[r] = bt.ids.len(r); rl[r] = bt.offsets[r + 1] - bt.offsets[r]; }
+                                    uint64_t need = taxor_format_reads(h, n, idp.data(), idl.data(), rl.data(), res.n_hashes, res.read_off, res.user_bin, res.count, text.data(), text.size());
+                                    if (need > text.size()) {
+                                        text.resize(need + need / 8 + 4096);
+                                        need = taxor_format_reads(h, n, idp.data(), idl.data(), rl.data(), res.n_hashes, res.read_off, res.user_bin, res.count, text.data(), text.size());
+                                    }
+                                    if (need && fwrite(text.data(), 1, need, out) != need) die("cannot write to " + cfg.report_file + ": " + strerror(errno));
+                                }
+                                ++n_batches;
+                                ++n_gpu_batches;
+                                total_reads += n;
+                                total_bases += bt.offsets.back();
+                            }
+                            ++bi;
+                            t_compute += now() - t1;
+                            t_search += now() - t1;
+                            pool.put(std::move(b));
+                        }, (uint32_t)f, 1);
+                }
+                t_search_wall += now() - t_search0;
+                if (tune_env("TAXOR_CLI_TRACE"))
+                    fprintf(stderr, "[trace] paged search: %u passes, %.3f s waiting for uploads, %.2f GB of earlier passes' results held at most\n", passes,
+                            taxor_gpu_index_upload_wait_seconds(idx), stored / 1e9);
+                taxor_gpu_searcher_destroy(s);
+                taxor_gpu_index_destroy(idx);
+                if (profile_mode) fused.finish(prof, cfg.threads, t_search_wall);
+                taxor_hixf_free(h);
+                return;
+            }
+        }
 
         // Overlapped stages (the reference joins its workers after every 1024 reads, do_parallel.hpp:31-32):
         //   reader threads    : FASTA/FASTQ(.gz) -> numbered chunks of records   (taxor_search.cpp:315-321);
@@ -1670,7 +1828,8 @@ int main(int argc, char **argv)
             std::vector<std::string> errs(ng);
             for (size_t g = 0; g < ng; ++g)
                 up.emplace_back([&, g] {
-                    if (taxor_gpu_index_create(view, cfg.gpus[g], &gidx[g]) != TAXOR_OK) errs[g] = taxor_gpu_last_error();
+                    const int rc = taxor_gpu_index_create(view, cfg.gpus[g], &gidx[g]);
+                    if (rc != TAXOR_OK) errs[g] = std::string(taxor_gpu_last_error()) + (rc == TAXOR_E_NOMEM ? "\n(--device-index-budget <MiB> searches an index in resident passes: taxor search --advanced-help)" : "");
                 });
             for (auto &t : up) t.join();
             for (const auto &e : errs)

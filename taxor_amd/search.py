@@ -67,6 +67,24 @@ class SearchResults:
 
 
 @dataclass
+class PassResults:
+    """one pass's results of a batch on a paged index, with the tuples' DFS keys: what merge_prior takes"""
+    results: SearchResults
+    key: np.ndarray        # uint32[n_tuples], ascending within a read
+
+
+def plan_passes(ixfs, n_user_bins, budget_bytes, **kw):
+    """taxor_index_plan_passes (host only) -> (plan dict, pass_of_ixf uint32[n_ixf] with _lib.PASS_ROOT for the root, pass_bytes uint64[n_passes])"""
+    view, keep = GpuIndex._view(ixfs, n_user_bins, kw.get("k", 22), kw.get("s", 12), kw.get("t", 5), kw.get("use_syncmer", True), 1, kw.get("window_size"))
+    plan = _lib.PassPlan()
+    of = np.zeros(len(ixfs), np.uint32)
+    by = np.zeros(len(ixfs), np.uint64)
+    check(_lib.lib().taxor_index_plan_passes(C.byref(view), int(budget_bytes), C.byref(plan), _p(of), _p(by)))
+    del keep
+    return {f: int(getattr(plan, f)) for f, _ in _lib.PassPlan._fields_}, of, by[:plan.n_passes].copy()
+
+
+@dataclass
 class FastxResults:
     """search_fastx: status 0 and the reads' results, ids and lengths -- or status FASTX_IRREGULAR and nothing else"""
     status: int
@@ -167,11 +185,37 @@ class GpuIndex:
         self.n_ixf = len(ixfs)
         self.n_user_bins = n_user_bins
         self.shapes = [(f["bins"], f["stride"], f["seg_len"]) for f in ixfs]
+        self._view_keep = None           # paged(): the view later passes upload from
+
+    @classmethod
+    def paged(cls, ixfs, n_user_bins, budget_bytes, k=22, s=12, t=5, device=0, use_syncmer=True, scaling=1, window_size=None, arith=0, layout=0):
+        """taxor_gpu_index_create_paged: an index whose slab holds the root and at most two groups of subtrees, at most budget_bytes.
+        load_pass(0) comes before the first search; the arrays of `ixfs` stay referenced (later passes upload from them)"""
+        view, keep = cls._view(ixfs, n_user_bins, k, s, t, use_syncmer, scaling, window_size, layout)
+        view.ixf_arith = int(arith)
+        view.ixf_layout = int(layout)
+        h = C.c_void_p()
+        check(_lib.lib().taxor_gpu_index_create_paged(C.byref(view), device, int(budget_bytes), C.byref(h)))
+        g = cls.__new__(cls)
+        g._adopt(h, ixfs, n_user_bins, k, s, t, device, use_syncmer, window_size)
+        g._view_keep = (view, keep)
+        return g
+
+    @property
+    def passes(self):
+        """number of passes of a paged index, 0 for an ordinary one"""
+        return int(_lib.lib().taxor_gpu_index_passes(self._h))
+
+    def load_pass(self, p):
+        """make group p the searched one (the next pass, or 0); every search of the pass before must have ended"""
+        view = self._view_keep[0] if self._view_keep else _lib.HixfView(self.n_ixf, None, self.n_user_bins)      # an ordinary index: the library refuses
+        check(_lib.lib().taxor_gpu_index_load_pass(self._h, C.byref(view), int(p)))
 
     def close(self):
         if getattr(self, "_h", None):
-            _lib.lib().taxor_gpu_index_destroy(self._h)
+            _lib.lib().taxor_gpu_index_destroy(self._h)      # (joins an upload in flight before the view's arrays go)
             self._h = None
+        self._view_keep = None
 
     __del__ = close
 
@@ -384,6 +428,33 @@ class Searcher:
         check(_lib.lib().taxor_gpu_search_batch_end(self._h, C.byref(res)))
         self._inflight = None
         return _results(res)
+
+    # --- paged index: per-pass results and their merge -------------------------------------------------------
+    def result_keys(self, n_tuples):
+        """DFS keys of the last results' tuples (taxor_gpu_results_keys)"""
+        kp = C.POINTER(C.c_uint32)()
+        check(_lib.lib().taxor_gpu_results_keys(self._h, C.byref(kp)))
+        return np.ctypeslib.as_array(kp, shape=(n_tuples,)).copy() if n_tuples else np.zeros(0, np.uint32)
+
+    def search_pass(self, bases, offsets) -> PassResults:
+        """search_batch + the tuples' keys: one pass's share of a batch on a paged index"""
+        r = self.search_batch(bases, offsets)
+        return PassResults(r, self.result_keys(r.user_bin.size))
+
+    def merge_prior(self, priors) -> SearchResults:
+        """after the LAST pass's batch: merge the earlier passes' PassResults of the same reads into the searcher's device CSR
+        (taxor_gpu_search_merge_prior) and fetch the complete results"""
+        arr = (_lib.Prior * max(1, len(priors)))()
+        keep = []
+        for i, p in enumerate(priors):
+            ro = np.ascontiguousarray(p.results.read_off, dtype=np.uint64)
+            ub = np.ascontiguousarray(p.results.user_bin, dtype=np.int64)
+            ct = np.ascontiguousarray(p.results.count, dtype=np.uint32)
+            ky = np.ascontiguousarray(p.key, dtype=np.uint32)
+            keep += [ro, ub, ct, ky]
+            arr[i] = _lib.Prior(ro.size - 1, ub.size, ro.ctypes.data, ub.ctypes.data, ct.ctypes.data, ky.ctypes.data)
+        check(_lib.lib().taxor_gpu_search_merge_prior(self._h, arr, len(priors)))
+        return self.fetch()
 
     # --- phases -------------------------------------------------------------------------------------------
     def upload(self, bases, offsets):
