@@ -60,7 +60,8 @@ typedef struct {
     uint64_t n_ixf;
     const taxor_ixf_view *ixf;
     uint64_t n_user_bins;
-    uint8_t kmer_size, syncmer_size, t_syncmer; /* src/main/index.hpp:219-221 */
+    uint8_t kmer_size, syncmer_size, t_syncmer; /* src/main/index.hpp:219-221; a syncmer index is admitted with 2 <= k <= 32,
+                             * 1 <= s <= 31, s < k, k - s + 1 <= 32 and t >= 1 (TAXOR_E_ARG otherwise) */
     uint8_t use_syncmer;    /* :223; 1 = open canonical syncmers (syncmer.cpp:80-165), 0 = seqan3 minimiser_hash over window_size
                                (taxor_search.cpp:210-212,239-260) */
     uint16_t scaling;       /* :224; > 1 = FracMinHash down-sampling (taxor_search.cpp:223-233), applied on the device */

@@ -154,7 +154,7 @@ int taxor_gpu_memcpy_from_host(void *d_dst, const void *src, uint64_t bytes);
  * Records are ASCII (any dna15 character; the dna4 mapping is applied on the device), at most 2^31 - 1 bases each. */
 typedef struct {
     uint32_t kmer_size, syncmer_size, t_syncmer;
-    uint32_t use_syncmer;     /* 1 = open canonical syncmers, 0 = minimisers over window_size */
+    uint32_t use_syncmer;     /* 1 = open canonical syncmers (s-mer sizes 1..31, as taxor_gpu_index_create admits), 0 = minimisers over window_size */
     uint64_t window_size;     /* minimiser mode: in [k, k+511] */
     uint32_t scaling;         /* > 1 = FracMinHash down-sampling */
     uint32_t reserved;

@@ -423,8 +423,8 @@ static int index_create_impl(const taxor_hixf_view *v, int device, bool upload, 
             return fail(TAXOR_E_ARG, "index_create: window size %llu must be in [k, k+511]", (unsigned long long)v->window_size);
     }
     const int k = v->kmer_size, s = v->syncmer_size, t = v->t_syncmer;
-    if (v->use_syncmer && (k < 2 || k > 32 || s < 1 || s > 16 || s >= k || k - s + 1 > 32 || t < 1))
-        return fail(TAXOR_E_ARG, "index_create: unsupported k=%d s=%d t=%d (need k<=32, s<=16, s<k, t>=1)", k, s, t);
+    if (v->use_syncmer && (k < 2 || k > 32 || s < 1 || s > 31 || s >= k || k - s + 1 > 32 || t < 1))
+        return fail(TAXOR_E_ARG, "index_create: unsupported k=%d s=%d t=%d (need 2<=k<=32, 1<=s<=31, s<k, k-s+1<=32, t>=1)", k, s, t);
     if (v->n_ixf >= (1u << 30)) return fail(TAXOR_E_ARG, "index_create: too many IXFs");
     if (!taxor::ixf_layout_valid(v->ixf_layout)) return fail(TAXOR_E_ARG, "index_create: unknown fingerprint layout code %u", v->ixf_layout);
     HIP_TRY(hipSetDevice(device));

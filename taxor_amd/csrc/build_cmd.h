@@ -31,7 +31,10 @@ const char *const BUILD_ADVANCED_HELP =
     "                                Genomes whose keys may exceed it are keyed in waves into host memory and the index is built\n"
     "                                from there, byte-identical to a build with every key resident (default: such a build is chosen\n"
     "                                when the keys may not fit the free device memory, with an eighth of it as the budget)\n"
-    "    --host-memory-mib <MiB>     host memory the key store of such a build may take, in [1,1073741824] (default: MemAvailable)\n";
+    "    --host-memory-mib <MiB>     host memory the key store of such a build may take, in [1,1073741824] (default: MemAvailable)\n"
+    "ranges of the syncmer scheme (--use-syncmer)\n"
+    "    --syncmer-size <s>          in [1,26] and below --kmer-size (at most 30 with syncmers); every such pair is built, and `taxor\n"
+    "                                search` takes syncmer indexes of any s-mer size from 1 to 31 with k-mer sizes up to 32\n";
 
 struct BuildSpecies {
     std::string accession, taxid, organism, taxnames, taxids, file_stem, path;
@@ -184,9 +187,9 @@ int build_command(int argc, char **argv)
     // what this build cannot do, said before any work
     if (c.output_file_name.empty()) return build_error("Please give the index's file name with --output-filename");
     const int k = (int)c.kmer_size, s = (int)c.syncmer_size, t = (k - s + 1) / 2;    // taxor_build.cpp:509-510 (integer division)
-    if (c.use_syncmer && (s >= k || s > 16 || t < 1))
+    if (c.use_syncmer && (s >= k || t < 1))
         return build_error("syncmer size " + std::to_string(s) + " with k-mer size " + std::to_string(k) +
-                           ": the search kernels take 1 <= s <= 16, s < k and k - s >= 1");
+                           ": the syncmer size must be smaller than the k-mer size, with k - s >= 1");
     if (!c.use_syncmer && (k > 32 || c.window_size < k))
         return build_error("the minimizer scheme needs k-mer size <= 32 and window size >= k-mer size (k " + std::to_string(k) + ", window " +
                            std::to_string(c.window_size) + ")");

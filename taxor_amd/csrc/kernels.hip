@@ -115,6 +115,10 @@ __device__ __forceinline__ uint32_t dedup_slot(uint64_t h, uint32_t mask)
 // tile once, and gets leftmost/rightmost argmin from two sparse-table min trees over keys (value<<5 | offset) and
 // (value<<5 | 31-offset).  FW == 0: generic window length, per-window scan in LDS.
 static constexpr int SY_RS = SY_T / SY_C + 5; // row stride (words) of the transposed s-mer tile; odd -> no bank conflicts
+// VT: the type of an s-mer value.  uint32_t holds s <= 16; the generic path with uint64_t holds s = 17..31 (at most 62 bits),
+// where k <= 32 leaves a window of at most SY_WIDE_W s-mers.  Consecutive lanes read consecutive 8-byte values, so the
+// per-window scan stays conflict-free at 64 bits; everything after the argmins is the same code for both types.
+static constexpr int SY_WIDE_W = 16;          // longest window of an index with s >= 17 (w = k - s + 1, k <= 32)
 
 // PROF: the same kernel with s_memtime marks at its phase boundaries (block-uniform, scalar), summed per launch into
 // a.prof -- a measurement aid compiled as a separate instantiation, the production kernel carries none of it.
@@ -125,12 +129,15 @@ static constexpr int SY_RS = SY_T / SY_C + 5; // row stride (words) of the trans
         plast = now_;                                                                                   \
     }
 
-template <int FW, bool PROF = false> __global__ __launch_bounds__(BLK) void k_syncmers(const SyncmerArgs a)
+template <int FW, bool PROF = false, typename VT = uint32_t> __global__ __launch_bounds__(BLK) void k_syncmers(const SyncmerArgs a)
 {
+    constexpr bool WIDE = sizeof(VT) == 8;
+    static_assert(!WIDE || FW == 0, "64-bit s-mer values: generic path only");
+    constexpr int SV_N = WIDE ? SY_T + SY_WIDE_W - 1 : SY_C * SY_RS;
     uint64_t pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t plast = PROF ? __builtin_amdgcn_s_memtime() : 0;
     __shared__ uint32_t sW[SY_WORDS];
-    __shared__ uint32_t sV[SY_C * SY_RS];
+    __shared__ VT sV[SV_N];
     __shared__ __attribute__((aligned(16))) uint8_t sLm[SY_T];
     __shared__ __attribute__((aligned(16))) uint8_t sRm[SY_T];
     __shared__ uint32_t sTab[SY_LDS_TAB];
@@ -274,12 +281,15 @@ template <int FW, bool PROF = false> __global__ __launch_bounds__(BLK) void k_sy
                 *reinterpret_cast<uint64_t *>(&sRm[xs]) = packR;
             } else {
                 for (int i = (int)tid; i < SY_T + w - 1; i += BLK) {
-                    uint32_t v = 0xFFFFFFFFu;
+                    VT v = (VT)~(VT)0;
                     if (i < nv) {
                         const uint32_t pos = (uint32_t)(x0 + i);
-                        const uint32_t f = (uint32_t)lds_bases(sW, (pos >> 4) - wbase, pos & 15u, s) & smask;
-                        const uint32_t rc = revcomp32(f, s);
-                        v = min(f, rc);
+                        if constexpr (WIDE) v = canon(lds_bases(sW, (pos >> 4) - wbase, pos & 15u, s), s);   // masked to 2s bits
+                        else {
+                            const uint32_t f = (uint32_t)lds_bases(sW, (pos >> 4) - wbase, pos & 15u, s) & smask;
+                            const uint32_t rc = revcomp32(f, s);
+                            v = min(f, rc);
+                        }
                     }
                     sV[i] = v;
                 }
@@ -289,10 +299,10 @@ template <int FW, bool PROF = false> __global__ __launch_bounds__(BLK) void k_sy
                 for (int c = 0; c < SY_C; ++c) {
                     const int xl = c * BLK + (int)tid;
                     if (xl < nw_tile) {
-                        uint32_t m = sV[xl];
+                        VT m = sV[xl];
                         int lm = 0, rm = 0;
                         for (int j = 1; j < w; ++j) {
-                            const uint32_t v = sV[xl + j];
+                            const VT v = sV[xl + j];
                             if (v < m) { m = v; lm = j; rm = j; }
                             else if (v == m) rm = j;
                         }
@@ -401,8 +411,8 @@ template <int FW, bool PROF = false> __global__ __launch_bounds__(BLK) void k_sy
                 else v = gcand[i];
                 return v;
             };
-            uint32_t *const sDupBits = sV;                               // the s-mer tile is dead by now: 1 bit per candidate
-            static_assert((uint32_t)(SY_C * SY_RS) * 32u == SYNC_LDS_DEDUP_MAX, "dup-bit capacity");
+            uint32_t *const sDupBits = reinterpret_cast<uint32_t *>(sV); // the s-mer tile is dead by now: 1 bit per candidate
+            static_assert((uint32_t)(SY_C * SY_RS) * 32u == SYNC_LDS_DEDUP_MAX && sizeof(sV) * 8u >= SYNC_LDS_DEDUP_MAX, "dup-bit capacity");
             const bool in_lds = n_sel <= SYNC_LDS_DEDUP_MAX;
             bool any_dup = false;                                        // block-uniform
             if (in_lds) {
@@ -932,7 +942,9 @@ void launch_syncmers(const SyncmerArgs &a, int grid, hipStream_t st)
     if (!generic_only && a.k - a.s + 1 == 11 && a.s <= 13) {
         if (a.prof) hipLaunchKernelGGL((k_syncmers<11, true>), dim3(grid), dim3(BLK), 0, st, a);
         else hipLaunchKernelGGL((k_syncmers<11, false>), dim3(grid), dim3(BLK), 0, st, a);
-    } else hipLaunchKernelGGL((k_syncmers<0, false>), dim3(grid), dim3(BLK), 0, st, a);
+    } else if (a.s > 16)        // s-mer values beyond 32 bits; index_create admits k <= 32, so the window is at most SY_WIDE_W
+        hipLaunchKernelGGL((k_syncmers<0, false, uint64_t>), dim3(grid), dim3(BLK), 0, st, a);
+    else hipLaunchKernelGGL((k_syncmers<0, false>), dim3(grid), dim3(BLK), 0, st, a);
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -209,7 +209,9 @@ void usage()
 {
     fprintf(stderr,
             "taxor search - Queries files of DNA sequences against a list of HIXF index files (MI355X)\n"
-            "  --index-file <f[,f..]>   taxor index file(s) containing HIXF index and reference information (required)\n"
+            "  --index-file <f[,f..]>   taxor index file(s) containing HIXF index and reference information (required); syncmer\n"
+            "                           indexes of k-mer size 2..32 and syncmer size 1..31 (below the k-mer size), minimiser indexes\n"
+            "                           of k-mer size 1..32\n"
             "  --query-file <f[,f..]>   file(s) containing sequences to query against the index\n"
             "  --output-file <f>        file name for the resulting output\n"
             "  --threads <1..32>        host threads parsing the query file (plain FASTA/FASTQ; gzip is one stream) and rendering\n"
