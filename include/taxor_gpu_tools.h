@@ -268,6 +268,9 @@ int taxor_gpu_results_keys(taxor_gpu_searcher *s, const uint32_t **key);
  *   fetch  : wait + D2H of the CSR results */
 int taxor_gpu_batch_upload(taxor_gpu_searcher *s, const char *bases, const uint64_t *offsets,
                            uint64_t n_reads);
+/* taxor_gpu_batch_upload with the HIP-event time of its packing kernel (k_pack_dna4) in *kernel_ms: the figure that stands beside
+ * taxor_gpu_pack_nibbles' kernel_ms in measurements */
+int taxor_gpu_pack_dna4_timed(taxor_gpu_searcher *s, const char *bases, const uint64_t *offsets, uint64_t n_reads, float *kernel_ms);
 int taxor_gpu_batch_run(taxor_gpu_searcher *s);
 int taxor_gpu_batch_sync(taxor_gpu_searcher *s);
 int taxor_gpu_batch_fetch(taxor_gpu_searcher *s, taxor_gpu_results *out);
@@ -351,6 +354,19 @@ int taxor_gpu_ixf_bulk_count(taxor_gpu_searcher *s, uint64_t ixf, const uint64_t
 /* membership_agent::bulk_contains(values, threshold) (:381-406) for one hash list. */
 int taxor_gpu_bulk_contains(taxor_gpu_searcher *s, const uint64_t *hashes, uint64_t n, uint64_t threshold,
                             taxor_gpu_results *out);
+/* k_pack_nibbles alone (taxor_amd/csrc/bam_pack.hip; the segments are those of taxor_gpu_search_nibbles_begin, described there): the
+ * packed words in host memory, read r's at words[word_off[r] .. word_off[r+1]) -- 16 bases per word, the first in the top bits, a
+ * read's words padded with zeros to a multiple of four: what taxor_gpu_batch_upload leaves on the device.  kernel_ms (may be NULL)
+ * receives the kernel's HIP-event time.  Pointers valid until the next call on the searcher. */
+typedef struct {
+    const uint8_t *seq4;
+    const uint64_t *byte_off;   /* [n_reads] ascending */
+    const uint32_t *read_len;   /* [n_reads] bases */
+    const uint8_t *reverse;     /* [n_reads] or NULL */
+    uint64_t n_reads;
+} taxor_nibble_segment;
+int taxor_gpu_pack_nibbles(taxor_gpu_searcher *s, const taxor_nibble_segment *segs, uint64_t n_segs, const uint64_t **word_off,
+                           const uint32_t **words, float *kernel_ms);
 
 
 /* ---- Diagnosis of an index this library did not write (`taxor verify --variants`, `taxor pin`).  Both the
@@ -528,6 +544,18 @@ typedef struct {
     uint32_t status;                   /* 0, or TAXOR_FASTX_IRREGULAR: nothing was enqueued, parse on the host */
 } taxor_fastx_scan;
 int taxor_gpu_search_fastx_begin(taxor_gpu_searcher *s, const char *raw, uint64_t n_bytes, int kind, taxor_fastx_scan *scan);
+
+/* ---- search from 4-bit sequences (taxor_amd/csrc/bam_pack.hip): what a BAM record's SEQ field holds, two bases per
+ * byte, the first in the high nibble, codes of the alphabet "=ACMGRSVTWYHKDBN".  Read i of a segment is read_len[i] bases from byte
+ * byte_off[i] of seq4 (every read starts on a byte; the low nibble of an odd read's last byte is ignored); reverse[i] != 0 says that the
+ * read is stored reverse-complemented and is restored on the device -- the complement is taken on the IUPAC code before the dna4
+ * mapping.  reverse == NULL: every read is forward.  The reads of all segments form ONE resident batch in segment order, like
+ * taxor_gpu_search_fastx_begin's (sub_batch_reads / sub_batch_bases, the processing order and the threshold models apply as for any
+ * batch; the lanes for small calls are not used); taxor_gpu_search_batch_end follows.  The arrays are free again when the call returns.
+ * Checked before anything is launched (TAXOR_E_ARG): null pointers, byte offsets that do not ascend or lie inside the read before,
+ * read_len >= 2^31, a segment of 2^40 bytes or more.  Nibble 0 ('=') is not dna15: TAXOR_E_ALPHABET.  Works on a searcher of a paged
+ * index (taxor_gpu_results_keys, taxor_gpu_search_merge_prior).  The segment type stands with taxor_gpu_pack_nibbles above. */
+int taxor_gpu_search_nibbles_begin(taxor_gpu_searcher *s, const taxor_nibble_segment *segs, uint64_t n_segs);
 
 #ifdef __cplusplus
 }

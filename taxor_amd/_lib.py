@@ -163,6 +163,10 @@ class FastxScan(C.Structure):
 FASTX_IRREGULAR = 1
 
 
+class NibbleSegment(C.Structure):
+    _fields_ = [("seq4", C.c_void_p), ("byte_off", C.c_void_p), ("read_len", C.c_void_p), ("reverse", C.c_void_p), ("n_reads", C.c_uint64)]
+
+
 class PassPlan(C.Structure):
     _fields_ = [("n_passes", C.c_uint32), ("n_subtrees", C.c_uint32), ("root_bytes", C.c_uint64), ("slab_bytes", C.c_uint64),
                 ("index_bytes", C.c_uint64)]
@@ -244,9 +248,13 @@ SIGNATURES = {
     "taxor_gpu_search_batch_begin": (C.c_int, [_P, _P, _P, C.c_uint64]),
     "taxor_gpu_search_segments_begin": (C.c_int, [_P, C.POINTER(ReadSegment), C.c_uint64]),
     "taxor_gpu_search_fastx_begin": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(FastxScan)]),
+    "taxor_gpu_search_nibbles_begin": (C.c_int, [_P, C.POINTER(NibbleSegment), C.c_uint64]),
+    "taxor_gpu_pack_nibbles": (C.c_int, [_P, C.POINTER(NibbleSegment), C.c_uint64, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint32)),
+                                         C.POINTER(C.c_float)]),
     "taxor_gpu_search_batch_end": (C.c_int, [_P, C.POINTER(Results)]),
     "taxor_gpu_search_batch": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(Results)]),
     "taxor_gpu_batch_upload": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "taxor_gpu_pack_dna4_timed": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_float)]),
     "taxor_gpu_batch_run": (C.c_int, [_P]),
     "taxor_gpu_batch_sync": (C.c_int, [_P]),
     "taxor_gpu_batch_fetch": (C.c_int, [_P, C.POINTER(Results)]),

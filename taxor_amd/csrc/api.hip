@@ -142,6 +142,11 @@ struct taxor_gpu_searcher {
     uint64_t packed_word_count = 0, packed_in_bytes = 0;
     FastxScan *fx = nullptr;                // record scanner of taxor_gpu_search_fastx_begin (fastx_scan.hip), made at first use
     std::vector<uint64_t> fx_off;           // ... and the read offsets it implies
+    DeviceBuf<uint64_t> d_boff;             // taxor_gpu_search_nibbles_begin: byte offset of every read's 4-bit SEQ field inside d_ascii
+    DeviceBuf<uint8_t> d_rev;               // ... and its reverse byte
+    std::vector<uint64_t> nib_off, nib_boff;   // host side of the two, and the read offsets the lengths imply
+    std::vector<uint8_t> nib_rev;
+    std::vector<uint32_t> h_words;          // taxor_gpu_pack_nibbles: the packed words in host memory
 
     // per-sub-batch scratch
     DeviceBuf<uint64_t> d_cand[2], d_hashes[2];   // double-buffered across sub-batches
@@ -1104,7 +1109,7 @@ extern "C" void taxor_gpu_searcher_destroy(taxor_gpu_searcher *s)
     if (s->st) (void)hipStreamSynchronize(s->st);
     s->d_ascii.release(); s->d_aoff.release(); s->d_poff.release(); s->d_hoff.release();
     s->d_packed.release(); s->d_rlen.release(); s->d_hcap.release(); s->d_nh.release(); s->d_thr.release();
-    s->d_order.release();
+    s->d_order.release(); s->d_boff.release(); s->d_rev.release();
     if (s->fx) fastx_scan_destroy(s->fx);
     for (int b = 0; b < 2; ++b) { s->d_cand[b].release(); s->d_hashes[b].release(); }
     s->d_sync_cursor.release();
@@ -2310,6 +2315,30 @@ extern "C" int taxor_gpu_batch_upload(taxor_gpu_searcher *s, const char *bases, 
     return check_flags(s, &rerun); // synchronises; reports a non-dna15 character
 }
 
+extern "C" int taxor_gpu_pack_dna4_timed(taxor_gpu_searcher *s, const char *bases, const uint64_t *offsets, uint64_t n_reads, float *kernel_ms)
+{
+    if (!kernel_ms) return fail(TAXOR_E_ARG, "pack_dna4_timed: null argument");
+    *kernel_ms = 0.f;
+    if (s) s->small_active = false;
+    if (int rc = prepare_batch(s, bases, offsets, n_reads, false)) return rc;
+    const uint64_t a0 = offsets[0], nb = offsets[n_reads] - a0;
+    if (nb) HIP_TRY(hipMemcpyAsync(s->d_ascii.p, bases + a0, nb, hipMemcpyHostToDevice, s->st));
+    struct EventPair {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    HIP_TRY(hipEventRecord(ev.a, s->st));
+    launch_pack_dna4(s->d_ascii.p, s->d_aoff.p, s->d_poff.p, s->d_packed.p, (uint32_t)n_reads, s->d_ctr, s->st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev.b, s->st));
+    bool rerun;
+    if (int rc = check_flags(s, &rerun)) return rc;
+    (void)hipEventElapsedTime(kernel_ms, ev.a, ev.b);
+    return TAXOR_OK;
+}
+
 extern "C" int taxor_gpu_batch_run(taxor_gpu_searcher *s)
 {
     if (!s) return fail(TAXOR_E_ARG, "batch_run: null searcher");
@@ -2721,6 +2750,100 @@ extern "C" int taxor_gpu_search_fastx_begin(taxor_gpu_searcher *s, const char *r
     scan->id_off = t.id_off;
     scan->id_len = t.id_len;
     scan->read_len = t.read_len;
+    return TAXOR_OK;
+}
+
+namespace {
+
+// The 4-bit SEQ bytes take the place of the ASCII bases in d_ascii (half their size), segment after segment; the batch is laid out
+// from the reads' lengths exactly as any other batch (prepare_batch) and k_pack_nibbles (bam_pack.hip) writes the packed words.
+// Everything is validated before anything is enqueued.  Synchronises; reports nibble 0 ('=') as TAXOR_E_ALPHABET.
+int nibbles_upload_pack(taxor_gpu_searcher *s, const taxor_nibble_segment *segs, uint64_t n_segs, const char *who, float *kernel_ms)
+{
+    if (!s || (n_segs && !segs)) return fail(TAXOR_E_ARG, "%s: null argument", who);
+    uint64_t n_reads = 0;
+    for (uint64_t j = 0; j < n_segs; ++j) {
+        if (segs[j].n_reads && (!segs[j].byte_off || !segs[j].read_len)) return fail(TAXOR_E_ARG, "%s: segment %llu is null", who, (unsigned long long)j);
+        n_reads += segs[j].n_reads;
+    }
+    std::vector<uint64_t> &off = s->nib_off, &boff = s->nib_boff;
+    std::vector<uint8_t> &rev = s->nib_rev;
+    off.resize(n_reads + 1);
+    boff.resize(n_reads + 1);
+    rev.assign(n_reads + 1, 0);
+    std::vector<std::pair<uint64_t, uint64_t>> spans(n_segs);     // (first byte inside d_ascii, bytes) of every segment
+    bool any_rev = false;
+    uint64_t r = 0, base = 0;
+    off[0] = 0;
+    for (uint64_t j = 0; j < n_segs; ++j) {
+        const taxor_nibble_segment &g = segs[j];
+        uint64_t end = 0;       // first byte behind the reads so far
+        for (uint64_t i = 0; i < g.n_reads; ++i, ++r) {
+            const uint64_t len = g.read_len[i], bytes = (len + 1) / 2;
+            if (len >= (1ull << 31)) return fail(TAXOR_E_ARG, "%s: read %llu of segment %llu is 2^31 bases or longer", who, (unsigned long long)i, (unsigned long long)j);
+            if (g.byte_off[i] < end)
+                return fail(TAXOR_E_ARG, "%s: byte offset of read %llu of segment %llu is not ascending or lies inside the read before it", who, (unsigned long long)i,
+                            (unsigned long long)j);
+            if (g.byte_off[i] >= (1ull << 40) || g.byte_off[i] + bytes >= (1ull << 40)) return fail(TAXOR_E_ARG, "%s: segment %llu holds 2^40 bytes or more", who, (unsigned long long)j);
+            end = g.byte_off[i] + bytes;
+            boff[r] = base + g.byte_off[i];
+            off[r + 1] = off[r] + len;
+            if (g.reverse && g.reverse[i]) { rev[r] = 1; any_rev = true; }
+        }
+        if (end && !g.seq4) return fail(TAXOR_E_ARG, "%s: segment %llu has reads and no bytes", who, (unsigned long long)j);
+        spans[j] = {base, end};
+        base += end;
+    }
+    static const char nothing = 0;
+    s->small_active = false;
+    if (int rc = prepare_batch(s, &nothing, off.data(), n_reads, false)) return rc;
+    if (reserve(s->d_ascii, std::max(base, s->n_bases) + 64) || reserve(s->d_boff, n_reads + 1) || reserve(s->d_rev, n_reads + 1)) return TAXOR_E_HIP;
+    for (uint64_t j = 0; j < n_segs; ++j)
+        if (spans[j].second) HIP_TRY(hipMemcpyAsync(s->d_ascii.p + spans[j].first, segs[j].seq4, spans[j].second, hipMemcpyHostToDevice, s->st));
+    if (n_reads) {
+        HIP_TRY(hipMemcpyAsync(s->d_boff.p, boff.data(), n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, s->st));
+        if (any_rev) HIP_TRY(hipMemcpyAsync(s->d_rev.p, rev.data(), n_reads, hipMemcpyHostToDevice, s->st));
+    }
+    struct EventPair {      // destroyed on every way out
+        hipEvent_t a = nullptr, b = nullptr;
+        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } ev;
+    if (kernel_ms) {
+        *kernel_ms = 0.f;
+        HIP_TRY(hipEventCreate(&ev.a));
+        HIP_TRY(hipEventCreate(&ev.b));
+        HIP_TRY(hipEventRecord(ev.a, s->st));
+    }
+    launch_pack_nibbles(s->d_ascii.p, s->d_boff.p, s->d_rlen.p, any_rev ? s->d_rev.p : nullptr, s->d_poff.p, s->d_packed.p, (uint32_t)n_reads, s->d_ctr, s->st);
+    HIP_TRY(hipGetLastError());
+    if (kernel_ms) HIP_TRY(hipEventRecord(ev.b, s->st));
+    bool rerun;
+    const int rc = check_flags(s, &rerun);      // synchronises: the caller's bytes and the host arrays above are free again
+    if (kernel_ms && rc == TAXOR_OK) (void)hipEventElapsedTime(kernel_ms, ev.a, ev.b);
+    return rc;
+}
+
+} // namespace
+
+extern "C" int taxor_gpu_search_nibbles_begin(taxor_gpu_searcher *s, const taxor_nibble_segment *segs, uint64_t n_segs)
+{
+    if (int rc = nibbles_upload_pack(s, segs, n_segs, "search_nibbles_begin", nullptr)) return rc;
+    s->host_spans.clear();
+    return run_pipeline(s, false);
+}
+
+extern "C" int taxor_gpu_pack_nibbles(taxor_gpu_searcher *s, const taxor_nibble_segment *segs, uint64_t n_segs, const uint64_t **word_off,
+                                      const uint32_t **words, float *kernel_ms)
+{
+    if (!word_off || !words) return fail(TAXOR_E_ARG, "pack_nibbles: null argument");
+    if (int rc = nibbles_upload_pack(s, segs, n_segs, "pack_nibbles", kernel_ms)) return rc;
+    const uint64_t n = s->n_reads, total = s->packed_word_count - 16;
+    s->lay_poff.resize(n + 1);
+    s->lay_poff[n] = total;
+    s->h_words.resize(total);
+    if (total) HIP_TRY(hipMemcpy(s->h_words.data(), s->d_packed.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *word_off = s->lay_poff.data();
+    *words = s->h_words.data();
     return TAXOR_OK;
 }
 

@@ -86,6 +86,7 @@ struct BaseBuf {
     char &back() { return p[n - 1]; }
     void pop_back() { --n; }
     void resize(size_t m) { if (m > cap) reserve(m); n = m; }      // added bytes are NOT initialised
+    void release() { free(p); p = nullptr; n = cap = 0; }
     void reserve(size_t want)
     {
         if (want <= cap) return;
@@ -146,6 +147,12 @@ struct Batch {
     BaseBuf raw;
     char raw_kind = 0;
     void *raw_pinned = nullptr; // raw.data() as page-locked by the range thread that filled it (search_main.cpp); recycled with the chunk
+    // raw_kind 'B': the chunk comes from a BAM file (bam.h).  raw holds the records' 4-bit SEQ fields back to back, read r being
+    // nib_len[r] bases from byte nib_off[r], stored reverse-complemented when nib_rev[r]; ids and offsets (the lengths summed up) are
+    // filled by the reader, bases stays empty.  The device unpacks the nibbles (bam_pack.hip)
+    std::vector<uint64_t> nib_off;
+    std::vector<uint32_t> nib_len;
+    std::vector<uint8_t> nib_rev;
 };
 
 // ---- bzip2 input (seqan3's sequence_file_input reads .bz2 when built with bzip2, which the reference's CMake fetches).
@@ -278,7 +285,10 @@ struct FastxReader {
     {
         buf.resize(8u << 20);
         unsigned char magic[3] = {0, 0, 0};
-        if (FILE *probe = fopen(path.c_str(), "rb")) {
+        // (a regular file only: a probe of a pipe would take its first bytes away from the stream opened below)
+        struct stat psb;
+        const bool regular = stat(path.c_str(), &psb) == 0 && S_ISREG(psb.st_mode);
+        if (FILE *probe = regular ? fopen(path.c_str(), "rb") : nullptr) {
             const size_t got = fread(magic, 1, 3, probe);
             fclose(probe);
             if (got == 3 && magic[0] == 'B' && magic[1] == 'Z' && magic[2] == 'h') {

@@ -196,7 +196,7 @@ private:
             if (t + 8 <= size_ - p) {
                 r.out.resize(n);
                 const uint16_t *sy = co.sym.data() + WIN;
-                uint8_t *o = reinterpret_cast<uint8_t *>(&r.out[0]);
+                uint8_t *o = reinterpret_cast<uint8_t *>(r.out.data());      // (an empty member -- BGZF's end-of-file block -- has no element 0)
                 uint32_t any = 0;
                 size_t i = 0;
 #if defined(__SSE2__)

@@ -189,6 +189,10 @@ void launch_finalize_small(const SmallFinalizeArgs &a, hipStream_t st);
 // launch wrappers (all asynchronous on `st`)
 void launch_pack_dna4(const uint8_t *ascii, const uint64_t *aoff, const uint64_t *poff, uint32_t *packed,
                       uint32_t n_reads, Counters *ctr, hipStream_t st, int max_grid = 0);
+// bam_pack.hip: 4-bit BAM SEQ fields -> the same packed words; read r: rlen[r] bases from byte boff[r] of seq4 (which needs 12 bytes
+// of slack past its end; the searcher's buffer has 64), reversed-complemented when rev[r] (rev may be null: all forward).  Nibble 0 ('=') raises FLAG_ALPHABET
+void launch_pack_nibbles(const uint8_t *seq4, const uint64_t *boff, const uint32_t *rlen, const uint8_t *rev, const uint64_t *poff,
+                         uint32_t *packed, uint32_t n_reads, Counters *ctr, hipStream_t st, int max_grid = 0);
 void launch_syncmers(const SyncmerArgs &a, int grid, hipStream_t st);
 // short reads (hcap <= SYNC_WAVE_CAND), k - s + 1 == 11: one wavefront per read
 void launch_syncmers_wave(const SyncmerArgs &a, int grid, hipStream_t st);

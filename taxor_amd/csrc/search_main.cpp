@@ -4,6 +4,7 @@
 // reading (:181-184), batching (:315-326) and output (:268-311, :343).
 #include "../../include/taxor_gpu_tools.h"
 #include "fastx.h"
+#include "bam.h"
 #include "tuning.h"
 #include "ixf_arith.h"
 #include "ixf_layout.h"
@@ -123,6 +124,14 @@ inline void unpin_buffers(Batch &b)
     if (b.raw_pinned) { taxor_gpu_host_unregister(b.raw_pinned); b.raw_pinned = nullptr; }
 }
 
+// a recycled chunk whose `raw` buffer last held file bytes or a BAM batch, refilled by a parser that never touches `raw`: the buffer
+// (up to 64 MB and more, page-locked) goes back instead of travelling with the chunk unused
+inline void drop_raw(Batch &b)
+{
+    if (b.raw_pinned) { taxor_gpu_host_unregister(b.raw_pinned); b.raw_pinned = nullptr; }
+    if (b.raw.capacity()) b.raw.release();
+}
+
 struct BatchPool {
     std::mutex mu;
     std::condition_variable cv;
@@ -212,7 +221,9 @@ void usage()
             "  --index-file <f[,f..]>   taxor index file(s) containing HIXF index and reference information (required); syncmer\n"
             "                           indexes of k-mer size 2..32 and syncmer size 1..31 (below the k-mer size), minimiser indexes\n"
             "                           of k-mer size 1..32\n"
-            "  --query-file <f[,f..]>   file(s) containing sequences to query against the index\n"
+            "  --query-file <f[,f..]>   file(s) containing sequences to query against the index: FASTA or FASTQ, plain, .gz or .bz2, or BAM\n"
+            "                           (unaligned or aligned; recognised by content; secondary and supplementary records are left out and\n"
+            "                           reads stored reverse-complemented are restored, as `samtools fastq` does); kinds may be mixed\n"
             "  --output-file <f>        file name for the resulting output\n"
             "  --threads <1..32>        host threads parsing the query file (plain FASTA/FASTQ; gzip is one stream) and rendering\n"
             "                           the report; default 4-16 by the size of the machine (the reference's default of 1 is its\n"
@@ -228,7 +239,8 @@ void usage()
             "  --sequential             read every query file front to back on one thread (FASTQ whose records wrap their lines)\n"
             "  --device-parse           plain FASTA / four-line FASTQ: the byte ranges go to the device as they are read and the records are\n"
             "                           found there (the host parses a range only where the device reports it irregular); compressed\n"
-            "                           and --sequential input is parsed on the host as without the switch\n"
+            "                           and --sequential input is parsed on the host as without the switch; a BAM file ignores it (its\n"
+            "                           records are walked on the host and its 4-bit sequences unpacked on the device in any case)\n"
             "  --group-reads <n>        reads per GPU batch, made of whole chunks (default 131072; --batch-reads if that is given)\n"
             "  --ixf-arithmetic <spec>  search an index whose fingerprints follow another reading of the IXF arithmetic than this\n"
             "                           build's (the spec `taxor verify --variants` prints: kh=..,sm=..,rot=..,red=..,fp=..)\n"
@@ -334,9 +346,10 @@ double produce_batches(const std::string &query, const Config &cfg, bool allow_r
     const double t_begin = now();
     double blocked = 0;   // time the sequential reader spent waiting for the consumers
     fastx::RangedFastx rf;
-    bool ranged = false;
+    bool ranged = false, is_bam = false;
     try {
-        ranged = allow_ranges && rf.open(query);
+        is_bam = bam::sniff(query) == bam::BAM;      // by content, never by name; CRAM and SAM text are refused by name
+        ranged = !is_bam && allow_ranges && rf.open(query);
     } catch (const std::exception &e) { die(e.what()); }
     if (ranged) {
         if (cfg.batch_reads) rf.plan(cfg.batch_reads, std::min<uint64_t>(cfg.batch_bases, 1ull << 30));
@@ -383,6 +396,7 @@ double produce_batches(const std::string &query, const Config &cfg, bool allow_r
                             push(std::move(bt));
                             continue;
                         }
+                        drop_raw(*bt);
                         const size_t need = fastx::bases_bound(e - b, rf.kind);
                         if (need > bt->bases.capacity()) {  // grow before parsing, and only with the old block unpinned
                             if (bt->pinned) { taxor_gpu_host_unregister(bt->pinned); bt->pinned = nullptr; }
@@ -422,8 +436,62 @@ double produce_batches(const std::string &query, const Config &cfg, bool allow_r
     }
     if (cfg.device_parse) {
         static std::atomic<bool> said{false};
-        if (!said.exchange(true))
-            fprintf(stderr, "--device-parse: %s is compressed or read sequentially: it is parsed on the host\n", query.c_str());
+        if (!said.exchange(true)) {
+            if (is_bam) fprintf(stderr, "--device-parse: %s is BAM: the switch is ignored (its records are walked on the host and its sequences unpacked on the device in any case)\n", query.c_str());
+            else fprintf(stderr, "--device-parse: %s is compressed or read sequentially: it is parsed on the host\n", query.c_str());
+        }
+    }
+    if (is_bam) {
+        // BAM (bam.h): the blocks are inflated on this file's threads (one zlib stream without allow_ranges), this thread walks the
+        // records and copies their 4-bit SEQ fields back to back into the chunk's raw buffer, which goes to the device as it is.
+        // With --batch-reads a chunk is exactly that many records, like the sequential FASTX reader's below.  Without, chunks are
+        // cut by size, in the class of the range readers' (128 MB of FASTQ text hold 64 MB of SEQ bytes): at 2^27 bases, so that the
+        // GPU starts on the first chunk while the walker fills the second -- a cut by records alone made ONE chunk of a file of
+        // long reads.  Either rule depends on the file alone: the paged route, which reads the file once per pass, gets the same
+        // chunks every time.  The buffer is page-locked by the pinner stage behind this thread (search_files), never here.
+        const unsigned bam_threads = parse_threads ? parse_threads : std::max(1u, std::min(cfg.threads, 32u));
+        const uint64_t batch_reads = cfg.batch_reads ? cfg.batch_reads : (1u << 20);
+        const uint64_t batch_bases = cfg.batch_reads ? cfg.batch_bases : std::min<uint64_t>(cfg.batch_bases, 1ull << 27);
+        uint64_t seq = 0;
+        try {
+            bam::Reader rd;
+            rd.open(query, bam_threads, !allow_ranges);
+            Batch *cur = nullptr;
+            // a buffer that is page-locked where it stands: the registration is given up before the buffer moves
+            rd.grow = [&](size_t) { if (cur && cur->raw_pinned) { taxor_gpu_host_unregister(cur->raw_pinned); cur->raw_pinned = nullptr; } };
+            for (bool more = true; more;) {
+                if (gate) gate();
+                auto b = pool.get();
+                cur = b.get();
+                b->seq = seq++;
+                b->may_pin = false;
+                b->ids.clear();
+                b->bases.clear();
+                b->raw.clear();
+                b->offsets.assign(1, 0);
+                b->nib_off.clear();
+                b->nib_len.clear();
+                b->nib_rev.clear();
+                if (!cfg.batch_reads && b->raw.capacity() < (batch_bases / 2 + (4u << 20))) {      // sized once: a size-cut chunk never grows past this
+                    rd.grow(0);
+                    b->raw.reserve(batch_bases / 2 + (4u << 20));
+                }
+                while (b->ids.size() < batch_reads && b->offsets.back() < batch_bases && (more = rd.next(b->ids, b->raw, b->nib_off, b->nib_len, b->nib_rev)))
+                    b->offsets.push_back(b->offsets.back() + b->nib_len.back());
+                cur = nullptr;
+                if (b->ids.empty()) { pool.put(std::move(b)); break; }
+                b->raw_kind = 'B';
+                const double t1 = now();
+                push(std::move(b));
+                blocked += now() - t1;
+            }
+            if (tune_env("TAXOR_CLI_TRACE"))
+                fprintf(stderr, "[trace] BAM %s: %llu records, %llu skipped as secondary or supplementary (flag & 0x900), blocks inflated %s, %llu chunks, walker %.3f s\n",
+                        query.c_str(), (unsigned long long)rd.ordinal, (unsigned long long)rd.n_skipped, rd.use_members ? "in parallel" : "as one zlib stream",
+                        (unsigned long long)n_pushed.load(), now() - t_begin - blocked);
+        } catch (const std::exception &ex) { die(ex.what()); }
+        finish();
+        return now() - t_begin - blocked;
     }
     fastx::FastxReader rd;
     fastx::GzMembers members;
@@ -509,6 +577,7 @@ double produce_batches(const std::string &query, const Config &cfg, bool allow_r
                             bt->seq = job.seq;
                             bt->may_pin = true;
                             ++bt->fills;
+                            drop_raw(*bt);
                             const size_t need = fastx::bases_bound(job.bytes, kind);
                             if (need > bt->bases.capacity()) {
                                 if (bt->pinned) { taxor_gpu_host_unregister(bt->pinned); bt->pinned = nullptr; }
@@ -599,6 +668,7 @@ double produce_batches(const std::string &query, const Config &cfg, bool allow_r
             // appends without a size bound, so the string can reallocate: give the registration up first (a stale
             // registration over freed memory would be a DMA source) and do not pin batches of this path again
             if (b->pinned) { taxor_gpu_host_unregister(b->pinned); b->pinned = nullptr; }
+            drop_raw(*b);
             b->may_pin = false;
             b->seq = seq++;
             b->ids.clear();
@@ -1197,16 +1267,17 @@ int main(int argc, char **argv)
     if (argc > 1 && strcmp(argv[1], "pin") == 0) return pin_command(argc, argv);   // published .hixf + reference TSV -> committed parity fixture
     if (argc > 1 && strcmp(argv[1], "reads") == 0) {                       // reader check: id, length, FNV-1a of every record
         Config cfg;
-        bool allow_ranges = true;
+        bool allow_ranges = true, summary_only = false;
         for (int i = 2; i < argc; ++i) {
             if (strcmp(argv[i], "--query-file") == 0 && i + 1 < argc) cfg.query_file = argv[++i];
             else if (strcmp(argv[i], "--threads") == 0 && i + 1 < argc) cfg.threads = (unsigned)atoi(argv[++i]);
             else if (strcmp(argv[i], "--batch-reads") == 0 && i + 1 < argc) cfg.batch_reads = strtoull(argv[++i], nullptr, 10);
             else if (strcmp(argv[i], "--batch-bases") == 0 && i + 1 < argc) cfg.batch_bases = strtoull(argv[++i], nullptr, 10);      // (tests: small parser jobs)
             else if (strcmp(argv[i], "--sequential") == 0) allow_ranges = false;
+            else if (strcmp(argv[i], "--summary-only") == 0) summary_only = true;      // the reader's rate: no record is printed or hashed
         }
         if (cfg.threads == 0) cfg.threads = 1;
-        if (cfg.query_file.empty() || !file_exists(cfg.query_file)) die("usage: taxor reads --query-file <fasta|fastq[.gz]> [--threads n] [--batch-reads n] [--sequential]");
+        if (cfg.query_file.empty() || !file_exists(cfg.query_file)) die("usage: taxor reads --query-file <fasta|fastq[.gz]|bam> [--threads n] [--batch-reads n] [--batch-bases n] [--sequential] [--summary-only]");
         std::mutex mu;
         std::map<uint64_t, std::unique_ptr<Batch>> got;
         BatchPool pool;
@@ -1220,8 +1291,15 @@ int main(int argc, char **argv)
         for (const auto &kv : got) {
             if (kv.first != expect++) die("batch numbering has a gap");
             const Batch &b = *kv.second;
+            std::string restored;
+            if (summary_only) { n += b.ids.size(); nb += b.offsets.back(); continue; }
             for (size_t r = 0; r < b.ids.size(); ++r) {
                 const uint64_t lo = b.offsets[r], len = b.offsets[r + 1] - lo;
+                if (b.raw_kind == 'B') {        // BAM: the read the record stands for (reverse-complemented back where flag 0x10 is set)
+                    restored.clear();
+                    bam::restore_read((const uint8_t *)b.raw.data() + b.nib_off[r], b.nib_len[r], b.nib_rev[r] != 0, restored);
+                    printf("%s\t%llu\t%016llx\n", b.ids.str(r).c_str(), (unsigned long long)len, (unsigned long long)fnv1a(restored.data(), restored.size()));
+                } else
                 printf("%s\t%llu\t%016llx\n", b.ids.str(r).c_str(), (unsigned long long)len, (unsigned long long)fnv1a(b.bases.data() + lo, len));
                 ++n;
                 nb += len;
@@ -1329,7 +1407,11 @@ int main(int argc, char **argv)
                             "                           over the query file per group, the file is parsed -- a .gz inflated -- once per pass) and every\n"
                             "                           read's results are merged on the device.  Taken by itself when the index exceeds the device's\n"
                             "                           free memory.  ONE device, a query file that can be read again (no pipe); the output is\n"
-                            "                           byte-identical to the resident search.\n");
+                            "                           byte-identical to the resident search.  A BAM query file is read once per pass like any other.\n"
+                            "BAM input: the BGZF blocks are inflated on --threads threads, one thread walks the records (block_size, flag, l_seq, read_name)\n"
+                            "                           and copies the 4-bit SEQ fields into a page-locked buffer; CIGAR, QUAL and tags are never read.  A\n"
+                            "                           missing BGZF end-of-file block is a warning; CRAM and SAM text are refused.  With TAXOR_CLI_TRACE the\n"
+                            "                           run reports how many records were skipped as secondary or supplementary.\n");
             return 0;
         }
         else if (k == "-h" || k == "--help") { usage(); return 0; }
@@ -1389,6 +1471,9 @@ int main(int argc, char **argv)
     }
     for (const auto &f : query_files)
         if (!file_exists(f)) die("Please check the given input query files. \nThe following query file does not exist: " + f);
+    for (const auto &f : query_files) {           // CRAM and SAM text are refused by name, before any HIP call
+        try { (void)bam::sniff(f); } catch (const std::exception &e) { die(e.what()); }
+    }
     if (!cfg.expect_file.empty() && !file_exists(cfg.expect_file)) die("The expected-output file does not exist: " + cfg.expect_file);
     printf("done!\n");
     trace("input checked");
@@ -1518,9 +1603,16 @@ int main(int argc, char **argv)
                             const uint64_t n = bt.ids.size();
                             const double t1 = now();
                             taxor_gpu_results res{};
-                            auto run = [&] { return taxor_gpu_search_batch(s, bt.bases.data(), bt.offsets.data(), n, &res); };
+                            const bool nibbles = bt.raw_kind == 'B';      // a BAM chunk: its 4-bit sequences are unpacked on the device
+                            bt.raw_kind = 0;
+                            auto run = [&]() -> int {
+                                if (!nibbles) return taxor_gpu_search_batch(s, bt.bases.data(), bt.offsets.data(), n, &res);
+                                const taxor_nibble_segment seg{(const uint8_t *)bt.raw.data(), bt.nib_off.data(), bt.nib_len.data(), bt.nib_rev.data(), n};
+                                const int rb = taxor_gpu_search_nibbles_begin(s, &seg, 1);
+                                return rb != TAXOR_OK ? rb : taxor_gpu_search_batch_end(s, &res);
+                            };
                             int rc = run();
-                            if (rc == TAXOR_E_ALPHABET && strip_space_and_digits(bt)) rc = run();
+                            if (rc == TAXOR_E_ALPHABET && !nibbles && strip_space_and_digits(bt)) rc = run();
                             if (rc != TAXOR_OK) die(taxor_gpu_last_error());
                             if (store.size() <= bi) store.resize(bi + 1);
                             if (!last_pass) {
@@ -1661,6 +1753,10 @@ int main(int argc, char **argv)
                     if (!b->end_of_file && b->may_pin && !b->pinned && b->fills >= pin_after && b->bases.capacity() >= (1u << 20) &&
                         taxor_gpu_host_register(&b->bases[0], b->bases.capacity()) == TAXOR_OK)
                         b->pinned = &b->bases[0];       // recycled with the chunk: a DMA source from then on
+                    // a BAM chunk's SEQ bytes go to the device as they are: page-locked here, beside the walker, once per buffer
+                    if (!b->end_of_file && b->raw_kind == 'B' && !b->raw_pinned && b->raw.capacity() >= (1u << 20) &&
+                        taxor_gpu_host_register(b->raw.data(), b->raw.capacity()) == TAXOR_OK)
+                        b->raw_pinned = b->raw.data();
                     q_in.push(std::move(b));
                 }
             });
@@ -1880,6 +1976,7 @@ int main(int argc, char **argv)
         // s, ids and offsets are filled from the scanner's table; 1 = the device reported the bytes irregular (or met a byte outside
         // dna15, which the parsed path may still repair) and the chunk was parsed here by the reader a range thread would have used
         // (the same records, the same messages for a malformed file) -- it goes on like any parsed chunk; -1 = err says why
+        std::atomic<uint64_t> n_bam{0};        // BAM chunks unpacked on the device
         std::atomic<uint64_t> n_scanned{0}, n_host_parsed{0}, n_pageable{0};   // n_pageable: chunks whose buffer could not be page-locked
         auto host_parse = [](Batch &bt) -> std::string {
             try {
@@ -1901,6 +1998,13 @@ int main(int argc, char **argv)
             return std::string();
         };
         auto scan_begin = [&](taxor_gpu_searcher *s, Batch &bt, std::string &err) -> int {
+            if (bt.raw_kind == 'B') {       // a BAM chunk: ids and lengths are the reader's, the device unpacks the 4-bit sequences
+                const taxor_nibble_segment seg{(const uint8_t *)bt.raw.data(), bt.nib_off.data(), bt.nib_len.data(), bt.nib_rev.data(), bt.ids.size()};
+                if (taxor_gpu_search_nibbles_begin(s, &seg, 1) != TAXOR_OK) { err = taxor_gpu_last_error(); return -1; }
+                bt.raw_kind = 0;
+                ++n_bam;
+                return 0;
+            }
             taxor_fastx_scan sc{};
             if (!bt.raw_pinned) ++n_pageable;
             const int rc = taxor_gpu_search_fastx_begin(s, bt.raw.data(), bt.raw.size(), bt.raw_kind, &sc);
@@ -2132,6 +2236,8 @@ int main(int argc, char **argv)
         if (cfg.device_parse && tune_env("TAXOR_CLI_TRACE"))
             fprintf(stderr, "[trace] --device-parse: %llu ranges scanned on the device, %llu parsed on the host; %llu copied from pageable memory\n",
                     (unsigned long long)n_scanned.load(), (unsigned long long)n_host_parsed.load(), (unsigned long long)n_pageable.load());
+        if (n_bam.load() && tune_env("TAXOR_CLI_TRACE"))
+            fprintf(stderr, "[trace] BAM: %llu chunks of 4-bit sequences unpacked on the device\n", (unsigned long long)n_bam.load());
         t_search_wall += now() - t_search0;
         if (tune_env("TAXOR_CLI_TRACE")) {
             const CpuMark c1 = cpu_mark();

@@ -423,6 +423,45 @@ class Searcher:
         ids = [buf[int(a):int(a + l)].tobytes() for a, l in zip(id_off, id_len)]
         return FastxResults(0, _results(res), ids, read_len)
 
+    @staticmethod
+    def _nibble_segments(segments):
+        """[(seq4 bytes, byte_off, read_len, reverse or None), ...] -> (taxor_nibble_segment array, what must stay alive)"""
+        keep = []
+        arr = (_lib.NibbleSegment * max(1, len(segments)))()
+        for i, (seq4, boff, rlen, rev) in enumerate(segments):
+            q = np.ascontiguousarray(np.frombuffer(bytes(seq4), dtype=np.uint8) if isinstance(seq4, (bytes, bytearray)) else seq4, dtype=np.uint8)
+            o = np.ascontiguousarray(boff, dtype=np.uint64)
+            n = np.ascontiguousarray(rlen, dtype=np.uint32)
+            v = None if rev is None else np.ascontiguousarray(rev, dtype=np.uint8)
+            assert o.size == n.size and (v is None or v.size == n.size)
+            keep += [q, o, n, v]
+            arr[i] = _lib.NibbleSegment(q.ctypes.data if q.size else None, o.ctypes.data if o.size else None, n.ctypes.data if n.size else None,
+                                        None if v is None else v.ctypes.data, n.size)
+        return arr, keep
+
+    def search_nibbles(self, segments) -> SearchResults:
+        """one batch over reads stored at 4 bits per base (a BAM record's SEQ field): segments = [(seq4, byte_off, read_len,
+        reverse or None), ...] (taxor_gpu_search_nibbles_begin + _batch_end)"""
+        arr, keep = self._nibble_segments(segments)
+        check(_lib.lib().taxor_gpu_search_nibbles_begin(self._h, arr, len(segments)))
+        res = _lib.Results()
+        check(_lib.lib().taxor_gpu_search_batch_end(self._h, C.byref(res)))
+        del keep
+        return _results(res)
+
+    def pack_nibbles(self, segments, timed=False):
+        """k_pack_nibbles alone (taxor_gpu_pack_nibbles) -> (word_off uint64[n+1], words uint32[]) in k_pack_dna4's layout
+        [, the kernel's HIP-event milliseconds]"""
+        arr, keep = self._nibble_segments(segments)
+        wo, ws, ms = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)(), C.c_float(0)
+        check(_lib.lib().taxor_gpu_pack_nibbles(self._h, arr, len(segments), C.byref(wo), C.byref(ws), C.byref(ms) if timed else None))
+        n = sum(int(a.n_reads) for a in arr[:len(segments)])
+        woff = np.ctypeslib.as_array(wo, shape=(n + 1,)).copy()
+        tot = int(woff[n])
+        words = np.ctypeslib.as_array(ws, shape=(tot,)).copy() if tot else np.zeros(0, np.uint32)
+        del keep
+        return (woff, words, float(ms.value)) if timed else (woff, words)
+
     def search_batch_end(self) -> SearchResults:
         res = _lib.Results()
         check(_lib.lib().taxor_gpu_search_batch_end(self._h, C.byref(res)))
@@ -460,6 +499,13 @@ class Searcher:
     def upload(self, bases, offsets):
         b, o = self._batch(bases, offsets)
         check(_lib.lib().taxor_gpu_batch_upload(self._h, _p(b), _p(o), o.size - 1))
+
+    def upload_timed(self, bases, offsets):
+        """upload() -> HIP-event milliseconds of its packing kernel, k_pack_dna4 (taxor_gpu_pack_dna4_timed)"""
+        b, o = self._batch(bases, offsets)
+        ms = C.c_float(0)
+        check(_lib.lib().taxor_gpu_pack_dna4_timed(self._h, _p(b), _p(o), o.size - 1, C.byref(ms)))
+        return float(ms.value)
 
     def run(self):
         check(_lib.lib().taxor_gpu_batch_run(self._h))
@@ -572,3 +618,38 @@ class Comm:
         st = _lib.CommStats()
         check(_lib.lib().taxor_gpu_comm_info(self._h, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _lib.CommStats._fields_}
+
+
+def read_bam(path):
+    """The reads of a BAM file as `taxor search` selects them (SAMv1 section 4.2; secondary and supplementary records left out):
+    (ids [bytes], seq4 uint8[], byte_off uint64[], read_len uint32[], reverse uint8[]) -- the SEQ fields back to back, what
+    Searcher.search_nibbles / pack_nibbles take.  Plain Python over gzip; for tests and small files."""
+    import gzip
+    import struct
+    with gzip.open(path, "rb") as f:
+        raw = f.read()
+    if raw[:4] != b"BAM\1":
+        raise ValueError(f"{path}: not BAM")
+    l_text, = struct.unpack_from("<i", raw, 4)
+    p = 8 + l_text
+    n_ref, = struct.unpack_from("<i", raw, p)
+    p += 4
+    for _ in range(n_ref):
+        l_name, = struct.unpack_from("<i", raw, p)
+        p += 4 + l_name + 4
+    ids, seq, boff, rlen, rev = [], bytearray(), [], [], []
+    while p < len(raw):
+        block_size, = struct.unpack_from("<I", raw, p)
+        l_read_name, = struct.unpack_from("<B", raw, p + 12)
+        n_cigar, flag, l_seq = struct.unpack_from("<HHi", raw, p + 16)
+        name_at = p + 36
+        if not flag & 0x900:
+            ids.append(raw[name_at:name_at + l_read_name - 1])
+            at = name_at + l_read_name + 4 * n_cigar
+            boff.append(len(seq))
+            rlen.append(l_seq)
+            rev.append(1 if flag & 0x10 else 0)
+            seq += raw[at:at + (l_seq + 1) // 2]
+        p += 4 + block_size
+    return (ids, np.frombuffer(bytes(seq), dtype=np.uint8), np.array(boff, dtype=np.uint64), np.array(rlen, dtype=np.uint32),
+            np.array(rev, dtype=np.uint8))
