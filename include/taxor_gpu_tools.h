@@ -205,6 +205,33 @@ typedef struct {
 int taxor_build_layout(const uint64_t *counts, uint64_t n, uint64_t t_max, taxor_layout **out);
 void taxor_layout_free(taxor_layout *l);
 
+/* ---- `taxor build --group-similar`: similar genomes under one merged bin (taxor_amd/csrc/sketch.hip, host_util.cpp; DESIGN.md
+ * section 9, "Similarity-aware layout").
+ * taxor_gpu_keys_sketch: bin b's keys are keys[off[b] .. off[b+1]) (host memory, or device memory with keys_on_device), distinct, as
+ * taxor_gpu_keyer_finish delivers them.  sketch[b*m ..] receives the min(m, n_b) smallest values of mix(key), ascending, len[b] how
+ * many; both in host memory, slots past len[b] unspecified.  mix is the fixed bijection of DESIGN.md.  m in [1, 1024].  Exact. */
+int taxor_gpu_keys_sketch(int device, const uint64_t *keys, int keys_on_device, const uint64_t *off, uint64_t n_bins, uint32_t m,
+                          uint64_t *sketch, uint32_t *len);
+/* All pairs of n sketches, n in [1, 8192]; count[b] = keys of bin b, len[b] = min(count[b], m) (else TAXOR_E_ARG).  A sketch is
+ * complete when count[b] <= m, then tau_b = 2^64 - 1, else tau_b is its largest value; tau = min(tau_a, tau_b);
+ * shared[a*n + b] = values <= tau present in both sketches, uni[a*n + b] = |A <= tau| + |B <= tau| - shared.  kernel_ms (may be NULL)
+ * receives the kernel's HIP-event time. */
+int taxor_gpu_sketch_pairs(int device, const uint64_t *sketch, const uint32_t *len, const uint64_t *count, uint64_t n, uint32_t m,
+                           uint32_t *shared, uint32_t *uni, float *kernel_ms);
+/* Host only.  Rows i and j are linked when uni > 0 && (double)shared >= jmin * (double)uni; clusters are the connected components
+ * (single linkage), ordered by their smallest member, members in ascending row order.  order[n]: that permutation of 0 .. n-1;
+ * cluster[i] (may be NULL): the ordinal of row i's cluster. */
+int taxor_cluster_order(const uint32_t *shared, const uint32_t *uni, uint64_t n, double jmin, uint64_t *order, uint64_t *cluster);
+/* The global rank: the bins in descending key count (ties on index) are cut into consecutive windows of `window` bins (in [2, 8192]),
+ * each window goes through taxor_gpu_sketch_pairs and taxor_cluster_order, and rank[u] is u's position in the concatenation of the
+ * windows' orders.  sketch / len as taxor_gpu_keys_sketch left them for all n bins.  *n_multi (may be NULL): clusters with more than
+ * one member; *pairs_ms (may be NULL): the pairs kernel's time summed over the windows. */
+int taxor_similarity_rank(int device, const uint64_t *sketch, const uint32_t *len, const uint64_t *counts, uint64_t n, uint32_t m,
+                          uint64_t window, double jmin, uint64_t *rank, uint64_t *n_multi, float *pairs_ms);
+/* taxor_build_layout with one change: in every IXF the user bins that do not stay leaves are ordered by rank[u] (ascending; ties keep
+ * the count order) instead of by count before they are cut into contiguous groups.  rank == NULL gives taxor_build_layout's result. */
+int taxor_build_layout_ranked(const uint64_t *counts, uint64_t n, uint64_t t_max, const uint64_t *rank, taxor_layout **out);
+
 /* ---- search of an index that does not fit the device ("Search beyond device memory").  A child IXF is reached
  * only through one merged bin of its parent, so the root stays resident and the SUBTREES -- one merged bin of the root with everything
  * below it -- are brought in group by group: every read is searched once per pass against "root + this pass's group", and per read the

@@ -219,6 +219,12 @@ SIGNATURES = {
     "taxor_gpu_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "taxor_build_layout": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(Layout))]),
     "taxor_layout_free": (None, [C.POINTER(Layout)]),
+    "taxor_gpu_keys_sketch": (C.c_int, [C.c_int, _P, C.c_int, _P, C.c_uint64, C.c_uint32, _P, _P]),
+    "taxor_gpu_sketch_pairs": (C.c_int, [C.c_int, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
+    "taxor_cluster_order": (C.c_int, [_P, _P, C.c_uint64, C.c_double, _P, _P]),
+    "taxor_similarity_rank": (C.c_int, [C.c_int, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint64, C.c_double, _P, C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_float)]),
+    "taxor_build_layout_ranked": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.POINTER(C.POINTER(Layout))]),
     "taxor_synth_key": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "taxor_gpu_synth_keys": (C.c_int, [C.c_int, _P, C.c_uint64, C.c_uint64, C.c_uint64]),
     "taxor_gpu_malloc": (C.c_int, [C.c_int, C.c_uint64, C.POINTER(_P)]),

@@ -21,6 +21,9 @@ struct BuildConfig {
     uint64_t tmax = 0;            // hidden: force one t_max (0 = choose, taxor_build.cpp:168-233)
     uint64_t key_budget_mib = 0;  // hidden: MiB of distinct keys on the device at a time (0 = an eighth of the free device memory)
     uint64_t host_memory_mib = 0; // hidden: the host memory the key store is held against (0 = MemAvailable)
+    bool group_similar = false;   // order the user bins of a merged level by sketch similarity ("Similarity-aware layout")
+    long sketch_size = 1024, similarity_window = 4096;   // hidden
+    double similarity_threshold = 0.1;                    // hidden
 };
 
 const char *const BUILD_ADVANCED_HELP =
@@ -32,6 +35,14 @@ const char *const BUILD_ADVANCED_HELP =
     "                                from there, byte-identical to a build with every key resident (default: such a build is chosen\n"
     "                                when the keys may not fit the free device memory, with an eighth of it as the budget)\n"
     "    --host-memory-mib <MiB>     host memory the key store of such a build may take, in [1,1073741824] (default: MemAvailable)\n"
+    "    --group-similar             group similar genomes under one merged bin: the genomes' key sets are sketched and compared on\n"
+    "                                the device, and the user bins of a merged level are ordered by similarity cluster instead of by\n"
+    "                                key count before they are cut into groups (default: off; works with every route above)\n"
+    "    --sketch-size <m>           values per sketch, in [16,1024] (default: 1024)\n"
+    "    --similarity-window <W>     genomes compared with one another: consecutive runs of W in descending key count, in [2,8192]\n"
+    "                                (default: 4096)\n"
+    "    --similarity-threshold <J>  two genomes are linked when the estimated Jaccard index of their key sets reaches J, in (0,1]\n"
+    "                                (default: 0.1, about 92.5 % identity at k = 22)\n"
     "ranges of the syncmer scheme (--use-syncmer)\n"
     "    --syncmer-size <s>          in [1,26] and below --kmer-size (at most 30 with syncmers); every such pair is built, and `taxor\n"
     "                                search` takes syncmer indexes of any s-mer size from 1 to 31 with k-mer sizes up to 32\n";
@@ -143,11 +154,12 @@ int build_command(int argc, char **argv)
         const bool has_v = i + 1 < args.size();
         if (o == "--advanced-help" || o == "-hh") { fputs(BUILD_ADVANCED_HELP, stdout); return 0; }
         else if (o == "--use-syncmer") c.use_syncmer = true;
+        else if (o == "--group-similar") c.group_similar = true;
         else if (o == "--output-verbose-statistics") c.verbose = true;
         else if (o == "--debug") c.debug = true;
         else if (o == "--input-file" || o == "--input-sequence-dir" || o == "--output-filename" || o == "--kmer-size" || o == "--syncmer-size" ||
                  o == "--window-size" || o == "--scaling" || o == "--threads" || o == "--gpu" || o == "--tmax" || o == "--device-key-budget" ||
-                 o == "--host-memory-mib") {
+                 o == "--host-memory-mib" || o == "--sketch-size" || o == "--similarity-window" || o == "--similarity-threshold") {
             if (!has_v) return build_error("Missing value for option " + o);
             const std::string v = args[++i];
             long tmp = 0;
@@ -163,6 +175,16 @@ int build_command(int argc, char **argv)
             else if (o == "--tmax") { if (!number(o, v, 2, 1 << 20, &tmp, err)) return build_error(err); c.tmax = (uint64_t)tmp; }
             else if (o == "--device-key-budget") { if (!number(o, v, 1, 1 << 24, &tmp, err)) return build_error(err); c.key_budget_mib = (uint64_t)tmp; }
             else if (o == "--host-memory-mib") { if (!number(o, v, 1, 1 << 30, &tmp, err)) return build_error(err); c.host_memory_mib = (uint64_t)tmp; }
+            else if (o == "--sketch-size" && !number(o, v, 16, 1024, &c.sketch_size, err)) return build_error(err);
+            else if (o == "--similarity-window" && !number(o, v, 2, 8192, &c.similarity_window, err)) return build_error(err);
+            else if (o == "--similarity-threshold") {
+                char *end = nullptr;
+                errno = 0;
+                const double x = strtod(v.c_str(), &end);
+                if (v.empty() || *end || errno) return build_error("Value parse failed for " + o + ": Argument " + v + " could not be parsed as type double.");
+                if (!(x > 0.0 && x <= 1.0)) return build_error("Validation failed for option " + o + ": Value " + v + " is not in range (0,1].");
+                c.similarity_threshold = x;
+            }
         } else
             return build_error("Unknown option " + o + ". In case this is meant to be a non-option/argument/parameter, please specify the start of "
                                "non-options with '--'. See -h/--help for program information.");
@@ -318,6 +340,21 @@ int build_command(int argc, char **argv)
     taxor_keyer_stats ks{};
     const uint64_t *bin_off = nullptr, *d_keys = nullptr;
     const uint64_t n_waves = wave_first.size() - 1;
+    // --group-similar: every keyer's bins are sketched while it holds their keys on the device
+    const uint32_t sk_m = (uint32_t)c.sketch_size;
+    std::vector<uint64_t> sketch;
+    std::vector<uint32_t> sketch_len;
+    double sketch_seconds = 0;
+    if (c.group_similar) {
+        sketch.resize(n * sk_m);
+        sketch_len.resize(n);
+    }
+    auto sketch_wave = [&](uint64_t g0, uint64_t g1, const uint64_t *off, const uint64_t *keys_on_device) {
+        const double t0 = now();
+        const int rc = taxor_gpu_keys_sketch(c.device, keys_on_device, 1, off, g1 - g0, sk_m, sketch.data() + g0 * sk_m, sketch_len.data() + g0);
+        sketch_seconds += now() - t0;
+        return rc == TAXOR_OK;
+    };
     if (stream && !store.reserve(bound_total)) return build_error("no address space for a key store of " + std::to_string(bound_total * 8 >> 20) + " MiB");
     for (uint64_t w = 0; w < n_waves; ++w) {
         const uint64_t g0 = wave_first[w], g1 = wave_first[w + 1];
@@ -328,11 +365,13 @@ int build_command(int argc, char **argv)
         if (!err.empty()) return build_error(err);
         if (!stream) {
             if (taxor_gpu_keyer_finish(kr, &bin_off, nullptr, &d_keys) != TAXOR_OK) return build_error(taxor_gpu_last_error());
+            if (c.group_similar && !sketch_wave(0, n, bin_off, d_keys)) return build_error(taxor_gpu_last_error());
             break;                                                        // (the resident keyer lives until the index is built)
         }
         // the wave's sorted, distinct keys per bin: into the store, and the keyer goes before the next one comes
-        const uint64_t *w_off = nullptr, *w_keys = nullptr;
-        if (taxor_gpu_keyer_finish(kr, &w_off, &w_keys, nullptr) != TAXOR_OK) return build_error(taxor_gpu_last_error());
+        const uint64_t *w_off = nullptr, *w_keys = nullptr, *w_dkeys = nullptr;
+        if (taxor_gpu_keyer_finish(kr, &w_off, &w_keys, &w_dkeys) != TAXOR_OK) return build_error(taxor_gpu_last_error());
+        if (c.group_similar && !sketch_wave(g0, g1, w_off, w_dkeys)) return build_error(taxor_gpu_last_error());
         if (!store.append(w_keys, w_off, g1 - g0)) return build_error("the key store is full: the genomes hold more distinct keys than their density bound");
         taxor_keyer_stats wks{};
         (void)taxor_gpu_keyer_stats(kr, &wks);
@@ -346,7 +385,20 @@ int build_command(int argc, char **argv)
     std::vector<uint64_t> counts(n);
     for (uint64_t b = 0; b < n; ++b) counts[b] = bin_off[b + 1] - bin_off[b];
     taxor_layout *lay = nullptr;
-    if (taxor_build_layout(counts.data(), n, c.tmax, &lay) != TAXOR_OK) return build_error("layout failed");
+    uint64_t sim_clusters = 0;
+    double pairs_seconds = 0;
+    if (c.group_similar) {
+        // windows of genomes of similar size: all pairs on the device, single-linkage clusters, and the layout cuts along that order
+        std::vector<uint64_t> rank(n);
+        const double t0 = now();
+        if (taxor_similarity_rank(c.device, sketch.data(), sketch_len.data(), counts.data(), n, sk_m, (uint64_t)c.similarity_window, c.similarity_threshold,
+                                  rank.data(), &sim_clusters, nullptr) != TAXOR_OK)
+            return build_error(taxor_gpu_last_error());
+        pairs_seconds = now() - t0;
+        std::vector<uint64_t>().swap(sketch);
+        if (taxor_build_layout_ranked(counts.data(), n, c.tmax, rank.data(), &lay) != TAXOR_OK) return build_error("layout failed");
+    } else if (taxor_build_layout(counts.data(), n, c.tmax, &lay) != TAXOR_OK)
+        return build_error("layout failed");
     std::unique_ptr<taxor_layout, void (*)(taxor_layout *)> lay_guard(lay, taxor_layout_free);
     const uint64_t n_ixf = lay->n_ixf;
     // user bins below each IXF (merged bins need the exact union of their subtree)
@@ -487,13 +539,21 @@ int build_command(int argc, char **argv)
     const double t_end = now();
     uint64_t n_keys = 0;
     for (uint64_t b = 0; b < n; ++b) n_keys += counts[b];
+    std::string similar;
+    if (c.group_similar) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "; similar genomes grouped: %llu clusters of more than one genome, sketches %.3f s, pairs and clustering %.3f s",
+                 (unsigned long long)sim_clusters, sketch_seconds, pairs_seconds);
+        similar = buf;
+    }
     fprintf(stderr,
             "taxor build: %llu genomes, %llu bases (%llu file bytes), %llu distinct keys, %llu IXFs, depth %u, %llu index bytes, t_max %llu; "
             "seconds: read+key %.3f (keyer on the device %.3f), layout %.3f, construction %.3f, store %.3f, total %.3f; "
-            "path %s: %llu waves, %u groups, %u bin ranges, %u restarts, key uploads %.3f s of which %.3f s were waited for\n",
+            "path %s: %llu waves, %u groups, %u bin ranges, %u restarts, key uploads %.3f s of which %.3f s were waited for%s\n",
             (unsigned long long)n, (unsigned long long)n_bases, (unsigned long long)file_bytes, (unsigned long long)n_keys,
-            (unsigned long long)n_ixf, depth, (unsigned long long)index_bytes, (unsigned long long)lay->t_max, t_key1 - t_key0, ks.seconds_device, t_lay - t_key1,
+            (unsigned long long)n_ixf, depth, (unsigned long long)index_bytes, (unsigned long long)lay->t_max, t_key1 - t_key0 - sketch_seconds, ks.seconds_device,
+            t_lay - t_key1 - pairs_seconds,
             t_build - t_lay, t_end - t_build, t_end - t_start, stream ? "stream" : "resident", (unsigned long long)n_waves, bst.stream_groups, bst.stream_ranges,
-            bst.stream_restarts, bst.seconds_upload + bst.seconds_stream_upload, bst.seconds_upload + bst.seconds_stream_upload_wait);
+            bst.stream_restarts, bst.seconds_upload + bst.seconds_stream_upload, bst.seconds_upload + bst.seconds_stream_upload_wait, similar.c_str());
     return 0;
 }

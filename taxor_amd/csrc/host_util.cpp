@@ -311,6 +311,8 @@ int taxor_synth_reads(const char *genomes, const uint64_t *genome_off, uint64_t 
 //   n > t_max: user bins of at least total / t_max keys stay leaves (split into floor(count / (total / t_max)) parts), the rest,
 //     in descending count order, are cut into the remaining bins as contiguous groups of about equal weight; a group of one is a
 //     leaf, a larger group a merged bin whose child IXF is laid out the same way.
+//   with a rank (taxor_build_layout_ranked, `taxor build --group-similar`): the rest is ordered by rank instead of by count before it
+//     is cut, in every IXF of the tree; which bins stay leaves does not change.
 // Deterministic: ties break on the user bin's index.
 namespace {
 
@@ -322,6 +324,7 @@ struct LayIxf {
 
 struct LayBuild {
     const uint64_t *cnt;
+    const uint64_t *rank = nullptr;   // --group-similar: the order of the bins that are cut into groups (null: their count order)
     uint64_t T;
     std::vector<LayIxf> ixfs;
     std::vector<uint32_t> level;
@@ -376,6 +379,8 @@ struct LayBuild {
                 else { sum_p -= lv.back().second; lv.pop_back(); --d; }
             }
             const uint64_t M = T - sum_p;                  // bins for the S[d..n) (n - d > M: there are more of them than bins)
+            if (rank)                                      // similar bins stand together; ties keep the count order
+                std::stable_sort(S.begin() + (ptrdiff_t)d, S.end(), [&](uint32_t a, uint32_t b) { return rank[a] < rank[b]; });
             double rest = 0;
             for (uint64_t i = d; i < n; ++i) rest += (double)cnt[S[i]];
             uint64_t i = d;
@@ -426,10 +431,11 @@ struct LayoutOwned {
     std::vector<int64_t> next, fname;
 };
 
-LayoutOwned *layout_for(const uint64_t *counts, uint64_t n, uint64_t T)
+LayoutOwned *layout_for(const uint64_t *counts, uint64_t n, uint64_t T, const uint64_t *rank)
 {
     LayBuild lb;
     lb.cnt = counts;
+    lb.rank = rank;
     lb.T = T;
     std::vector<uint32_t> all(n);
     for (uint64_t i = 0; i < n; ++i) all[i] = (uint32_t)i;
@@ -490,6 +496,11 @@ extern "C" {
 
 int taxor_build_layout(const uint64_t *counts, uint64_t n, uint64_t t_max, taxor_layout **out)
 {
+    return taxor_build_layout_ranked(counts, n, t_max, nullptr, out);
+}
+
+int taxor_build_layout_ranked(const uint64_t *counts, uint64_t n, uint64_t t_max, const uint64_t *rank, taxor_layout **out)
+{
     if (!out) return TAXOR_E_ARG;
     *out = nullptr;
     if (!counts || n == 0 || n >= (1ull << 31) || (t_max && t_max < 2)) return TAXOR_E_ARG;
@@ -501,7 +512,7 @@ int taxor_build_layout(const uint64_t *counts, uint64_t n, uint64_t t_max, taxor
     }
     LayoutOwned *best = nullptr;
     for (const uint64_t T : cand) {                                              // ascending: ties keep the smaller t_max
-        LayoutOwned *L = layout_for(counts, n, T);
+        LayoutOwned *L = layout_for(counts, n, T, rank);
         if (!best || L->pub.bytes_per_hash < best->pub.bytes_per_hash ||
             (L->pub.bytes_per_hash == best->pub.bytes_per_hash && L->pub.index_bytes < best->pub.index_bytes)) {
             delete best;
@@ -516,6 +527,45 @@ int taxor_build_layout(const uint64_t *counts, uint64_t n, uint64_t t_max, taxor
 void taxor_layout_free(taxor_layout *l)
 {
     delete reinterpret_cast<LayoutOwned *>(l);   // pub is the first member
+}
+
+// ---- the similarity order of `taxor build --group-similar` ("Similarity-aware layout")
+int taxor_cluster_order(const uint32_t *shared, const uint32_t *uni, uint64_t n, double jmin, uint64_t *order, uint64_t *cluster)
+{
+    if (!shared || !uni || !order || n == 0 || n >= (1ull << 31) || !(jmin > 0.0)) return TAXOR_E_ARG;
+    std::vector<uint32_t> up(n);                          // union-find; a root is the smallest member of its set
+    for (uint64_t i = 0; i < n; ++i) up[i] = (uint32_t)i;
+    auto find = [&](uint32_t x) {
+        while (up[x] != x) x = up[x] = up[up[x]];
+        return x;
+    };
+    for (uint64_t i = 0; i < n; ++i)
+        for (uint64_t j = i + 1; j < n; ++j) {
+            const uint32_t s = shared[i * n + j], u = uni[i * n + j];
+            if (u > 0 && (double)s >= jmin * (double)u) {
+                const uint32_t a = find((uint32_t)i), b = find((uint32_t)j);
+                if (a != b) up[std::max(a, b)] = std::min(a, b);
+            }
+        }
+    // clusters in the order of their smallest member = of their roots; members ascending
+    std::vector<uint64_t> ordinal(n, 0), size(n, 0), at(n, 0);
+    uint64_t nc = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t r = find((uint32_t)i);
+        if (r == i) ordinal[i] = nc++;
+        ++size[ordinal[r]];                               // (a root comes before every other member)
+    }
+    uint64_t run = 0;
+    for (uint64_t c = 0; c < nc; ++c) {
+        at[c] = run;
+        run += size[c];
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t c = ordinal[find((uint32_t)i)];
+        order[at[c]++] = i;
+        if (cluster) cluster[i] = c;
+    }
+    return TAXOR_OK;
 }
 
 // ---- taxor_index_plan_passes: which IXFs a search of an index larger than the device holds together (DESIGN.md section 9,

@@ -107,12 +107,83 @@ def keys_union(lists, device=0, want_keys=True, on_device=False):
             L.taxor_gpu_free(d)
 
 
-def build_layout(counts, t_max=0):
+def keys_sketch(keys, off, m, device=0, on_device=False):
+    """taxor_gpu_keys_sketch: bottom-m sketches of the bins keys[off[b]:off[b+1]] (distinct keys) -> (sketch uint64[n_bins, m],
+    len uint32[n_bins]); row b holds the len[b] = min(m, n_b) smallest mix(key), ascending.  on_device: the keys are first put into
+    device memory and handed over as a device pointer."""
+    L = _lib.lib()
+    k = np.ascontiguousarray(keys, dtype=np.uint64)
+    o = np.ascontiguousarray(off, dtype=np.uint64)
+    n = o.size - 1
+    sk = np.zeros((max(n, 1), int(m)), dtype=np.uint64)
+    ln = np.zeros(max(n, 1), dtype=np.uint32)
+    d = None
+    try:
+        if on_device:
+            d = C.c_void_p()
+            check(L.taxor_gpu_malloc(device, max(k.size, 1) * 8, C.byref(d)))
+            if k.size:
+                check(L.taxor_gpu_memcpy_from_host(d, _p(k), k.size * 8))
+        check(L.taxor_gpu_keys_sketch(device, d if on_device else (_p(k) if k.size else None), 1 if on_device else 0, _p(o), n, int(m), _p(sk), _p(ln)))
+    finally:
+        if d is not None:
+            L.taxor_gpu_free(d)
+    return sk[:n], ln[:n]
+
+
+def sketch_pairs(sketch, length, count, device=0, want_ms=False):
+    """taxor_gpu_sketch_pairs: (shared uint32[n, n], uni uint32[n, n]) of n sketches (rows of `sketch`, `length` values each, from
+    bins of `count` keys); with want_ms also the kernel's milliseconds."""
+    sk = np.ascontiguousarray(sketch, dtype=np.uint64)
+    ln = np.ascontiguousarray(length, dtype=np.uint32)
+    ct = np.ascontiguousarray(count, dtype=np.uint64)
+    n, m = sk.shape
+    assert ln.size == n and ct.size == n
+    shared = np.zeros((n, n), dtype=np.uint32)
+    uni = np.zeros((n, n), dtype=np.uint32)
+    ms = C.c_float(0)
+    check(_lib.lib().taxor_gpu_sketch_pairs(device, _p(sk), _p(ln), _p(ct), n, m, _p(shared), _p(uni), C.byref(ms)))
+    return (shared, uni, float(ms.value)) if want_ms else (shared, uni)
+
+
+def cluster_order(shared, uni, jmin):
+    """taxor_cluster_order (host only): single-linkage clusters of the rows linked by shared >= jmin * uni (uni > 0) ->
+    (order uint64[n], cluster uint64[n])."""
+    s = np.ascontiguousarray(shared, dtype=np.uint32)
+    u = np.ascontiguousarray(uni, dtype=np.uint32)
+    n = s.shape[0]
+    assert s.shape == (n, n) and u.shape == (n, n)
+    order = np.zeros(n, dtype=np.uint64)
+    cluster = np.zeros(n, dtype=np.uint64)
+    check(_lib.lib().taxor_cluster_order(_p(s), _p(u), n, float(jmin), _p(order), _p(cluster)))
+    return order, cluster
+
+
+def similarity_rank(sketch, length, counts, window=4096, jmin=0.1, device=0):
+    """taxor_similarity_rank: the bins in descending count, in windows of `window`, each paired on the device and cluster-ordered ->
+    (rank uint64[n], clusters with more than one member)."""
+    sk = np.ascontiguousarray(sketch, dtype=np.uint64)
+    ln = np.ascontiguousarray(length, dtype=np.uint32)
+    ct = np.ascontiguousarray(counts, dtype=np.uint64)
+    n, m = sk.shape
+    rank = np.zeros(n, dtype=np.uint64)
+    multi = C.c_uint64(0)
+    check(_lib.lib().taxor_similarity_rank(device, _p(sk), _p(ln), _p(ct), n, m, int(window), float(jmin), _p(rank), C.byref(multi), None))
+    return rank, int(multi.value)
+
+
+def build_layout(counts, t_max=0, rank=None):
     """taxor_build_layout: the IXF tree for these per-user-bin distinct key counts.  Returns a dict with t_max, depth,
-    bytes_per_hash, index_bytes and ixfs: [{bins, next_ixf, fname_idx, part, parts}] (IXF 0 = root)."""
+    bytes_per_hash, index_bytes and ixfs: [{bins, next_ixf, fname_idx, part, parts}] (IXF 0 = root).  rank (one value per user bin):
+    taxor_build_layout_ranked -- the bins that are cut into groups are ordered by it instead of by count."""
     c = np.ascontiguousarray(counts, dtype=np.uint64)
     L = C.POINTER(_lib.Layout)()
-    check(_lib.lib().taxor_build_layout(_p(c), c.size, int(t_max), C.byref(L)))
+    if rank is None:
+        check(_lib.lib().taxor_build_layout(_p(c), c.size, int(t_max), C.byref(L)))
+    else:
+        r = np.ascontiguousarray(rank, dtype=np.uint64)
+        assert r.size == c.size
+        check(_lib.lib().taxor_build_layout_ranked(_p(c), c.size, int(t_max), _p(r), C.byref(L)))
     try:
         l = L.contents
         first = np.ctypeslib.as_array(l.bin_first, shape=(l.n_ixf + 1,))
