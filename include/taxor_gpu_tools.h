@@ -287,6 +287,56 @@ int taxor_gpu_search_merge_prior(taxor_gpu_searcher *s, const taxor_gpu_prior *p
  * thousand reads keeps its keys only on a searcher of a paged index (TAXOR_E_ARG otherwise). */
 int taxor_gpu_results_keys(taxor_gpu_searcher *s, const uint32_t **key);
 
+/* ---- a batch's hash lists, saved once and replayed ("Search beyond device memory": capture and replay).  What the
+ * query of a batch consumes -- every read's distinct hashes, their count and the read's threshold -- depends on the reads and on the
+ * hashing and threshold parameters alone, not on which part of an index is resident: a caller that searches the same reads again (the
+ * next pass over a paged index) keeps them and neither parses, uploads, packs nor hashes the reads a second time. */
+typedef struct taxor_gpu_saved taxor_gpu_saved;
+typedef struct {
+    uint64_t n_reads, total_hashes, n_sub_batches;
+    const uint32_t *read_len;    /* [n_reads] bases */
+    const uint32_t *n_hashes;    /* [n_reads] distinct hashes (QHASH_COUNT) */
+    const uint64_t *threshold;   /* [n_reads] the FINAL threshold, whatever the model: a replay evaluates none */
+    const uint64_t *hash_off;    /* [n_reads + 1] read r's hashes are hashes[hash_off[r] .. hash_off[r+1]), first-insertion order */
+    const uint64_t *hashes;      /* [total_hashes] dense, batch read order */
+    const uint32_t *sub_first;   /* [n_sub_batches + 1] the run's sub-batch plan: reads [sub_first[i], sub_first[i+1]) were queried together */
+    const uint32_t *order;       /* [n_reads] processing order inside each sub-batch (indices relative to its first read) */
+    /* the searcher's hashing and threshold parameters at capture */
+    uint32_t use_syncmer, kmer_size, syncmer_size, t_syncmer;
+    uint32_t scaling, model;     /* model: TAXOR_THR_* */
+    uint64_t window_size;        /* minimiser mode, else 0 */
+    double error_rate, ratio;    /* ratio: the percentage / syncmer models' factor */
+} taxor_gpu_saved_view;
+/* on != 0: every batch the searcher runs from now on (taxor_gpu_search_batch, _batch_begin, _segments_begin, _nibbles_begin, _fastx_begin,
+ * taxor_gpu_batch_run) also leaves a saved batch in host memory: per sub-batch, behind its hashing kernels, a scan of the counts and a
+ * gather of the lists into a dense device array, copied out through a bounded page-locked buffer while the sub-batch is queried.  Calls
+ * of a few thousand reads take the pipeline of large batches while capture is on (the lanes keep no hash lists).  on == 0: nothing of
+ * this exists -- no launch, copy or allocation is added to any path -- and the capture's buffers are released. */
+int taxor_gpu_search_capture(taxor_gpu_searcher *s, int on);
+/* after taxor_gpu_search_batch_end (or _batch_sync) of a batch that ran with capture on: the saved batch, the caller's from then on
+ * (taxor_gpu_saved_free).  TAXOR_E_ARG when capture is off or the batch was taken already. */
+int taxor_gpu_search_take_saved(taxor_gpu_searcher *s, taxor_gpu_saved **saved);
+/* read-only pointers into the saved batch, valid until it is freed; host bytes it holds */
+int taxor_gpu_saved_view_get(const taxor_gpu_saved *saved, taxor_gpu_saved_view *view);
+uint64_t taxor_gpu_saved_bytes(const taxor_gpu_saved *saved);
+void taxor_gpu_saved_free(taxor_gpu_saved *saved);
+/* The batch again, from its saved lists: they are staged sub-batch by sub-batch (same plan, same double buffering, same queue sizing as
+ * the run from bases) and queried from level 0; nothing is packed or hashed.  taxor_gpu_search_batch_end follows, and afterwards the
+ * searcher is where a batch from bases leaves it: taxor_gpu_batch_fetch, _batch_export_device, taxor_gpu_results_keys,
+ * taxor_gpu_search_merge_prior, taxor_gpu_profile_feed_add_batch (the read lengths are on the device) and taxor_gpu_batch_stats work
+ * unchanged.  `saved` stays valid until _batch_end.  The searcher may be another one and its index another index -- a paged index in
+ * another pass is that case -- but its hashing and threshold parameters must be the saved batch's: TAXOR_E_ARG naming the field
+ * (use_syncmer, kmer_size, syncmer_size, t_syncmer, window_size, scaling, model, error_rate, ratio) otherwise.  Before any launch the
+ * host checks what the kernels rely on (TAXOR_E_ARG naming the field): hash_off ascending from 0 and inside the array, n_hashes
+ * consistent with it, sub_first tiling the reads, order inside its sub-batch. */
+int taxor_gpu_search_saved_begin(taxor_gpu_searcher *s, const taxor_gpu_saved *saved);
+/* Host only: host bytes the saved hash lists of `bases` bases of query may need -- 8 per hash at one hash per min(t, k-s+1-t+1) bases
+ * for syncmers (k22/s12/t5: per 5 bases), per base otherwise, plus one per k bases, and 28 per read at one read per 200 bases -- and
+ * whether a store of that bound fits `available_bytes` with a quarter of a gibibyte to spare (1; always 1 when available_bytes is 0:
+ * no figure to hold against).  `taxor search` decides between replaying and re-reading the query with these two. */
+uint64_t taxor_saved_bytes_bound(uint64_t bases, int use_syncmer, uint32_t kmer_size, uint32_t syncmer_size, uint32_t t_syncmer);
+int taxor_saved_store_fits(uint64_t bound_bytes, uint64_t available_bytes);
+
 /* ---- taxor_gpu_search_batch split into its three phases so that a caller can keep a batch resident in HBM
  * (upload once, run many times) and overlap transfers with compute:
  *   upload : H2D of the ASCII bases + on-device dna4 mapping and 2-bit packing

@@ -180,6 +180,14 @@ class Prior(C.Structure):
 PASS_ROOT = 0xFFFFFFFF
 
 
+class SavedView(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("total_hashes", C.c_uint64), ("n_sub_batches", C.c_uint64), ("read_len", C.POINTER(C.c_uint32)),
+                ("n_hashes", C.POINTER(C.c_uint32)), ("threshold", C.POINTER(C.c_uint64)), ("hash_off", C.POINTER(C.c_uint64)),
+                ("hashes", C.POINTER(C.c_uint64)), ("sub_first", C.POINTER(C.c_uint32)), ("order", C.POINTER(C.c_uint32)),
+                ("use_syncmer", C.c_uint32), ("kmer_size", C.c_uint32), ("syncmer_size", C.c_uint32), ("t_syncmer", C.c_uint32),
+                ("scaling", C.c_uint32), ("model", C.c_uint32), ("window_size", C.c_uint64), ("error_rate", C.c_double), ("ratio", C.c_double)]
+
+
 SIGNATURES = {
     "taxor_gpu_last_error": (C.c_char_p, []),
     "taxor_gpu_index_create": (C.c_int, [C.POINTER(HixfView), C.c_int, C.POINTER(_P)]),
@@ -191,6 +199,14 @@ SIGNATURES = {
     "taxor_gpu_index_upload_wait_seconds": (C.c_double, [_P]),
     "taxor_gpu_search_merge_prior": (C.c_int, [_P, C.POINTER(Prior), C.c_uint32]),
     "taxor_gpu_results_keys": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_uint32))]),
+    "taxor_gpu_search_capture": (C.c_int, [_P, C.c_int]),
+    "taxor_gpu_search_take_saved": (C.c_int, [_P, C.POINTER(_P)]),
+    "taxor_gpu_saved_view_get": (C.c_int, [_P, C.POINTER(SavedView)]),
+    "taxor_gpu_saved_bytes": (C.c_uint64, [_P]),
+    "taxor_gpu_saved_free": (None, [_P]),
+    "taxor_gpu_search_saved_begin": (C.c_int, [_P, _P]),
+    "taxor_saved_bytes_bound": (C.c_uint64, [C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "taxor_saved_store_fits": (C.c_int, [C.c_uint64, C.c_uint64]),
     "taxor_gpu_index_build_hixf": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint32)]),
     "taxor_gpu_index_build_ixf_ex": (C.c_int, [_P, C.c_uint64, _P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(BuildStats)]),
     "taxor_gpu_index_build_hixf_ex": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, C.POINTER(BuildStats)]),

@@ -7,6 +7,7 @@
 #include "ixf_arith.h"
 #include "ixf_layout.h"
 #include "kernels.h"
+#include "saved_batch.h"
 #include "tuning.h"
 
 #include <sys/mman.h>
@@ -201,6 +202,19 @@ struct taxor_gpu_searcher {
     bool dev_results_stale = false;         // ... and not (yet) in the device-resident CSR that export_device / the communicator read
     bool keep_keys = false;                 // searcher of a paged index: a call that goes through the lanes keeps its tuples' DFS keys (h_key)
     std::vector<uint32_t> h_key;            // taxor_gpu_results_keys
+
+    // the batches' hash lists: captured (taxor_gpu_search_capture / _take_saved) and replayed (taxor_gpu_search_saved_begin).  Nothing
+    // below exists while capture is off and no saved batch is replayed
+    bool capture = false;
+    taxor_gpu_saved *cap_cur = nullptr;     // the lists of the batch in flight (or of the last one), until they are taken
+    bool cap_done = false;                  // ... complete: every sub-batch's hashes, the counts and the thresholds are in it
+    DeviceBuf<uint64_t> d_cap_dense[2], d_cap_off;   // a sub-batch's lists dense (sub-batch i in array i & 1), and their offsets (the scan of its counts)
+    uint64_t *h_cap_pin[2] = {nullptr, nullptr};  // the bounded page-locked staging between d_cap_dense and the pageable store
+    uint64_t *h_cap_total = nullptr;        // page-locked words: the hash count of sub-batch i at [i & 1]
+    hipEvent_t ev_cap[2] = {nullptr, nullptr}, ev_cap_gather[2] = {nullptr, nullptr};
+    hipStream_t st_cap = nullptr;           // the dense hashes' way to the host, nothing else
+    const taxor_gpu_saved *replay = nullptr;      // the batch in flight runs from these saved lists (until it is synchronised)
+    bool from_saved = false;                // the last batch did: the searcher holds no packed bases to run again
 
     // timing
     std::vector<hipEvent_t> ev;
@@ -1084,6 +1098,27 @@ static int searcher_create_impl(taxor_gpu_index *idx, const taxor_gpu_search_par
     return TAXOR_OK;
 }
 
+// the capture's buffers and an untaken saved batch go (capture off, or the searcher's end)
+static void capture_release(taxor_gpu_searcher *s)
+{
+    delete s->cap_cur;
+    s->cap_cur = nullptr;
+    s->cap_done = false;
+    s->d_cap_off.release();
+    if (s->st_cap) { (void)hipStreamSynchronize(s->st_cap); (void)hipStreamDestroy(s->st_cap); s->st_cap = nullptr; }
+    for (int i = 0; i < 2; ++i) {
+        s->d_cap_dense[i].release();
+        if (s->ev_cap_gather[i]) (void)hipEventDestroy(s->ev_cap_gather[i]);
+        s->ev_cap_gather[i] = nullptr;
+        if (s->h_cap_pin[i]) (void)hipHostFree(s->h_cap_pin[i]);
+        if (s->ev_cap[i]) (void)hipEventDestroy(s->ev_cap[i]);
+        s->h_cap_pin[i] = nullptr;
+        s->ev_cap[i] = nullptr;
+    }
+    if (s->h_cap_total) (void)hipHostFree(s->h_cap_total);
+    s->h_cap_total = nullptr;
+}
+
 extern "C" void taxor_gpu_searcher_destroy(taxor_gpu_searcher *s)
 {
     if (!s) return;
@@ -1103,6 +1138,7 @@ extern "C" void taxor_gpu_searcher_destroy(taxor_gpu_searcher *s)
         if (L.h_out) (void)hipHostFree(L.h_out);
     }
     s->lanes.clear();
+    capture_release(s);
     if (s->st_copy) (void)hipStreamSynchronize(s->st_copy);
     if (s->st_sync2) (void)hipStreamSynchronize(s->st_sync2);
     if (s->st_sync) (void)hipStreamSynchronize(s->st_sync);
@@ -1174,9 +1210,7 @@ int layout_batch(taxor_gpu_searcher *s, const uint64_t *offsets, uint64_t n_read
                  std::vector<uint32_t> &order, uint32_t first_div, bool ramp)
 {
     const taxor_gpu_index *idx = s->idx;
-    const int w = idx->k - idx->s + 1;
-    int gap = std::min(idx->t, w - idx->t + 1); // minimum distance between two open syncmers of one read
-    if (gap < 1) gap = 1;
+    const int gap = syncmer_min_gap(idx->k, idx->s, idx->t); // minimum distance between two open syncmers of one read (saved_batch.h)
     poff.resize(n_reads);
     rlen.resize(n_reads);
     hoff.resize(n_reads);
@@ -1637,6 +1671,8 @@ int prepare_batch(taxor_gpu_searcher *s, const char *bases, const uint64_t *offs
     if (n_reads >= (1ull << 32)) return fail(TAXOR_E_ARG, "batch_upload: more than 2^32 reads in one batch");
     HIP_TRY(hipSetDevice(s->idx->device));
     s->ran = s->synced = false;
+    s->replay = nullptr;
+    s->from_saved = false;
     // the per-read layout arrays live in the searcher: a batch of a million short reads is 45 MB of them, and fresh vectors
     // per call cost more in page faults than the loop that fills them
     std::vector<uint64_t> &poff = s->lay_poff, &hoff = s->lay_hoff, &aoff = s->lay_aoff;
@@ -1745,9 +1781,122 @@ bool host_pointer_is_pinned(const void *p)
     return a.type == hipMemoryTypeHost;
 }
 
+// ---- capture of a batch's hash lists (taxor_gpu_search_capture).  d_hashes[buf] is double-buffered across sub-batches and a read's
+// list sits at its slot offset with slack behind it, so the lists are taken per sub-batch: behind its hashing kernels, on their
+// stream, a scan of the counts and a gather into one of TWO dense device arrays, with an event (capture_launch; the sub-batch's
+// query was enqueued before and runs on its own stream).  Nothing waits there: the host drains sub-batch i - 1 (capture_drain) after
+// it has enqueued sub-batch i's hashing, query and gather, so the device works on sub-batch i while the dense hashes of i - 1 cross
+// on a stream of their own -- not the bases' copy stream, whose uploads of a page-locked batch are all queued up front -- through two
+// page-locked buffers into the pageable store (chunk c + 1 crosses while chunk c is copied).  Sub-batch i + 2's hashing and gather
+// are enqueued after the drain of i, so neither d_hashes[i & 1] nor the dense array i & 1 is overwritten while it is read.  The
+// counts and thresholds are batch-wide arrays: one copy each at the end.
+constexpr uint64_t kCapChunk = 1ull << 20;       // hashes per page-locked buffer: 8 MiB each, two of them
+
+int capture_begin(taxor_gpu_searcher *s)
+{
+    delete s->cap_cur;
+    s->cap_cur = nullptr;
+    s->cap_done = false;
+    if (ensure_stream(&s->st_cap)) return TAXOR_E_HIP;
+    for (int i = 0; i < 2; ++i) {
+        if (!s->h_cap_pin[i]) HIP_TRY(hipHostMalloc((void **)&s->h_cap_pin[i], kCapChunk * 8, hipHostMallocDefault));
+        if (!s->ev_cap[i]) HIP_TRY(hipEventCreateWithFlags(&s->ev_cap[i], hipEventDisableTiming));
+        if (!s->ev_cap_gather[i]) HIP_TRY(hipEventCreateWithFlags(&s->ev_cap_gather[i], hipEventDisableTiming));
+        if (reserve(s->d_cap_dense[i], s->max_slots + 64)) return TAXOR_E_HIP;
+    }
+    if (!s->h_cap_total) HIP_TRY(hipHostMalloc((void **)&s->h_cap_total, 64, hipHostMallocDefault));
+    if (reserve(s->d_cap_off, (uint64_t)s->max_sub_reads + 1)) return TAXOR_E_HIP;
+    auto *b = new taxor_gpu_saved();
+    s->cap_cur = b;
+    const taxor_gpu_index *idx = s->idx;
+    b->n_reads = s->n_reads;
+    b->n_bases = s->n_bases;
+    b->use_syncmer = idx->w_min == 0;
+    b->kmer_size = (uint32_t)idx->k;
+    b->syncmer_size = (uint32_t)idx->s;
+    b->t_syncmer = (uint32_t)idx->t;
+    b->window_size = idx->w_min > 0 ? (uint64_t)idx->w_min : 0;
+    b->scaling = idx->scaling;
+    b->model = s->prm.model;
+    b->error_rate = s->prm.error_rate;
+    b->ratio = s->prm.ratio;
+    b->read_len.assign(s->h_rlen.begin(), s->h_rlen.begin() + s->n_reads);
+    b->order.assign(s->lay_order.begin(), s->lay_order.begin() + s->n_reads);
+    uint64_t slots = 0;
+    b->sub_first.assign(1, 0u);
+    for (const SubBatch &sb : s->subs) {
+        b->sub_first.push_back(sb.first + sb.n);
+        slots += sb.slots;
+    }
+    if (!b->reserve(slots)) return fail(TAXOR_E_NOMEM, "capture: no address space for %llu hashes", (unsigned long long)slots);
+    return 0;
+}
+
+// sub-batch i: scan, gather into dense array i & 1, its hash count into the page-locked word i & 1, an event; nothing waits
+int capture_launch(taxor_gpu_searcher *s, const SubBatch &sb, size_t i, int buf, hipStream_t ss)
+{
+    const int c = (int)(i & 1);
+    launch_hash_offsets(s->d_nh.p + sb.first, s->d_cap_off.p, sb.n, ss);       // (d_cap_off is read by the gather behind it on the same stream only)
+    launch_gather_hashes(s->d_hashes[buf].p, s->d_hoff.p + sb.first, s->d_hcap.p + sb.first, s->d_nh.p + sb.first, s->d_cap_off.p, s->d_cap_dense[c].p,
+                         s->d_cap_dense[c].cap, sb.n, ss);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(s->h_cap_total + c, s->d_cap_off.p + sb.n, 8, hipMemcpyDeviceToHost, ss));
+    HIP_TRY(hipEventRecord(s->ev_cap_gather[c], ss));
+    return 0;
+}
+
+// sub-batch i's dense hashes into the store
+int capture_drain(taxor_gpu_searcher *s, const SubBatch &sb, size_t i)
+{
+    const int d = (int)(i & 1);
+    HIP_TRY(hipEventSynchronize(s->ev_cap_gather[d]));
+    const uint64_t total = s->h_cap_total[d];
+    if (total > sb.slots || total > s->d_cap_dense[d].cap)
+        return fail(TAXOR_E_INTERNAL, "capture: a sub-batch of %llu slots holds %llu hashes", (unsigned long long)sb.slots, (unsigned long long)total);
+    uint64_t prev_n = 0;
+    int c = 0;
+    for (uint64_t at = 0; at < total; at += kCapChunk, ++c) {
+        const uint64_t n = std::min(kCapChunk, total - at);
+        HIP_TRY(hipMemcpyAsync(s->h_cap_pin[c & 1], s->d_cap_dense[d].p + at, n * 8, hipMemcpyDeviceToHost, s->st_cap));
+        HIP_TRY(hipEventRecord(s->ev_cap[c & 1], s->st_cap));
+        if (c) {
+            HIP_TRY(hipEventSynchronize(s->ev_cap[(c - 1) & 1]));
+            if (!s->cap_cur->append(s->h_cap_pin[(c - 1) & 1], prev_n)) return fail(TAXOR_E_INTERNAL, "capture: the batch holds more hashes than slots");
+        }
+        prev_n = n;
+    }
+    if (c) {
+        HIP_TRY(hipEventSynchronize(s->ev_cap[(c - 1) & 1]));
+        if (!s->cap_cur->append(s->h_cap_pin[(c - 1) & 1], prev_n)) return fail(TAXOR_E_INTERNAL, "capture: the batch holds more hashes than slots");
+    }
+    return 0;
+}
+
+int capture_finish(taxor_gpu_searcher *s)
+{
+    taxor_gpu_saved &b = *s->cap_cur;
+    const uint64_t n = s->n_reads;
+    b.n_hashes.resize(n);
+    b.threshold.resize(n);
+    b.hash_off.assign(n + 1, 0);
+    if (n) {          // every hashing kernel has ended (the last drain waited for the last sub-batch's gather, which stands behind them)
+        HIP_TRY(hipMemcpyAsync(b.n_hashes.data(), s->d_nh.p, n * 4, hipMemcpyDeviceToHost, s->st_cap));
+        HIP_TRY(hipMemcpyAsync(b.threshold.data(), s->d_thr.p, n * 8, hipMemcpyDeviceToHost, s->st_cap));
+        HIP_TRY(hipStreamSynchronize(s->st_cap));
+    }
+    for (uint64_t r = 0; r < n; ++r) b.hash_off[r + 1] = b.hash_off[r] + b.n_hashes[r];
+    if (b.hash_off[n] != b.total_hashes)
+        return fail(TAXOR_E_INTERNAL, "capture: the counts sum to %llu hashes, %llu were gathered", (unsigned long long)b.hash_off[n], (unsigned long long)b.total_hashes);
+    b.finish();
+    s->cap_done = true;
+    return 0;
+}
+
 int run_pipeline(taxor_gpu_searcher *s, bool host_ascii)
 {
     if (int rc = ensure_scratch(s)) return rc;
+    if (s->capture)
+        if (int rc = capture_begin(s)) return rc;
     bool need_wave = false;
     for (const SubBatch &sb : s->subs) need_wave = need_wave || (s->idx->w_min == 0 && sb.n_long < sb.n);
     if (need_wave && ensure_stream(&s->st_sync2)) return TAXOR_E_HIP;
@@ -1829,6 +1978,54 @@ int run_pipeline(taxor_gpu_searcher *s, bool host_ascii)
                                sb.n, s->d_read_off.p + sb.first, i + 1 == s->subs.size(), nullptr, -1, s->d_order.p + sb.first))
             return rc;
         HIP_TRY(hipEventRecord(s->ev_query_done[i], s->st));
+        if (s->capture) {          // this sub-batch's gather behind its hashing; then the one before it leaves for the host
+            if (int rc = capture_launch(s, sb, i, buf, ss)) return rc;
+            if (i)
+                if (int rc = capture_drain(s, s->subs[i - 1], i - 1)) return rc;
+        }
+    }
+    if (ev_end(s, tot_slot)) return TAXOR_E_HIP;
+    if (s->capture) {
+        if (!s->subs.empty())
+            if (int rc = capture_drain(s, s->subs.back(), s->subs.size() - 1)) return rc;
+        if (int rc = capture_finish(s)) return rc;
+    }
+    s->ran = true;
+    s->synced = false;
+    return TAXOR_OK;
+}
+
+// ---- replay of a batch from its saved hash lists (taxor_gpu_search_saved_begin): run_pipeline without the copy of the bases, the
+// pack and the hashing.  Sub-batch i's dense hashes go straight into d_hashes[i & 1] on the copy stream -- behind the query of
+// sub-batch i - 2, which read that buffer -- and the query follows on its own stream; d_hoff, d_nh, d_thr, d_rlen and d_order went up
+// with the batch.
+int run_saved_pipeline(taxor_gpu_searcher *s)
+{
+    const taxor_gpu_saved &b = *s->replay;
+    if (int rc = ensure_scratch(s)) return rc;
+    if (ensure_stream(&s->st_copy)) return TAXOR_E_HIP;
+    s->ev_used = 0;
+    s->ev_spans.clear();
+    s->stats = taxor_gpu_run_stats{};
+    size_t tot_slot;
+    if (reset_sub_counters(s, true)) return TAXOR_E_HIP;
+    HIP_TRY(hipEventRecord(s->ev_reset, s->st));
+    HIP_TRY(hipStreamWaitEvent(s->st_copy, s->ev_reset, 0));
+    if (ev_begin(s, 3, &tot_slot)) return TAXOR_E_HIP;
+    if (s->subs.empty()) HIP_TRY(hipMemsetAsync(s->d_read_off.p, 0, sizeof(uint64_t), s->st));
+    for (size_t i = 0; i < s->subs.size(); ++i) {
+        const SubBatch &sb = s->subs[i];
+        const int buf = (int)(i & 1);
+        const uint64_t h0 = b.hash_off[sb.first], nh = b.hash_off[sb.first + sb.n] - h0;
+        if (i >= 2) HIP_TRY(hipStreamWaitEvent(s->st_copy, s->ev_query_done[i - 2], 0));
+        if (nh) HIP_TRY(hipMemcpyAsync(s->d_hashes[buf].p, b.hashes + h0, nh * 8, hipMemcpyHostToDevice, s->st_copy));
+        HIP_TRY(hipEventRecord(s->ev_copy_done[i], s->st_copy));
+        HIP_TRY(hipStreamWaitEvent(s->st, s->ev_copy_done[i], 0));
+        if (i && reset_sub_counters(s, false)) return TAXOR_E_HIP;
+        if (int rc = run_query(s, s->d_hashes[buf].p, s->d_hoff.p + sb.first, s->d_nh.p + sb.first, s->d_thr.p + sb.first, sb.n,
+                               s->d_read_off.p + sb.first, i + 1 == s->subs.size(), nullptr, -1, s->d_order.p + sb.first))
+            return rc;
+        HIP_TRY(hipEventRecord(s->ev_query_done[i], s->st));
     }
     if (ev_end(s, tot_slot)) return TAXOR_E_HIP;
     s->ran = true;
@@ -1866,6 +2063,7 @@ bool small_applicable(const taxor_gpu_searcher *s, const uint64_t *offsets, uint
 {
     static const bool off = [] { const char *e = tune_env("TAXOR_SMALL_PATH"); return e && atoi(e) == 0; }();
     if (off || !s->small_path || s->lane_mode || s->prm.time_kernels || s->d_prof || s->idx->w_min != 0) return false;
+    if (s->capture) return false;          // the lanes keep no hash lists: the call takes the pipeline of large batches, as their own fall-back does
     if (s->prm.model != TAXOR_THR_PERCENTAGE && s->prm.model != TAXOR_THR_SYNCMER) return false;
     if (n_reads == 0 || n_reads > SMALL_MAX_READS || offsets[n_reads] - offsets[0] > SMALL_MAX_BASES) return false;
     return true;
@@ -2343,6 +2541,8 @@ extern "C" int taxor_gpu_batch_run(taxor_gpu_searcher *s)
 {
     if (!s) return fail(TAXOR_E_ARG, "batch_run: null searcher");
     HIP_TRY(hipSetDevice(s->idx->device));
+    if (s->replay) return run_saved_pipeline(s);
+    if (s->from_saved) return fail(TAXOR_E_ARG, "batch_run: the last batch ran from saved hash lists, the searcher holds no bases to run again (taxor_gpu_search_saved_begin replays it)");
     return run_pipeline(s, false);
 }
 
@@ -2362,6 +2562,11 @@ extern "C" int taxor_gpu_batch_sync(taxor_gpu_searcher *s)
             st.n_reads = s->n_reads;
             st.n_bases = s->n_bases;
             st.n_hashes = s->h_ctr.n_hashes;
+            if (s->replay) {                 // nothing was hashed: the count is the saved lists'
+                st.n_hashes = s->replay->total_hashes;
+                s->replay = nullptr;         // the saved batch is the caller's again
+                s->from_saved = true;
+            }
             st.n_tuples = s->h_ctr.tuple_total;
             st.n_work_items = s->h_ctr.n_work;
             st.query_bytes = s->h_ctr.query_bytes;
@@ -2847,6 +3052,116 @@ extern "C" int taxor_gpu_pack_nibbles(taxor_gpu_searcher *s, const taxor_nibble_
     return TAXOR_OK;
 }
 
+// =========================================================================================================
+// saved hash lists: capture and replay
+// =========================================================================================================
+extern "C" int taxor_gpu_search_capture(taxor_gpu_searcher *s, int on)
+{
+    if (!s) return fail(TAXOR_E_ARG, "search_capture: null searcher");
+    if (s->ran && !s->synced) return fail(TAXOR_E_ARG, "search_capture: a batch is in flight; end it first");
+    HIP_TRY(hipSetDevice(s->idx->device));
+    s->capture = on != 0;
+    if (!s->capture) capture_release(s);
+    return TAXOR_OK;
+}
+
+extern "C" int taxor_gpu_search_take_saved(taxor_gpu_searcher *s, taxor_gpu_saved **saved)
+{
+    if (!s || !saved) return fail(TAXOR_E_ARG, "search_take_saved: null argument");
+    *saved = nullptr;
+    if (!s->capture) return fail(TAXOR_E_ARG, "search_take_saved: capture is off (taxor_gpu_search_capture)");
+    if (!s->ran) return fail(TAXOR_E_ARG, "search_take_saved: capture is on, but no batch has run");
+    if (!s->synced)
+        if (int rc = taxor_gpu_batch_sync(s)) return rc;
+    if (!s->cap_cur || !s->cap_done) return fail(TAXOR_E_ARG, "search_take_saved: capture holds no saved batch (taken already, or the last batch was a replay)");
+    *saved = s->cap_cur;
+    s->cap_cur = nullptr;
+    s->cap_done = false;
+    return TAXOR_OK;
+}
+
+extern "C" int taxor_gpu_saved_view_get(const taxor_gpu_saved *saved, taxor_gpu_saved_view *view)
+{
+    if (!saved || !view) return fail(TAXOR_E_ARG, "saved_view_get: null argument");
+    saved->view(view);
+    return TAXOR_OK;
+}
+
+extern "C" uint64_t taxor_gpu_saved_bytes(const taxor_gpu_saved *saved) { return saved ? saved->bytes() : 0; }
+extern "C" void taxor_gpu_saved_free(taxor_gpu_saved *saved) { delete saved; }
+
+extern "C" int taxor_gpu_search_saved_begin(taxor_gpu_searcher *s, const taxor_gpu_saved *saved)
+{
+    if (!s || !saved) return fail(TAXOR_E_ARG, "search_saved_begin: null argument");
+    if (s->ran && !s->synced) return fail(TAXOR_E_ARG, "search_saved_begin: a batch is in flight; end it first");
+    const taxor_gpu_index *idx = s->idx;
+    const taxor_gpu_saved &b = *saved;
+    // the hashing and threshold parameters: the lists and thresholds are a function of them (and of the reads) alone
+    auto differs = [](const char *field, double mine, double theirs) {
+        return fail(TAXOR_E_ARG, "search_saved_begin: %s differs: the saved batch was captured with %g, the searcher has %g", field, theirs, mine);
+    };
+    const uint32_t use_syncmer = idx->w_min == 0;
+    if (b.use_syncmer != use_syncmer) return differs("use_syncmer", use_syncmer, b.use_syncmer);
+    if (b.kmer_size != (uint32_t)idx->k) return differs("kmer_size", idx->k, b.kmer_size);
+    if (use_syncmer && b.syncmer_size != (uint32_t)idx->s) return differs("syncmer_size", idx->s, b.syncmer_size);
+    if (use_syncmer && b.t_syncmer != (uint32_t)idx->t) return differs("t_syncmer", idx->t, b.t_syncmer);
+    if (b.window_size != (idx->w_min > 0 ? (uint64_t)idx->w_min : 0)) return differs("window_size", idx->w_min, (double)b.window_size);
+    if (b.scaling != idx->scaling) return differs("scaling", idx->scaling, b.scaling);
+    if (b.model != s->prm.model) return differs("model", s->prm.model, b.model);
+    if (b.error_rate != s->prm.error_rate) return differs("error_rate", s->prm.error_rate, b.error_rate);
+    const bool by_ratio = s->prm.model == TAXOR_THR_PERCENTAGE || s->prm.model == TAXOR_THR_SYNCMER;
+    if (by_ratio && b.ratio != s->prm.ratio) return differs("ratio", s->prm.ratio, b.ratio);
+    // what the copies and kernels rely on, before anything is launched
+    const std::string bad = saved_validate(b);
+    if (!bad.empty()) return fail(TAXOR_E_ARG, "search_saved_begin: %s", bad.c_str());
+    HIP_TRY(hipSetDevice(idx->device));
+    s->ran = s->synced = false;
+    s->small_active = false;
+    s->from_saved = false;
+    delete s->cap_cur;             // (an untaken capture of an earlier batch: this batch leaves none)
+    s->cap_cur = nullptr;
+    s->cap_done = false;
+    // the searcher's view of the batch, as prepare_batch leaves it: the saved plan instead of a layout from offsets
+    const uint64_t n = b.n_reads;
+    s->n_reads = n;
+    s->n_bases = 0;
+    s->packed_in_bytes = 0;
+    s->h_rlen.assign(b.read_len.begin(), b.read_len.end());
+    for (uint64_t r = 0; r < n; ++r) {
+        s->n_bases += b.read_len[r];
+        s->packed_in_bytes += (b.read_len[r] + 3u) / 4u;
+    }
+    s->mean_read_len = n ? s->n_bases / n : (1u << 20);
+    s->host_spans.clear();
+    s->subs.clear();
+    s->max_slots = 0;
+    s->max_sub_reads = 0;
+    s->max_read_slots = 16;        // (sizes the hashing kernels' dedup scratch only)
+    std::vector<uint64_t> &hoff = s->lay_hoff;
+    hoff.resize(n);
+    for (size_t i = 0; i + 1 < b.sub_first.size(); ++i) {
+        const uint32_t first = b.sub_first[i], m = b.sub_first[i + 1] - first;
+        const uint64_t h0 = b.hash_off[first], slots = b.hash_off[first + m] - h0;
+        s->subs.push_back({first, m, m, slots, 0, 0});
+        s->max_slots = std::max(s->max_slots, slots);
+        s->max_sub_reads = std::max(s->max_sub_reads, m);
+        for (uint32_t r = first; r < first + m; ++r) hoff[r] = b.hash_off[r] - h0;      // d_hoff: the scan of the sub-batch's counts, no slack
+    }
+    if (reserve(s->d_hoff, n + 1) || reserve(s->d_nh, n + 1) || reserve(s->d_thr, n + 1) || reserve(s->d_rlen, n + 1) || reserve(s->d_order, n + 1))
+        return TAXOR_E_HIP;
+    if (int rc = ensure_scratch(s)) return rc;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(s->d_hoff.p, hoff.data(), n * 8, hipMemcpyHostToDevice, s->st));
+        HIP_TRY(hipMemcpyAsync(s->d_nh.p, b.n_hashes.data(), n * 4, hipMemcpyHostToDevice, s->st));
+        HIP_TRY(hipMemcpyAsync(s->d_thr.p, b.threshold.data(), n * 8, hipMemcpyHostToDevice, s->st));
+        HIP_TRY(hipMemcpyAsync(s->d_rlen.p, b.read_len.data(), n * 4, hipMemcpyHostToDevice, s->st));
+        HIP_TRY(hipMemcpyAsync(s->d_order.p, b.order.data(), n * 4, hipMemcpyHostToDevice, s->st));
+        HIP_TRY(hipStreamSynchronize(s->st));
+    }
+    s->replay = saved;
+    return run_saved_pipeline(s);
+}
+
 extern "C" int taxor_gpu_search_batch_end(taxor_gpu_searcher *s, taxor_gpu_results *out) { return taxor_gpu_batch_fetch(s, out); }
 
 extern "C" int taxor_gpu_search_batch(taxor_gpu_searcher *s, const char *bases, const uint64_t *offsets, uint64_t n_reads,
@@ -2909,6 +3224,8 @@ int stage_hash_list(taxor_gpu_searcher *s, const uint64_t *hashes, uint64_t n, u
     HIP_TRY(hipSetDevice(s->idx->device));
     s->ran = s->synced = false;
     s->small_active = false;
+    s->replay = nullptr;
+    s->from_saved = false;
     s->n_reads = 1;
     s->n_bases = 0;
     s->mean_read_len = 1u << 20;

@@ -2,6 +2,7 @@
 // (threshold ratio, classification filter, XOR-filter bin construction, synthetic reads).
 #include "../../include/taxor_gpu_tools.h"
 #include "ixf_arith.h"
+#include "saved_batch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -684,5 +685,13 @@ int taxor_index_plan_passes(const taxor_hixf_view *v, uint64_t budget_bytes, tax
         for (size_t g = 0; g < gbytes.size(); ++g) pass_bytes[g] = gbytes[g];
     return TAXOR_OK;
 }
+
+// ---- the saved hash lists' store of a paged search (saved_batch.h): its bound and the decision made from it, for `taxor search`
+uint64_t taxor_saved_bytes_bound(uint64_t bases, int use_syncmer, uint32_t kmer_size, uint32_t syncmer_size, uint32_t t_syncmer)
+{
+    return taxor::saved_bytes_bound(bases, use_syncmer != 0, (int)kmer_size, (int)syncmer_size, (int)t_syncmer);
+}
+
+int taxor_saved_store_fits(uint64_t bound_bytes, uint64_t available_bytes) { return taxor::saved_store_fits(bound_bytes, available_bytes) ? 1 : 0; }
 
 } // extern "C"

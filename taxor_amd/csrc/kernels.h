@@ -249,4 +249,11 @@ void launch_merge_place(const MergeArgs &a, hipStream_t st);
 void launch_merge_count(const MergeArgs &a, hipStream_t st);   // n_out and out_off
 void launch_merge_write(const MergeArgs &a, hipStream_t st);
 
+// capture of a sub-batch's hash lists (taxor_gpu_search_capture): off[0 .. n] = exclusive 64-bit scan of nh[0 .. n) (one block), then
+// read r's nh[r] hashes (never more than its hcap[r] slots) from hashes + hoff[r] to dense + off[r], one wavefront per read; a list
+// that would pass dense_cap is left out (the host sees off[n] > dense_cap)
+void launch_hash_offsets(const uint32_t *nh, uint64_t *off, uint32_t n_reads, hipStream_t st);
+void launch_gather_hashes(const uint64_t *hashes, const uint64_t *hoff, const uint32_t *hcap, const uint32_t *nh, const uint64_t *off,
+                          uint64_t *dense, uint64_t dense_cap, uint32_t n_reads, hipStream_t st);
+
 } // namespace taxor

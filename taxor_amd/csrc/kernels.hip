@@ -2393,4 +2393,50 @@ void launch_merge_write(const MergeArgs &a, hipStream_t st)
     hipLaunchKernelGGL(k_merge_emit<true>, dim3(merge_grid(a.n_reads)), dim3(256), 0, st, a);
 }
 
+// ------------------------------------------------------------------------------------------------------
+// capture of a sub-batch's hash lists (taxor_gpu_search_capture).  The syncmer kernels leave read r's distinct hashes at its slot
+// offset hoff[r] with capacity slack behind them; a saved batch holds them dense.
+//   k_hash_offsets  : off = exclusive 64-bit scan of the counts, one block, block_excl_add per round and a carry between rounds
+//   k_gather_hashes : one wavefront per read, 64 entries at a time whatever the list's length (k_merge_place's loop shape): a pure
+//                     copy, 512 contiguous bytes read and written per wave and round
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_hash_offsets(const uint32_t *__restrict__ nh, uint64_t *__restrict__ off, uint32_t n)
+{
+    __shared__ uint64_t sScr[16];
+    uint64_t carry = 0;
+    for (uint32_t r0 = 0; r0 < n; r0 += 1024u) {                         // block-uniform bounds: every thread takes every barrier
+        const uint32_t r = r0 + threadIdx.x;
+        const uint64_t v = r < n ? nh[r] : 0u;
+        uint64_t tot;
+        const uint64_t ex = block_excl_add<16>(v, sScr, &tot);
+        if (r < n) off[r] = carry + ex;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) off[n] = carry;
+}
+
+__global__ __launch_bounds__(256) void k_gather_hashes(const uint64_t *__restrict__ hashes, const uint64_t *__restrict__ hoff,
+                                                       const uint32_t *__restrict__ hcap, const uint32_t *__restrict__ nh,
+                                                       const uint64_t *__restrict__ off, uint64_t *__restrict__ dense, uint64_t dense_cap, uint32_t n)
+{
+    const uint32_t l = lane_id();
+    for (uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6; r < n; r += gridDim.x * 4u) {
+        const uint64_t src = hoff[r], dst = off[r];
+        const uint32_t c = min(nh[r], hcap[r]);                           // (the count never passes the slots: FLAG_CAND_OVERFLOW otherwise)
+        if (dst + c > dense_cap) continue;
+        for (uint32_t i = l; i < c; i += 64u) dense[dst + i] = hashes[src + i];
+    }
+}
+
+void launch_hash_offsets(const uint32_t *nh, uint64_t *off, uint32_t n_reads, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_hash_offsets, dim3(1), dim3(1024), 0, st, nh, off, n_reads);
+}
+void launch_gather_hashes(const uint64_t *hashes, const uint64_t *hoff, const uint32_t *hcap, const uint32_t *nh, const uint64_t *off,
+                          uint64_t *dense, uint64_t dense_cap, uint32_t n_reads, hipStream_t st)
+{
+    if (!n_reads) return;
+    hipLaunchKernelGGL(k_gather_hashes, dim3(merge_grid(n_reads)), dim3(256), 0, st, hashes, hoff, hcap, nh, off, dense, dense_cap, n_reads);
+}
+
 } // namespace taxor

@@ -185,6 +185,8 @@ struct Config {                              // taxor_search_configuration.hpp:8
     uint32_t ixf_layout = 0;
     uint64_t group_reads = 0;   // reads per GPU batch, made of queued chunks (0: 131072, or --batch-reads when that is given)
     uint64_t index_budget_mib = 0;   // hidden --device-index-budget: fingerprint bytes on the device at a time; the index is searched in resident passes
+    bool paged_replay = false;       // hidden --paged-replay: the query file is read in the first resident pass only, the later ones replay the reads' saved hash lists
+    bool paged_reread = false;       // hidden --paged-reread: every resident pass reads the query file again (the default, said aloud; wins over --paged-replay)
     std::string gather;         // several devices: "rccl" | "host" (taxor_gpu_comm transports) | "none" (independent workers, each
                                 // fetching its own results); empty = rccl when the devices are distinct, host when one repeats
 };
@@ -1382,6 +1384,8 @@ int main(int argc, char **argv)
             if (n < 1 || n > (1ll << 24)) die("Validation failed for option --device-index-budget: Value not in range [1,16777216].");
             cfg.index_budget_mib = (uint64_t)n;
         }
+        else if (k == "--paged-replay") cfg.paged_replay = true;
+        else if (k == "--paged-reread") cfg.paged_reread = true;
         else if (k == "--expect") cfg.expect_file = val();
         else if (k == "--sequential") cfg.sequential = true;
         else if (k == "--device-parse") cfg.device_parse = true;
@@ -1408,6 +1412,12 @@ int main(int argc, char **argv)
                             "                           read's results are merged on the device.  Taken by itself when the index exceeds the device's\n"
                             "                           free memory.  ONE device, a query file that can be read again (no pipe); the output is\n"
                             "                           byte-identical to the resident search.  A BAM query file is read once per pass like any other.\n"
+                            "  --paged-replay           with --device-index-budget: read, inflate, pack and hash the query in the first pass only; every\n"
+                            "                           read's hash list is kept in host memory (8 bytes per hash) and the later passes replay the lists\n"
+                            "                           without opening the file.  Same output.  When the lists' bound does not fit the host's available\n"
+                            "                           memory the run reads the file again in every pass instead, and says so.  Not the default: it has\n"
+                            "                           not been measured against re-reading from a file yet (docs/EXPERIMENTS.md).\n"
+                            "  --paged-reread           the default said aloud: read the query file again in every pass; wins over --paged-replay.\n"
                             "BAM input: the BGZF blocks are inflated on --threads threads, one thread walks the records (block_size, flag, l_seq, read_name)\n"
                             "                           and copies the 4-bit SEQ fields into a page-locked buffer; CIGAR, QUAL and tags are never read.  A\n"
                             "                           missing BGZF end-of-file block is a warning; CRAM and SAM text are refused.  With TAXOR_CLI_TRACE the\n"
@@ -1589,23 +1599,66 @@ int main(int argc, char **argv)
                 std::vector<uint64_t> idl, rl;
                 std::vector<char> text;
                 std::vector<taxor_gpu_prior> pri;
+                // The query is read, inflated, packed and hashed in pass 0 only: with capture on, every batch leaves its reads' hash lists
+                // in host memory (taxor_gpu_search_take_saved), kept here with the batch's ids and read offsets, and passes 1 .. n-1 replay
+                // the kept batches (taxor_gpu_search_saved_begin) without opening the file.  The lists' store is metered like the results':
+                // a bound from the file sizes up front (8 B per hash at the densest selection the index's k, s, t admit), MemAvailable
+                // while it grows.  This is the route of --paged-replay; without it, and where the store does not fit, the run re-reads the file in
+                // every pass.  Either way one line on stderr says what was done with the query.
+                struct Kept { taxor_gpu_saved *lists = nullptr; fastx::IdList ids; std::vector<uint64_t> offsets; };
+                std::vector<Kept> kept;
+                uint64_t kept_bytes = 0, lists_bytes = 0;      // everything kept per batch / of it: the saved hash lists
+                bool replay = passes > 1 && cfg.paged_replay && !cfg.paged_reread;
+                std::string reread_why = cfg.paged_reread ? "--paged-reread" : "the default; --paged-replay keeps the reads' hash lists in host memory instead";
+                if (replay) {
+                    uint64_t bases = 0;         // what the files can hold: a compressed byte at four bases (BAM: 4-bit sequences, deflated)
+                    for (const auto &q : queries) {
+                        struct stat sb;
+                        if (stat(q.c_str(), &sb) != 0) continue;
+                        auto ends = [&](const char *e) { const size_t m = strlen(e); return q.size() > m && q.compare(q.size() - m, m, e) == 0; };
+                        bases += (uint64_t)sb.st_size * (ends(".gz") || ends(".bz2") || ends(".bam") ? 4 : 1);
+                    }
+                    const uint64_t bound = taxor_saved_bytes_bound(bases, view->use_syncmer, view->kmer_size, view->syncmer_size, view->t_syncmer);
+                    const uint64_t avail = taxor::host_memory_available();
+                    if (!taxor_saved_store_fits(bound, avail)) {
+                        replay = false;
+                        reread_why = "the reads' saved hash lists may need " + std::to_string(bound) + " bytes of host memory, MemAvailable is " + std::to_string(avail) + " bytes";
+                    }
+                }
+                if (passes > 1 && !replay) fprintf(stderr, "taxor search: the query is read again in every pass (%s)\n", reread_why.c_str());
+                auto drop_kept = [&]() {
+                    for (Kept &k : kept) taxor_gpu_saved_free(k.lists);
+                    std::vector<Kept>().swap(kept);
+                    kept_bytes = 0;
+                };
+                // pass 0 only: the store is given up -- what it held goes, pass 0's results stay, the file is read again from pass 1 on
+                auto give_up_replay = [&](const std::string &why_not) {
+                    fprintf(stderr, "taxor search: the query is read again in every pass (%s)\n", why_not.c_str());
+                    drop_kept();
+                    replay = false;
+                    if (taxor_gpu_search_capture(s, 0) != TAXOR_OK) die(taxor_gpu_last_error());
+                };
                 const double t_search0 = now();
                 for (uint32_t p = 0; p < passes; ++p) {
                     const double tl = now();
                     if (taxor_gpu_index_load_pass(idx, view, p) != TAXOR_OK) die(taxor_gpu_last_error());
                     t_index += now() - tl;
                     const bool last_pass = p + 1 == passes;
+                    const bool capturing = replay && p == 0;
+                    if (taxor_gpu_search_capture(s, capturing ? 1 : 0) != TAXOR_OK) die(taxor_gpu_last_error());
                     size_t bi = 0;
-                    for (size_t f = 0; f < queries.size(); ++f)
-                        t_reads += produce_batches(queries[f], seq_cfg, false, pool, [&](std::unique_ptr<Batch> b) {
-                            if (b->end_of_file) return;
-                            Batch &bt = *b;
+                    // one batch of one pass: from its bases (lists == nullptr) or from its saved hash lists
+                    auto process = [&](Batch &bt, const taxor_gpu_saved *lists) {
                             const uint64_t n = bt.ids.size();
                             const double t1 = now();
                             taxor_gpu_results res{};
                             const bool nibbles = bt.raw_kind == 'B';      // a BAM chunk: its 4-bit sequences are unpacked on the device
                             bt.raw_kind = 0;
                             auto run = [&]() -> int {
+                                if (lists) {
+                                    const int rb = taxor_gpu_search_saved_begin(s, lists);
+                                    return rb != TAXOR_OK ? rb : taxor_gpu_search_batch_end(s, &res);
+                                }
                                 if (!nibbles) return taxor_gpu_search_batch(s, bt.bases.data(), bt.offsets.data(), n, &res);
                                 const taxor_nibble_segment seg{(const uint8_t *)bt.raw.data(), bt.nib_off.data(), bt.nib_len.data(), bt.nib_rev.data(), n};
                                 const int rb = taxor_gpu_search_nibbles_begin(s, &seg, 1);
@@ -1613,12 +1666,42 @@ int main(int argc, char **argv)
                             };
                             int rc = run();
                             if (rc == TAXOR_E_ALPHABET && !nibbles && strip_space_and_digits(bt)) rc = run();
+                            if (rc == TAXOR_E_NOMEM && capturing && replay) {      // (a kernel that commits every mapping in full refuses the lists' reservation)
+                                give_up_replay("a batch's hash lists found no room: " + std::string(taxor_gpu_last_error()));
+                                rc = run();
+                            }
                             if (rc != TAXOR_OK) die(taxor_gpu_last_error());
+                            if (capturing && replay) {          // (replay goes off below when the store stops fitting: the rest of pass 0 keeps nothing)
+                                taxor_gpu_saved *sv = nullptr;
+                                if (taxor_gpu_search_take_saved(s, &sv) != TAXOR_OK) die(taxor_gpu_last_error());
+                                const uint64_t need = taxor_gpu_saved_bytes(sv) + bt.ids.data.size() + (bt.ids.off.size() + bt.offsets.size()) * 8;
+                                const uint64_t avail = taxor::host_memory_available();
+                                if (avail && avail < (1ull << 29)) {
+                                    // the lists are in memory already, so what is left is the figure: below half a gibibyte -- twice what the
+                                    // results' store below asks for, so that the lists go before the results' check can end the run
+                                    taxor_gpu_saved_free(sv);
+                                    give_up_replay("the reads' saved hash lists no longer fit host memory: " + std::to_string(kept_bytes + need) + " bytes kept so far, MemAvailable is " +
+                                                   std::to_string(avail) + " bytes");
+                                } else {
+                                    kept.emplace_back();
+                                    kept.back().lists = sv;
+                                    kept.back().ids = bt.ids;
+                                    kept.back().offsets = bt.offsets;
+                                    kept_bytes += need;
+                                    lists_bytes += taxor_gpu_saved_bytes(sv);
+                                }
+                            }
                             if (store.size() <= bi) store.resize(bi + 1);
                             if (!last_pass) {
                                 const uint32_t *key = nullptr;
                                 if (taxor_gpu_results_keys(s, &key) != TAXOR_OK) die(taxor_gpu_last_error());
-                                const uint64_t need = (n + 1) * 8 + res.n_tuples * 16, avail = taxor::host_memory_available();
+                                const uint64_t need = (n + 1) * 8 + res.n_tuples * 16;
+                                uint64_t avail = taxor::host_memory_available();
+                                if (avail && need + (1ull << 28) > avail && capturing && replay) {      // the saved lists go first: the run does not end on their account
+                                    give_up_replay("the passes' results need the memory the reads' saved hash lists hold: " + std::to_string(kept_bytes) + " bytes of lists dropped, MemAvailable was " +
+                                                   std::to_string(avail) + " bytes");
+                                    avail = taxor::host_memory_available();
+                                }
                                 if (avail && need + (1ull << 28) > avail)
                                     die("the passes' results no longer fit host memory: " + std::to_string(stored + need) + " bytes kept so far, MemAvailable is " + std::to_string(avail) + " bytes.");
                                 stored += need;
@@ -1663,9 +1746,34 @@ int main(int argc, char **argv)
                             ++bi;
                             t_compute += now() - t1;
                             t_search += now() - t1;
-                            pool.put(std::move(b));
-                        }, (uint32_t)f, 1);
+                    };
+                    if (p == 0 || !replay) {
+                        for (size_t f = 0; f < queries.size(); ++f)
+                            t_reads += produce_batches(queries[f], seq_cfg, false, pool, [&](std::unique_ptr<Batch> b) {
+                                if (b->end_of_file) return;
+                                process(*b, nullptr);
+                                pool.put(std::move(b));
+                            }, (uint32_t)f, 1);
+                    } else {
+                        Batch bt;           // carries a kept batch's ids and offsets: what the last pass formats and feeds the profile with
+                        for (Kept &k : kept) {
+                            bt.ids = std::move(k.ids);
+                            bt.offsets = std::move(k.offsets);
+                            process(bt, k.lists);
+                            if (last_pass) {
+                                taxor_gpu_saved_free(k.lists);
+                                k.lists = nullptr;
+                            } else {
+                                k.ids = std::move(bt.ids);
+                                k.offsets = std::move(bt.offsets);
+                            }
+                        }
+                    }
+                    if (p == 0 && replay)
+                        fprintf(stderr, "taxor search: passes 1 to %u replay %llu batch%s from %llu bytes of saved hash lists (the query file is read once)\n", passes - 1,
+                                (unsigned long long)kept.size(), kept.size() == 1 ? "" : "es", (unsigned long long)lists_bytes);
                 }
+                drop_kept();
                 t_search_wall += now() - t_search0;
                 if (tune_env("TAXOR_CLI_TRACE"))
                     fprintf(stderr, "[trace] paged search: %u passes, %.3f s waiting for uploads, %.2f GB of earlier passes' results held at most\n", passes,

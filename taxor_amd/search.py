@@ -495,6 +495,29 @@ class Searcher:
         check(_lib.lib().taxor_gpu_search_merge_prior(self._h, arr, len(priors)))
         return self.fetch()
 
+    # --- saved hash lists: capture and replay ----------------------------------------------------------------
+    def capture(self, on=True):
+        """taxor_gpu_search_capture: while on, every batch also leaves its hash lists on the host (take_saved)"""
+        check(_lib.lib().taxor_gpu_search_capture(self._h, 1 if on else 0))
+
+    def take_saved(self) -> "SavedBatch":
+        """the saved batch of the last batch that ran with capture on (taxor_gpu_search_take_saved)"""
+        h = C.c_void_p()
+        check(_lib.lib().taxor_gpu_search_take_saved(self._h, C.byref(h)))
+        return SavedBatch(h)
+
+    def search_saved(self, saved: "SavedBatch") -> SearchResults:
+        """the batch again from its saved hash lists (taxor_gpu_search_saved_begin + _batch_end): nothing is packed or hashed"""
+        check(_lib.lib().taxor_gpu_search_saved_begin(self._h, saved._h))
+        res = _lib.Results()
+        check(_lib.lib().taxor_gpu_search_batch_end(self._h, C.byref(res)))
+        return _results(res)
+
+    def search_saved_pass(self, saved: "SavedBatch") -> PassResults:
+        """search_saved + the tuples' keys: one pass's share of a batch on a paged index"""
+        r = self.search_saved(saved)
+        return PassResults(r, self.result_keys(r.user_bin.size))
+
     # --- phases -------------------------------------------------------------------------------------------
     def upload(self, bases, offsets):
         b, o = self._batch(bases, offsets)
@@ -566,6 +589,52 @@ class Searcher:
         check(_lib.lib().taxor_gpu_bulk_contains(self._h, _p(h), h.size, int(thr), C.byref(res)))
         r = _results(res)
         return r.user_bin, r.count
+
+
+class SavedBatch:
+    """A batch's saved hash lists (taxor_gpu_saved): owned by this object, freed by close().  The arrays are VIEWS of the library's
+    own host memory (the C ABI's read-only pointers), valid until close()."""
+
+    PARAMS = ("use_syncmer", "kmer_size", "syncmer_size", "t_syncmer", "scaling", "model", "window_size", "error_rate", "ratio")
+
+    def __init__(self, h):
+        self._h = h
+        v = _lib.SavedView()
+        check(_lib.lib().taxor_gpu_saved_view_get(h, C.byref(v)))
+        n, t, ns = int(v.n_reads), int(v.total_hashes), int(v.n_sub_batches)
+        arr = lambda p, m, dt: np.ctypeslib.as_array(p, shape=(m,)) if m else np.zeros(0, dt)
+        self.n_reads, self.total_hashes, self.n_sub_batches = n, t, ns
+        self.read_len = arr(v.read_len, n, np.uint32)
+        self.n_hashes = arr(v.n_hashes, n, np.uint32)
+        self.threshold = arr(v.threshold, n, np.uint64)
+        self.hash_off = np.ctypeslib.as_array(v.hash_off, shape=(n + 1,))
+        self.hashes = arr(v.hashes, t, np.uint64)
+        self.sub_first = np.ctypeslib.as_array(v.sub_first, shape=(ns + 1,))
+        self.order = arr(v.order, n, np.uint32)
+        self.params = {f: getattr(v, f) for f in self.PARAMS}
+
+    @property
+    def nbytes(self):
+        return int(_lib.lib().taxor_gpu_saved_bytes(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            for f in ("read_len", "n_hashes", "threshold", "hash_off", "hashes", "sub_first", "order"):
+                setattr(self, f, None)
+            _lib.lib().taxor_gpu_saved_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def saved_bytes_bound(bases, use_syncmer=True, k=22, s=12, t=5):
+    """taxor_saved_bytes_bound (host only): host bytes the saved hash lists of `bases` bases of query may need"""
+    return int(_lib.lib().taxor_saved_bytes_bound(int(bases), 1 if use_syncmer else 0, int(k), int(s), int(t)))
+
+
+def saved_store_fits(bound_bytes, available_bytes):
+    """taxor_saved_store_fits (host only): True = keep the lists and replay, False = re-read the query every pass"""
+    return bool(_lib.lib().taxor_saved_store_fits(int(bound_bytes), int(available_bytes)))
 
 
 class Comm:
