@@ -100,8 +100,9 @@ enum {
     TAXOR_SEARCH_GROUP_ALWAYS = 2u,    /* group each level's work items by IXF whatever the sub-batch size */
     TAXOR_SEARCH_NO_SMALL_PATH = 4u,   /* calls of a few thousand reads take the pipeline of large batches */
     TAXOR_SEARCH_SPLIT_ALWAYS = 8u,    /* root work items split over column ranges whatever the batch size */
-    TAXOR_SEARCH_FORCE_TREE_STALL = 16u /* test hook: a small call's one-launch traversal gives up at its first empty poll, so
+    TAXOR_SEARCH_FORCE_TREE_STALL = 16u,/* test hook: a small call's one-launch traversal gives up at its first empty poll, so
                                           every piece takes the recovery path (rerun level by level) */
+    TAXOR_SEARCH_NO_SCREEN = 32u       /* large batches count the root's rows without first screening them on the root's 2-bit plane */
 };
 typedef struct taxor_gpu_searcher taxor_gpu_searcher;
 int taxor_gpu_searcher_create(taxor_gpu_index *idx, const taxor_gpu_search_params *prm, taxor_gpu_searcher **out);

@@ -407,7 +407,14 @@ typedef struct {
     uint32_t small_pieces_rerun;     /* pieces of a small call that were classified again through the pipeline of large batches, for
                                         any reason (a queue, the hit buffer or the result area too small, or a stall as above);
                                         0 says that every piece of the call was assembled by the lanes' own finalize */
+    uint64_t screen_plane_loads;     /* rows of the root's 2-bit plane read by the screen of large batches (three per screened hash); they
+                                        are in level_requested_bytes[0] with their bytes and in level_row_reads[0] as the fraction of a
+                                        full row that a plane row is.  0: nothing was screened */
 } taxor_gpu_run_stats;
+/* The root's 2-bit plane (a quarter-size copy of the root's rows holding fingerprint & 3, 16 bins per 32-bit word, low bins first;
+ * derived on the device, never stored): *rows and *plane_stride as the searches see it, both 0 when the root has none; with out != NULL
+ * (len = rows * plane_stride) the plane itself, derived first if the root was written since. */
+int taxor_gpu_index_root_plane(taxor_gpu_index *idx, uint8_t *out, uint64_t len, uint64_t *rows, uint32_t *plane_stride);
 int taxor_gpu_batch_stats(taxor_gpu_searcher *s, taxor_gpu_run_stats *out);
 /* Measurement aid: a searcher created while TAXOR_PROFILE_PHASES=1 is set launches instrumented instantiations of the
  * two big kernels (s_memtime marks at their phase boundaries, summed over blocks).  Returns and clears 16 cycle sums:

@@ -45,6 +45,7 @@ class SearchParams(C.Structure):
 
 
 SEARCH_NO_PRUNE, SEARCH_GROUP_ALWAYS, SEARCH_NO_SMALL_PATH, SEARCH_SPLIT_ALWAYS, SEARCH_FORCE_TREE_STALL = 1, 2, 4, 8, 16
+SEARCH_NO_SCREEN = 32
 
 
 THR_PERCENTAGE, THR_SYNCMER, THR_KMER, THR_FRACMINHASH = 0, 1, 2, 3
@@ -62,7 +63,8 @@ class RunStats(C.Structure):
                 ("query_bytes", C.c_uint64), ("query_touched_bytes", C.c_uint64), ("query_launches", C.c_uint32), ("query_ms", C.c_float),
                 ("syncmer_ms", C.c_float), ("finalize_ms", C.c_float), ("total_ms", C.c_float),
                 ("level_ms", C.c_float * 8), ("level_requested_bytes", C.c_uint64 * 8), ("level_row_reads", C.c_uint64 * 8),
-                ("level_sparse_loads", C.c_uint64 * 8), ("tree_stalls_recovered", C.c_uint32), ("small_pieces_rerun", C.c_uint32)]
+                ("level_sparse_loads", C.c_uint64 * 8), ("tree_stalls_recovered", C.c_uint32), ("small_pieces_rerun", C.c_uint32),
+                ("screen_plane_loads", C.c_uint64)]
 
 
 class CommStats(C.Structure):
@@ -259,6 +261,7 @@ SIGNATURES = {
     "taxor_gpu_index_fill_random": (C.c_int, [_P, C.c_uint64, C.c_uint64]),
     "taxor_gpu_index_upload_bin": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.c_uint64]),
     "taxor_gpu_index_download_ixf": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64]),
+    "taxor_gpu_index_root_plane": (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
     "taxor_gpu_index_build_ixf": (C.c_int, [_P, C.c_uint64, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "taxor_gpu_searcher_create": (C.c_int, [_P, C.POINTER(SearchParams), C.POINTER(_P)]),
     "taxor_gpu_searcher_destroy": (None, [_P]),

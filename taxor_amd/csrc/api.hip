@@ -64,6 +64,17 @@ struct taxor_gpu_index {
     // part j when the row is cut into root_pmax parts (every boundary is a unit boundary at which a bin run ends)
     uint32_t root_pmax = 1;
     uint16_t root_cut[9] = {};
+    // the root's 2-bit plane (kernels.hip, query_screen_range): never in a file, derived on the device from the root's rows by the
+    // first large-batch search that wants it (root_plane_ensure) and derived AGAIN after anything that may have written the rows.
+    // Every entry point that writes fingerprints, or hands out a pointer through which its caller does, calls
+    // root_plane_invalidate: index_upload (taxor_gpu_index_create, taxor_index_upload and the re-layout it runs),
+    // taxor_index_slab (the replica's slab arrives over RCCL), taxor_index_ixf_info (the builder's and the re-layout's way to an
+    // IXF's rows), taxor_gpu_index_fill_random, taxor_gpu_index_upload_bin (k_scatter_column).  plane_stride = 0: the root is not
+    // eligible (index_create_impl), or the allocation failed -- the index then works as it always did
+    uint8_t *d_plane = nullptr;
+    uint32_t plane_stride = 0;
+    bool plane_valid = false;
+    std::mutex plane_mu;
     // the builder's scratch (builder.hip: peeling state, union table, mark bytes), kept from one build of this index to the next --
     // hipMalloc / hipFree of GB-sized blocks takes the driver anything between nothing and a second -- and released with the index
     void *build_ctx = nullptr;
@@ -87,6 +98,31 @@ struct taxor_gpu_index {
     std::mutex searchers_mu;
     std::vector<taxor_gpu_searcher *> searchers; // the index's searchers (lanes not listed): load_pass checks that none has a run in flight
 };
+
+static void root_plane_invalidate(taxor_gpu_index *idx)
+{
+    std::lock_guard<std::mutex> lk(idx->plane_mu);
+    idx->plane_valid = false;
+}
+
+// the plane for a launch on `st`, or nullptr (no plane: not eligible, or no memory for it -- never an error).  Derived under the
+// lock and waited for, so that a second searcher on a stream of its own never sees a half-written plane; once per index and write
+static const uint8_t *root_plane_ensure(taxor_gpu_index *idx, hipStream_t st)
+{
+    if (!idx->plane_stride) return nullptr;
+    std::lock_guard<std::mutex> lk(idx->plane_mu);
+    if (idx->plane_valid) return idx->d_plane;
+    if (!idx->d_plane && hipMalloc((void **)&idx->d_plane, idx->rows[0] * (uint64_t)idx->plane_stride) != hipSuccess) {
+        (void)hipGetLastError();        // the failure is not the next launch's
+        idx->d_plane = nullptr;
+        idx->plane_stride = 0;
+        return nullptr;
+    }
+    launch_build_plane(idx->h_ixf[0].data, idx->rows[0], idx->h_ixf[0].stride, idx->d_plane, idx->plane_stride, st);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return nullptr;
+    idx->plane_valid = true;
+    return idx->d_plane;
+}
 
 struct SubBatch {
     uint32_t first, n;
@@ -127,6 +163,7 @@ struct taxor_gpu_searcher {
     bool split_always = false;   // TAXOR_SEARCH_SPLIT_ALWAYS: root items in column parts whatever the batch size (parity tests)
     bool force_tree_stall = false; // TAXOR_SEARCH_FORCE_TREE_STALL: the one-launch traversal's watchdog fires at once (recovery-path test)
     bool small_path = true;      // !TAXOR_SEARCH_NO_SMALL_PATH: calls of up to a few thousand reads go through the lanes below
+    bool screen = true;          // !TAXOR_SEARCH_NO_SCREEN: large batches screen the root's rows on its 2-bit plane, where it has one
     size_t lds_query = 0;
 
     // batch-resident input
@@ -283,6 +320,7 @@ static bool view_is_search_layout(const taxor_hixf_view *v)
 
 static int index_upload(taxor_gpu_index *idx, const taxor_hixf_view *v, void (*progress)(void *, uint64_t), void *pctx)
 {
+    root_plane_invalidate(idx);
     if (!view_is_search_layout(v)) {
         // another writer's layout (ixf_layout.h): transposed on the device while it is uploaded (relayout.hip).  The slab is final
         // only when the last chunk has landed (a bin-major chunk writes a column range of every row), so progress is one step
@@ -561,6 +599,36 @@ static int index_create_impl(const taxor_hixf_view *v, int device, bool upload, 
             }
         }
     }
+    {   // Does the root get a 2-bit plane?  A resident index only, rows of >= 512 B (the plane row is then at least one whole 128-B
+        // line and at most about a quarter of the row's lines), and few split runs: a run of len >= 2 bins has a 2-bit sum of about
+        // len * d / 4 after d hashes, so sum + (n - d) * len stays above any threshold <= n for every d <= n -- the screen never kills
+        // it and its units are counted exactly over all n hashes.  With S = the 128-B lines of a row that hold split runs, L the
+        // lines of a row, thr ~ n / 2 and d2 ~ 0.71 n, an item asks for about 0.71 n * L / 4 + n * S lines with the screen and
+        // 0.5 n * L + 0.5 n * S without: the screen pays while S < 0.645 L.  The plane is built when S <= L / 2 (the rest is margin
+        // for the screen's own bookkeeping) and the split runs cover at most half of the Q_MAXU = 32 units an item may keep alive
+        // (beyond Q_MAXU every item falls back to the rows and the plane is pure cost)
+        const IxfDesc &r0 = idx->h_ixf[0];
+        if (!paged_budget && r0.stride >= 512 && r0.bin_base == 0) {
+            std::vector<uint8_t> unit_split((size_t)r0.units, 0);
+            uint32_t run0 = 0;
+            for (uint32_t b = 0; b < r0.bins; ++b) {
+                if (binfo[b] >> 30) {                     // the run's last bin (merged bins are runs of one)
+                    if (b > run0)
+                        for (uint32_t u = run0 >> 4; u <= (b >> 4); ++u) unit_split[u] = 1;
+                    run0 = b + 1;
+                }
+            }
+            uint32_t split_units = 0, split_lines = 0;
+            for (uint32_t u0 = 0; u0 < r0.units; u0 += 8) {       // eight 16-B units to a 128-B line
+                uint32_t in_line = 0;
+                for (uint32_t u = u0; u < std::min(u0 + 8, r0.units); ++u) in_line += unit_split[u];
+                split_units += in_line;
+                split_lines += in_line ? 1u : 0u;
+            }
+            const uint32_t lines = (r0.stride + 127) / 128;
+            if (split_units <= 16 && split_lines <= lines / 2) idx->plane_stride = plane_stride_of(r0.stride);
+        }
+    }
     idx->h_binfo = binfo;
     idx->h_bin_base.resize(n + 1);
     for (uint64_t i = 0; i < n; ++i) idx->h_bin_base[i] = idx->h_ixf[i].bin_base;
@@ -781,6 +849,7 @@ extern "C" __attribute__((visibility("hidden"))) int taxor_index_slab(taxor_gpu_
                                                                       const uint64_t **ixf_off, uint64_t *n_ixf, int *device)
 {
     if (!idx) return -1;
+    root_plane_invalidate(idx);
     *slab = idx->d_slab;
     *slab_bytes = idx->slab_bytes;
     *ixf_off = idx->slab_off.data();
@@ -809,6 +878,7 @@ extern "C" void taxor_gpu_index_destroy(taxor_gpu_index *idx)
     if (idx->build_ctx && idx->build_ctx_free) idx->build_ctx_free(idx->build_ctx);
     idx->build_ctx = nullptr;
     if (idx->d_slab) (void)hipFree(idx->d_slab);
+    if (idx->d_plane) (void)hipFree(idx->d_plane);
     if (idx->d_ixf) (void)hipFree(idx->d_ixf);
     if (idx->d_binfo) (void)hipFree(idx->d_binfo);
     if (idx->d_ubin) (void)hipFree(idx->d_ubin);
@@ -822,6 +892,7 @@ extern "C" __attribute__((visibility("hidden"))) int taxor_index_ixf_info(taxor_
                                                                           int *device)
 {
     if (!idx || ixf >= idx->h_ixf.size()) return -1;
+    if (ixf == 0) root_plane_invalidate(idx);
     *data = const_cast<uint8_t *>(idx->h_ixf[ixf].data);
     *stride = idx->h_ixf[ixf].stride;
     *seg_len = idx->h_ixf[ixf].seg_len;
@@ -868,6 +939,7 @@ extern "C" int taxor_gpu_index_fill_random(taxor_gpu_index *idx, uint64_t ixf, u
 {
     if (!idx || ixf >= idx->h_ixf.size()) return fail(TAXOR_E_ARG, "fill_random: bad IXF id");
     HIP_TRY(hipSetDevice(idx->device));
+    if (ixf == 0) root_plane_invalidate(idx);
     const uint64_t bytes = idx->rows[ixf] * idx->h_ixf[ixf].stride; // multiple of 64
     launch_fill_random(const_cast<uint8_t *>(idx->h_ixf[ixf].data), bytes, seed, nullptr);
     HIP_TRY(hipGetLastError());
@@ -973,6 +1045,7 @@ extern "C" int taxor_gpu_index_upload_bin(taxor_gpu_index *idx, uint64_t ixf, ui
     if (!idx || ixf >= idx->h_ixf.size() || bin >= idx->h_ixf[ixf].bins || rows != idx->rows[ixf] || !column)
         return fail(TAXOR_E_ARG, "upload_bin: bad arguments");
     HIP_TRY(hipSetDevice(idx->device));
+    if (ixf == 0) root_plane_invalidate(idx);
     uint8_t *d_col = nullptr;
     HIP_TRY(hipMalloc((void **)&d_col, rows));
     hipError_t e = hipMemcpy(d_col, column, rows, hipMemcpyHostToDevice);
@@ -983,6 +1056,24 @@ extern "C" int taxor_gpu_index_upload_bin(taxor_gpu_index *idx, uint64_t ixf, ui
     if (e == hipSuccess) e = hipDeviceSynchronize();
     (void)hipFree(d_col);
     if (e != hipSuccess) return fail(TAXOR_E_HIP, "upload_bin: %s", hipGetErrorString(e));
+    return TAXOR_OK;
+}
+
+extern "C" int taxor_gpu_index_root_plane(taxor_gpu_index *idx, uint8_t *out, uint64_t len, uint64_t *rows, uint32_t *plane_stride)
+{
+    if (!idx || !rows || !plane_stride) return fail(TAXOR_E_ARG, "root_plane: null argument");
+    HIP_TRY(hipSetDevice(idx->device));
+    *rows = 0;
+    *plane_stride = 0;
+    if (!idx->plane_stride) return TAXOR_OK;
+    if (out) {
+        const uint8_t *p = root_plane_ensure(idx, nullptr);
+        if (!p) return TAXOR_OK;             // no memory for it: the index has none
+        if (len != idx->rows[0] * (uint64_t)idx->plane_stride) return fail(TAXOR_E_ARG, "root_plane: the buffer does not match the plane");
+        HIP_TRY(hipMemcpy(out, p, len, hipMemcpyDeviceToHost));
+    }
+    *rows = idx->rows[0];
+    *plane_stride = idx->plane_stride;
     return TAXOR_OK;
 }
 
@@ -1061,7 +1152,9 @@ static int searcher_create_impl(taxor_gpu_index *idx, const taxor_gpu_search_par
     s->split_always = (prm->flags & TAXOR_SEARCH_SPLIT_ALWAYS) != 0;
     s->force_tree_stall = (prm->flags & TAXOR_SEARCH_FORCE_TREE_STALL) != 0;
     s->small_path = !(prm->flags & TAXOR_SEARCH_NO_SMALL_PATH);
+    s->screen = !(prm->flags & TAXOR_SEARCH_NO_SCREEN);
     if (const char *e = tune_env("TAXOR_QUERY_PRUNE")) s->prune = atoi(e) != 0;
+    if (const char *e = tune_env("TAXOR_QUERY_SCREEN")) s->screen = s->screen && atoi(e) != 0;
     if (const char *e = tune_env("TAXOR_FIRST_DIV")) { const int v = atoi(e); if (v >= 1 && v <= 64) s->first_div = (uint32_t)v; }
     if (const char *e = tune_env("TAXOR_SUB_READS")) { const long v = atol(e); if (v >= 1 && v <= (1 << 20)) { s->prm.sub_batch_reads = (uint32_t)v; s->auto_sub_reads = false; } }
     {   // syncmer launches that run beside a query kernel keep to two blocks per CU: at full occupancy (three) the
@@ -1499,6 +1592,14 @@ int run_query(taxor_gpu_searcher *s, const uint64_t *d_hashes, const uint64_t *d
         // single-wave instantiation, sixteen blocks per CU; raw bulk_count calls (d_counts_out) stay on the general one
         const bool small = !d_counts_out && only_ixf < 0 && lvl < (uint32_t)MAX_LEVELS && s->grid_query_small[lvl] > 0 &&
                            s->mean_read_len < 2600 && !s->d_prof;
+        // the root level of a large batch (the level-synchronous launches of a searcher's own run, never a lane's): rows screened on
+        // the root's 2-bit plane where the index has one.  No pruning, no screen: the unpruned run stays an independent result
+        q.plane = nullptr;
+        q.plane_stride = 0;
+        if (lvl == 0 && !small && s->screen && q.prune && !s->lane_mode && !s->d_prof && only_ixf < 0 && root_parts == 1) {
+            q.plane = root_plane_ensure(s->idx, s->st);
+            q.plane_stride = q.plane ? idx->plane_stride : 0;
+        }
         if (small) {
             QueryArgs qs = q;
             qs.max_stride = idx->lvl_max_stride[lvl];
@@ -2571,6 +2672,7 @@ extern "C" int taxor_gpu_batch_sync(taxor_gpu_searcher *s)
             st.n_work_items = s->h_ctr.n_work;
             st.query_bytes = s->h_ctr.query_bytes;
             st.query_touched_bytes = s->h_ctr.touched_bytes;
+            st.screen_plane_loads = s->h_ctr.plane_loads;
             st.algorithmic_bytes = s->packed_in_bytes + st.query_bytes + 8 * st.n_reads + 12 * st.n_tuples;
             st.query_ms = st.syncmer_ms = st.finalize_ms = st.total_ms = 0.f;
             for (int l = 0; l < 8; ++l) {
@@ -3290,6 +3392,7 @@ extern "C" int taxor_gpu_bulk_contains(taxor_gpu_searcher *s, const uint64_t *ha
         if (int rc = check_flags(s, &rerun)) return rc;
         if (!rerun) {
             s->ran = s->synced = true;
+            s->stats.screen_plane_loads = s->h_ctr.plane_loads;      // (what a test of the root's screen asks taxor_gpu_batch_stats for)
             return taxor_gpu_batch_fetch(s, out);
         }
     }

@@ -61,7 +61,8 @@ struct Counters {
     alignas(128) unsigned long long query_bytes;   // sum n_h*3*bins over work items
     unsigned long long n_work;                     // work items processed
     unsigned long long touched_bytes;              // bytes the query kernel actually requested (after pruning)
-    unsigned long long pad1[13];
+    unsigned long long plane_loads;                // plane rows read by the root's screen (k_query_level<..., SCREEN>)
+    unsigned long long pad1[12];
     // per HIXF level (levels >= 7 share the last entry): requested bytes and fingerprint-row reads (one per hash and row
     // in the dense phase, one per hash, row and surviving unit in the sparse phase) -- a narrow row is bound by the
     // number of DRAM rows opened, not by its bytes
@@ -138,6 +139,8 @@ struct QueryArgs {
     uint32_t dense_max_stride;// rows of at most this many bytes are counted densely to the end (a 16-B load of the sparse phase costs HBM
                               // the same 128-B line as the row itself): no alive-unit bookkeeping for them; 0 = prune every width
     uint32_t tally_mode;      // measurement aid (TAXOR_QUERY_TALLY): bit 0 = tally walks every bin, bit 1 = bin info fetched per item
+    const uint8_t *plane;     // level 0 of a large batch only, else nullptr: the root's 2-bit plane (launch_build_plane); with it the launch
+    uint32_t plane_stride;    // takes the SCREEN instantiation.  Bytes per plane row (a multiple of 128)
     unsigned long long *prof; // measurement aid (TAXOR_PROFILE_PHASES=1): 16 per-phase cycle sums, else nullptr
 };
 
@@ -222,6 +225,9 @@ uint64_t launch_gather_ceiling(const uint8_t *data, uint64_t rows, uint32_t stri
                                uint64_t seed, uint32_t *sink, bool nt, hipStream_t st, uint32_t n_ixf = 1, uint64_t spacing = 0);
 void launch_scatter_column(uint8_t *data, uint64_t stride, uint64_t bin, const uint8_t *col, uint64_t rows,
                            hipStream_t st);
+// the 2-bit plane of an IXF: plane row r, word w = (fingerprint[r][16 w + i] & 3) << 2 i for i in 0 .. 15 (bins beyond the row: 0)
+inline uint32_t plane_stride_of(uint32_t stride) { return (stride / 4u + 127u) & ~127u; }
+void launch_build_plane(const uint8_t *data, uint64_t rows, uint32_t stride, uint8_t *plane, uint32_t plane_stride, hipStream_t st);
 
 // the pass's bin info table of a paged index: binfo[i] = full[i] with the child id of a merged bin cleared when resident[child] == 0
 void launch_binfo_pass(const uint32_t *full, const uint8_t *resident, uint32_t *binfo, uint32_t n_bins, uint32_t n_ixf, hipStream_t st);

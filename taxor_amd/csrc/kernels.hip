@@ -1117,6 +1117,98 @@ __device__ __forceinline__ void query_dense_range(const IxfDesc &D, const uint64
     }
 }
 
+// ---- the root's 2-bit plane (SCREEN) -----------------------------------------------------------------------------
+// Plane row r holds fingerprint[r][b] & 3 of every bin, 16 bins per word (bin 16 w + i in bits 2i, 2i + 1 of word w), a quarter of
+// the row's bytes.  XOR commutes with the mask, so a bin whose three fingerprints XOR to fp also XORs to fp & 3 on the plane: the
+// 2-bit match count of a bin is an UPPER BOUND of its exact count, and a run that cannot reach the threshold with it cannot reach
+// it at all.  A thread owns one 16-B piece (64 bins) of every plane row and the hash subset g, g + G, ...; the 64 match bits of a
+// hash go into two words (word 0 | word 1 << 1, word 2 | word 3 << 1: a match is bit 2i of its word) and from there into
+// SCR_PLANES-bit vertical counters, one bit plane per register pair -- 255 hashes per thread and tile, then the counters are added
+// to the LDS tally.  Bit j of match word m is bin 32 m + 16 (j & 1) + (j >> 1) of the piece.
+static constexpr int SCR_PLANES = 8;
+// Reads of fewer hashes are not screened: m2 is then a fifth of the read (d2 = 80 of 87 hashes for a 1-kb read), the item is a
+// handful of memory round trips, and the screen's own evaluation pass and counter flush cost more than the lines it saves
+// (measured: 1-kb reads, ~87 hashes, -6.6 % screened; 2-kb reads, ~174 hashes, +18 % -- docs/EXPERIMENTS.md)
+static constexpr int SCR_MIN_HASHES = 128;
+
+__device__ __forceinline__ uint32_t plane_match16(uint32_t x) { return ~(x | (x >> 1)) & 0x55555555u; }
+
+template <bool NT, int BS, int QC>
+__device__ __forceinline__ void query_screen_range(const IxfDesc &D, const uint8_t *__restrict__ plane, uint32_t pstride,
+                                                   const uint64_t *__restrict__ hp, uint32_t h1, uint4 *sProbe, uint32_t *sC, bool staged)
+{
+    const uint32_t tid = threadIdx.x;
+    const uint32_t pieces = pstride / 16u;
+    for (uint32_t p0 = 0; p0 < pieces; p0 += BS) {          // column passes: 256 pieces (16384 bins) per pass; one in practice
+        const uint32_t ppass = min(pieces - p0, (uint32_t)BS);
+        const uint32_t G = BS / ppass;
+        const uint32_t g = tid / ppass;
+        const uint32_t pc = p0 + (tid - g * ppass);
+        const bool active = g < G;
+        const uint8_t *__restrict__ base = plane + (size_t)pc * 16u;
+        const uint32_t HT = staged ? 255u * G : min((G == 1u) ? (uint32_t)Q_HT : (uint32_t)Q_HT2, (uint32_t)QC);
+        for (uint32_t t0 = 0; t0 < h1; t0 += HT) {
+            const uint32_t nt = min(HT, h1 - t0);
+            const uint4 *pr = sProbe + (staged ? t0 : 0u);
+            if (!staged) {
+                __syncthreads();
+                for (uint32_t i = tid; i < nt; i += BS) {
+                    const ixf_probe p = ixf_probe_key_arith(hp[t0 + i], D.seed, D.seg_len, D.arith);
+                    sProbe[i] = make_uint4(p.row[0], p.row[1], p.row[2], p.fp4);
+                }
+                __syncthreads();
+            }
+            if (!active) continue;
+            uint32_t c0[SCR_PLANES], c1[SCR_PLANES];
+#pragma unroll
+            for (int k = 0; k < SCR_PLANES; ++k) c0[k] = c1[k] = 0u;
+            for (uint32_t i = g; i < nt; i += 2u * G) {      // two hashes = six plane-row loads in flight per lane
+                const bool two = i + G < nt;
+                const uint4 pa = pr[i], pb = pr[two ? i + G : i];
+                const uint4 a0 = ld16<NT>(base + (size_t)pa.x * pstride), a1 = ld16<NT>(base + (size_t)pa.y * pstride),
+                            a2 = ld16<NT>(base + (size_t)pa.z * pstride);
+                uint4 b0 = make_uint4(0, 0, 0, 0), b1 = b0, b2 = b0;
+                if (two) {
+                    b0 = ld16<NT>(base + (size_t)pb.x * pstride);
+                    b1 = ld16<NT>(base + (size_t)pb.y * pstride);
+                    b2 = ld16<NT>(base + (size_t)pb.z * pstride);
+                }
+                const uint32_t fa = (pa.w & 3u) * 0x55555555u, fb = (pb.w & 3u) * 0x55555555u;
+                uint32_t m0 = plane_match16(a0.x ^ a1.x ^ a2.x ^ fa) | plane_match16(a0.y ^ a1.y ^ a2.y ^ fa) << 1;
+                uint32_t m1 = plane_match16(a0.z ^ a1.z ^ a2.z ^ fa) | plane_match16(a0.w ^ a1.w ^ a2.w ^ fa) << 1;
+#pragma unroll
+                for (int k = 0; k < SCR_PLANES; ++k) {
+                    const uint32_t t0_ = c0[k] & m0, t1_ = c1[k] & m1;
+                    c0[k] ^= m0; c1[k] ^= m1;
+                    m0 = t0_; m1 = t1_;
+                }
+                if (two) {
+                    m0 = plane_match16(b0.x ^ b1.x ^ b2.x ^ fb) | plane_match16(b0.y ^ b1.y ^ b2.y ^ fb) << 1;
+                    m1 = plane_match16(b0.z ^ b1.z ^ b2.z ^ fb) | plane_match16(b0.w ^ b1.w ^ b2.w ^ fb) << 1;
+#pragma unroll
+                    for (int k = 0; k < SCR_PLANES; ++k) {
+                        const uint32_t t0_ = c0[k] & m0, t1_ = c1[k] & m1;
+                        c0[k] ^= m0; c1[k] ^= m1;
+                        m0 = t0_; m1 = t1_;
+                    }
+                }
+            }
+            // the tile's counters into the LDS tally (bins past the row -- the plane row's padding -- have none)
+            for (uint32_t j = 0; j < 32u; ++j) {
+                uint32_t v0 = 0u, v1 = 0u;
+#pragma unroll
+                for (int k = 0; k < SCR_PLANES; ++k) {
+                    v0 |= ((c0[k] >> j) & 1u) << k;
+                    v1 |= ((c1[k] >> j) & 1u) << k;
+                }
+                const uint32_t b = pc * 64u + 16u * (j & 1u) + (j >> 1);
+                if (v0 && b < D.stride) atomicAdd(&sC[b], v0);
+                if (v1 && b + 32u < D.stride) atomicAdd(&sC[b + 32u], v1);
+            }
+        }
+    }
+}
+
 // BS threads per block; QC probes fit the LDS staging area.  (256, 1024) is the general instantiation; (64, 256) serves
 // launches of TINY items -- levels of narrow IXFs (<= 512 bins) under short reads -- where an item is a handful of memory
 // round trips and fixed cost: sixteen single-wave blocks per CU keep four times as many items in flight as four
@@ -1138,9 +1230,15 @@ __device__ __forceinline__ void query_dense_range(const IxfDesc &D, const uint64
 // milliseconds per launch.)  Consumers put ~0 back, so the queue is clean for the next launch.  A wait that outlives any
 // plausible run raises FLAG_TREE_STALL, releases the other waiting blocks and leaves -- never a hung GPU, and the host classifies
 // the piece again level by level (api.hip, small_harvest_one).
-template <bool NT, int U, bool PROF = false, int BS = BLK, int QC = Q_CAP, bool TREE = false>
+//
+// SCREEN = true: level 0 of a large batch on an index whose root has a 2-bit plane (a.plane, see query_screen_range).  An item the
+// pruning applies to counts its first d2 hashes on the plane instead of its first dense_end hashes on the rows; the runs whose
+// 2-bit sum can still reach the threshold are the alive AND the candidate set, the tally is cleared, and the staged sparse loop
+// counts them exactly over ALL n hashes.  More than Q_MAXU alive units: the whole item densely, as before.
+template <bool NT, int U, bool PROF = false, int BS = BLK, int QC = Q_CAP, bool TREE = false, bool SCREEN = false>
 __global__ __launch_bounds__(BS) void k_query_level(const QueryArgs a)
 {
+    static_assert(!SCREEN || (!TREE && BS == BLK && !PROF), "the plane screen exists for the large-batch root launch only");
     uint64_t pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t plast = PROF ? __builtin_amdgcn_s_memtime() : 0;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1162,6 +1260,7 @@ __global__ __launch_bounds__(BS) void k_query_level(const QueryArgs a)
     const uint32_t n_parts = (!a.q_in && a.parts > 1u) ? a.parts : 1u;
     const uint32_t n_items = a.q_in ? min(a.ctr->q_n[lvl].v, a.q_cap) : a.n_level0 * n_parts;
     unsigned long long st_bytes = 0, st_touched = 0, st_work = 0, st_rows = 0, st_sparse = 0;
+    unsigned long long st_plane = 0;    // SCREEN: plane-row loads, billed below as full-row equivalents
 
     // Returning atomics on one word are served serially by one L2 channel, ~13 ns each.  A launch of small work items
     // (deeper levels, short reads) issues one per item on the work cursor and one per item on the hit / queue append
@@ -1386,6 +1485,20 @@ __global__ __launch_bounds__(BS) void k_query_level(const QueryArgs a)
             dense_end = (thr >= (uint64_t)n + margin) ? 0u : min(n, (uint32_t)((uint64_t)n + margin - thr));
         }
         uint64_t touched = 0, rows_read = 0, sparse_loads = 0;
+        // SCREEN: a random bin matches a hash on the plane with p = 1/4 and is dead after d hashes once count + (n - d) < thr, i.e.
+        // 0.75 d - 4 sigma(d) > n - thr with sigma(d) = sqrt(3 d / 16): d2 = (n - thr + m2) / 0.75, m2 = 4 sigma at the d that solves
+        // the mean alone (+ 2).  When even all n hashes do not get there (thr below ~n/4) the screen kills nothing and the item takes
+        // the rows as before.  d2 only trades plane against row traffic: any value is exact.
+        uint32_t d2 = 0;
+        if constexpr (SCREEN) {
+            if (n >= (uint32_t)SCR_MIN_HASHES && dense_end > 0u && dense_end < n && thr <= (uint64_t)n) {
+                const float x = (float)((uint64_t)n - thr);
+                const float m2 = 4.0f * sqrtf(0.1875f * (x * (1.0f / 0.75f) + 16.0f)) + 2.0f;
+                const float d = ceilf((x + m2) * (1.0f / 0.75f));
+                if (d <= (float)n) d2 = max((uint32_t)d, 1u);
+            }
+        }
+        const bool screen = SCREEN && d2 > 0u;
 
         const bool staged = n <= (uint32_t)QC; // all probes of this read fit: stage them once for both phases
         if (staged)
@@ -1407,14 +1520,20 @@ __global__ __launch_bounds__(BS) void k_query_level(const QueryArgs a)
         info_of = D.bins ? D.bin_base : 0xFFFFFFFFu;
         __syncthreads();
         PMARK(1)                                                     // 1: clearing the tally, bin info + probe staging
-        query_dense_range<NT, U, BS, QC>(D, hp, 0, dense_end, sProbe, sC, staged);
-        touched += (uint64_t)dense_end * 3ull * (D.units * 16u);      // (= stride for a whole row; a column part reads its own units)
-        rows_read += (uint64_t)dense_end * 3ull;
+        if (screen) {
+            query_screen_range<NT, BS, QC>(D, a.plane, a.plane_stride, hp, d2, sProbe, sC, staged);
+            touched += (uint64_t)d2 * 3ull * a.plane_stride;
+            st_plane += (unsigned long long)d2 * 3ull;
+        } else {
+            query_dense_range<NT, U, BS, QC>(D, hp, 0, dense_end, sProbe, sC, staged);
+            touched += (uint64_t)dense_end * 3ull * (D.units * 16u);      // (= stride for a whole row; a column part reads its own units)
+            rows_read += (uint64_t)dense_end * 3ull;
+        }
         __syncthreads();
         PMARK(2)                                                     // 2: dense phase (row gathers)
 
         bool cand_valid = false;
-        if (dense_end < n) {
+        if (dense_end < n) {      // (always so for a screened item)
             // The remaining hashes probe only the 16-bin units that still matter, in up to three stages; between stages the
             // set is re-evaluated with the counts so far.  A unit matters while it holds
             //   * a LEAF run that can still reach the threshold (or has reached it): its count is reported (:328-331), so it
@@ -1424,12 +1543,13 @@ __global__ __launch_bounds__(BS) void k_query_level(const QueryArgs a)
             // A matching read's merged bins reach the threshold after ~thr / (fraction of its hashes that match) hashes,
             // i.e. well before the last one, and every later stage also drops the random survivors of the stage before: each
             // unit dropped saves a 128-B line per hash and row (what HBM moves for a 16-B load).
-            uint32_t done = dense_end;
+            uint32_t done = screen ? 0u : dense_end;      // after the screen the exact count starts over
             uint32_t chunk = 0;
             bool first_eval = true;
             cand_valid = !a.counts_out && !(a.tally_mode & 1u);
             for (;;) {
-                const uint64_t rem = n - done;
+                uint64_t rem = (screen && first_eval) ? n - d2 : n - done;
+                const bool on_plane = screen && first_eval;   // sC holds 2-bit sums: an upper bound, never proof that a merged bin has passed
                 if (!first_eval) {
                     for (uint32_t i = tid; i < a.map_words; i += BS) sMap[i] = 0;
                     if (tid == 0) sScal[1] = 0;
@@ -1438,13 +1558,16 @@ __global__ __launch_bounds__(BS) void k_query_level(const QueryArgs a)
                 for (uint32_t b = tid; b < nb_round; b += BS) {
                     if (b < D.bins) {
                         const uint32_t info = sInfo[b];
-                        if (info & BINFO_END) { // merged bins are runs of length one and carry BINFO_END too
+                        // (a screened item: the exact tally holds nothing for a run the screen killed, so `sum + rem * len` would
+                        // call it alive again -- only runs in the candidate units of the screen are asked)
+                        const bool dead_on_plane = screen && !first_eval && !((sCandMap[b >> 9] >> ((b >> 4) & 31u)) & 1u);
+                        if ((info & BINFO_END) && !dead_on_plane) { // merged bins are runs of length one and carry BINFO_END too
                             int bb = (int)b;
                             uint64_t sum = sC[bb];
                             bool alive, cand;
                             if (info & BINFO_MERGED) {
                                 cand = sum + rem >= thr;
-                                alive = cand && sum < thr;
+                                alive = cand && (on_plane || sum < thr);
                             } else {
                                 while (bb > 0 && (sInfo[bb - 1] >> 30) == 0u) sum += sC[--bb];
                                 const uint64_t len = (uint64_t)b - (uint64_t)bb + 1u;
@@ -1486,6 +1609,11 @@ __global__ __launch_bounds__(BS) void k_query_level(const QueryArgs a)
                     __syncthreads();
                 }
                 if (first_eval) { PMARK(3) }                             // 3: which runs can still reach the threshold
+                if (on_plane) {                                          // (a barrier has passed since the last read of the 2-bit sums)
+                    for (uint32_t i = tid; i < stride; i += BS) sC[i] = 0;
+                    rem = n;
+                    __syncthreads();
+                }
                 const uint32_t n_alive = sScal[1];
                 if (n_alive == 0) break;
                 if (n_alive > (uint32_t)Q_MAXU) { // too many survivors (long split runs, tiny thresholds): stay dense
@@ -1629,6 +1757,8 @@ __global__ __launch_bounds__(BS) void k_query_level(const QueryArgs a)
         if (tid == 0 && a.prof)
             for (int i = 0; i < 8; ++i) atomicAdd(&a.prof[8 + i], (unsigned long long)pacc[i]);
     }
+    if constexpr (SCREEN)      // a plane row is plane_stride / stride of a row: the 128-B lines it touches, in the level's row-read unit
+        st_rows += st_plane * (a.plane_stride / 128u) / max((a.ixf[0].stride + 127u) / 128u, 1u);
     if (tid == 0 && st_work) { // one set of statistics atomics per block, not per work item
         atomicAdd(&a.ctr->query_bytes, st_bytes);
         atomicAdd(&a.ctr->touched_bytes, st_touched);
@@ -1636,6 +1766,8 @@ __global__ __launch_bounds__(BS) void k_query_level(const QueryArgs a)
         atomicAdd(&a.ctr->lvl_touched[min(lvl, 7u)], st_touched);
         atomicAdd(&a.ctr->lvl_rows[min(lvl, 7u)], st_rows);
         if (st_sparse) atomicAdd(&a.ctr->lvl_sparse[min(lvl, 7u)], st_sparse);
+        if constexpr (SCREEN)
+            if (st_plane) atomicAdd(&a.ctr->plane_loads, st_plane);
     }
 }
 
@@ -1698,6 +1830,11 @@ void launch_query_level(const QueryArgs &a, int grid, size_t lds_bytes, hipStrea
     }
     if (a.prof) {
         hipLaunchKernelGGL((k_query_level<true, 2, true>), dim3(grid), dim3(BLK), lds_bytes, st, a);
+        return;
+    }
+    if (a.plane && a.level == 0 && !a.q_in && a.parts <= 1u && a.prune && !a.counts_out) {    // the one SCREEN instantiation (api.hip sets a.plane)
+        if (nt) hipLaunchKernelGGL((k_query_level<true, 2, false, BLK, Q_CAP, false, true>), dim3(grid), dim3(BLK), lds_bytes, st, a);
+        else hipLaunchKernelGGL((k_query_level<false, 2, false, BLK, Q_CAP, false, true>), dim3(grid), dim3(BLK), lds_bytes, st, a);
         return;
     }
     if (unroll == 2) {
@@ -2241,6 +2378,36 @@ void launch_scatter_column(uint8_t *data, uint64_t stride, uint64_t bin, const u
     uint64_t grid = (rows + BLK - 1) / BLK;
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(k_scatter_column, dim3((uint32_t)grid), dim3(BLK), 0, st, data, stride, bin, col, rows);
+}
+
+// plane word w of row r from the sixteen fingerprints of bins 16 w .. 16 w + 15 (kernels.h, plane_stride_of); one thread per word
+__global__ __launch_bounds__(BLK) void k_build_plane(const uint8_t *__restrict__ data, uint64_t rows, uint32_t stride,
+                                                     uint32_t *__restrict__ plane, uint32_t pwords)
+{
+    const uint64_t total = rows * pwords;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLK + threadIdx.x; i < total; i += (uint64_t)gridDim.x * BLK) {
+        const uint64_t r = i / pwords;
+        const uint32_t w = (uint32_t)(i - r * pwords);
+        uint32_t out = 0u;
+        if (w * 16u < stride) {         // (stride is a multiple of 64: the sixteen bytes are all inside the row)
+            const uint4 v = *reinterpret_cast<const uint4 *>(data + r * stride + (size_t)w * 16u);
+            const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) out |= ((x[q] >> (8 * b)) & 3u) << (2 * (4 * q + b));
+        }
+        plane[i] = out;
+    }
+}
+
+void launch_build_plane(const uint8_t *data, uint64_t rows, uint32_t stride, uint8_t *plane, uint32_t plane_stride, hipStream_t st)
+{
+    const uint32_t pwords = plane_stride / 4u;
+    const uint64_t total = rows * pwords;
+    if (!total) return;
+    const int grid = (int)std::min<uint64_t>((total + BLK - 1) / BLK, 1u << 16);
+    hipLaunchKernelGGL(k_build_plane, dim3(grid), dim3(BLK), 0, st, data, rows, stride, reinterpret_cast<uint32_t *>(plane), pwords);
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -337,6 +337,17 @@ class GpuIndex:
     def ixf_seed(self, ixf):
         return int(_lib.lib().taxor_gpu_index_ixf_seed(self._h, ixf))
 
+    def root_plane(self):
+        """the root's 2-bit plane as the searches see it (derived now if it is stale) -> uint8[rows, plane_stride], or None when the
+        root has none"""
+        rows, ps = C.c_uint64(), C.c_uint32()
+        check(_lib.lib().taxor_gpu_index_root_plane(self._h, None, 0, C.byref(rows), C.byref(ps)))
+        if not ps.value:
+            return None
+        out = np.empty((int(rows.value), int(ps.value)), dtype=np.uint8)
+        check(_lib.lib().taxor_gpu_index_root_plane(self._h, _p(out), out.size, C.byref(rows), C.byref(ps)))
+        return out
+
     def download_ixf(self, ixf, out=None):
         bins, stride, seg = self.shapes[ixf]
         if out is None:
@@ -351,11 +362,11 @@ class Searcher:
 
     def __init__(self, index: GpuIndex, error_rate=0.04, percentage=-1.0, ratio=None, sub_batch_reads=0,
                  sub_batch_bases=0, time_kernels=False, prune=True, group_always=False, small_path=True, split_always=False,
-                 force_tree_stall=False):
+                 force_tree_stall=False, screen=True):
         self.index = index
         flags = ((0 if prune else _lib.SEARCH_NO_PRUNE) | (_lib.SEARCH_GROUP_ALWAYS if group_always else 0)
                  | (0 if small_path else _lib.SEARCH_NO_SMALL_PATH) | (_lib.SEARCH_SPLIT_ALWAYS if split_always else 0)
-                 | (_lib.SEARCH_FORCE_TREE_STALL if force_tree_stall else 0))
+                 | (_lib.SEARCH_FORCE_TREE_STALL if force_tree_stall else 0) | (0 if screen else _lib.SEARCH_NO_SCREEN))
         prm = _lib.SearchParams(0.0, sub_batch_reads, sub_batch_bases, 1 if time_kernels else 0, _lib.THR_PERCENTAGE, error_rate, flags)
         if ratio is not None:          # explicit (size_t)(n * ratio), whatever the index
             prm.ratio = float(ratio)
