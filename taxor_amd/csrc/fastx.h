@@ -136,17 +136,17 @@ struct Batch {
     std::vector<int64_t> user_bin;
     std::vector<uint32_t> count, n_hashes;
     std::string text;   // the chunk's TSV lines (formatter threads), written by the writer in chunk order
-    // bases.data() as pinned for DMA by the consumer (search_main.cpp); the producer keeps bases from reallocating
+    // bases.data() as pinned for DMA by the consumer (search_cmd.h, pin_bases); the producer keeps bases from reallocating
     void *pinned = nullptr;
     bool may_pin = false;
-    uint64_t pool_bytes = 0;    // what the CLI's buffer pool has on its books for this batch (search_main.cpp, BatchPool)
+    uint64_t pool_bytes = 0;    // what the CLI's buffer pool has on its books for this batch (query_reader.h, BatchPool)
     uint32_t fills = 0;         // how often this buffer has been filled by a parser: it is page-locked when it comes round again
     uint64_t feed_first = 0;    // search-to-profile in one run: the index its first read was given in the profile feed
     // --device-parse: the chunk is a byte range of the file as read (whole records of kind raw_kind, '>' or '@'); the device finds
     // the records, ids and offsets are filled from its table and bases stays empty.  raw_kind 0: a parsed chunk, as above
     BaseBuf raw;
     char raw_kind = 0;
-    void *raw_pinned = nullptr; // raw.data() as page-locked by the range thread that filled it (search_main.cpp); recycled with the chunk
+    void *raw_pinned = nullptr; // raw.data() as page-locked by the range thread that filled it (query_reader.h); recycled with the chunk
     // raw_kind 'B': the chunk comes from a BAM file (bam.h).  raw holds the records' 4-bit SEQ fields back to back, read r being
     // nib_len[r] bases from byte nib_off[r], stored reverse-complemented when nib_rev[r]; ids and offsets (the lengths summed up) are
     // filled by the reader, bases stays empty.  The device unpacks the nibbles (bam_pack.hip)

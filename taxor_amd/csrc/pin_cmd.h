@@ -1,7 +1,7 @@
 // pin_cmd.h -- `taxor pin`: ONE command that turns a published .hixf + a query file + the TSV the reference wrote for them into
 // a committed parity fixture (tests/golden/real_<name>.json), SURVEY.md 8(f) #2.  Included by search_main.cpp inside its
-// anonymous namespace (it uses that file's helpers: die, file_exists, str_split, parse_arith_spec, arith_spec, fnv1a,
-// compare_tsv, variant_family, rank_variants).
+// anonymous namespace, after the headers whose helpers it uses: cli_util.h (die, file_exists, str_split, fnv1a), tools_cmd.h
+// (parse_arith_spec, arith_spec, variant_family, rank_variants) and search_cmd.h (compare_tsv).
 //
 //   taxor pin --index-file X.hixf --query-file R.fq --expect ref.tsv --out tests/golden/real_<name>.json
 //             [--ixf-arithmetic spec] [--ixf-layout spec] [--error-rate e] [--percentage p] [--threads n] [--fixture-reads n] [--gpu id] [--name s]

@@ -204,7 +204,7 @@ bool profile_write_abundances(const std::string &path, const std::map<std::strin
 }
 
 // the value of one of the profile's options into c, with the reference parser's messages (:19-76); false and *err on a value that
-// does not parse or lies outside its range.  `taxor search` takes the same options for its one-run mode (search_main.cpp).
+// does not parse or lies outside its range.  `taxor search` takes the same options for its one-run mode (search_cmd.h).
 bool profile_set_option(const std::string &o, const std::string &v, ProfileConfig &c, std::string &err)
 {
     char *end = nullptr;

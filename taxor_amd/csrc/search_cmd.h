@@ -1,0 +1,1509 @@
+// search_cmd.h -- `taxor search`: options, one index file against its query files (search_files), by one of two routes: the index
+// resident on the devices and the host stages overlapped (search_resident), or an index larger than device memory searched in
+// resident passes (search_paged).  DESIGN.md, "CLI host", names the stages and who owns which shared state.  Included by
+// search_main.cpp inside its anonymous namespace, after query_reader.h, tools_cmd.h and profile_cmd.h.
+
+struct Config : ReaderOptions {              // taxor_search_configuration.hpp:8-20
+    std::string index_file, query_file, report_file;
+    double threshold = -1.0, error_rate = 0.04;
+    std::vector<int> gpus{0};   // devices that classify batches in parallel, each with its own index replica
+    std::string expect_file;    // --expect: a TSV the reference wrote for the same reads and index, compared per read
+    bool sequential = false;    // --sequential: one reader thread per file, no byte-range cutting (any legal FASTA/FASTQ)
+    uint32_t ixf_arith = 0;     // --ixf-arithmetic: the reading of the un-vendored IXF arithmetic the index follows (0 = this library's)
+    bool layout_given = false;  // --ixf-layout: how the file stores each IXF's fingerprints (ixf_layout.h); transposed on the device at load
+    uint32_t ixf_layout = 0;
+    uint64_t group_reads = 0;   // reads per GPU batch, made of queued chunks (0: 131072, or --batch-reads when that is given)
+    uint64_t index_budget_mib = 0;   // hidden --device-index-budget: fingerprint bytes on the device at a time; the index is searched in resident passes
+    bool paged_replay = false;       // hidden --paged-replay: the query file is read in the first resident pass only, the later ones replay the reads' saved hash lists
+    bool paged_reread = false;       // hidden --paged-reread: every resident pass reads the query file again (the default, said aloud; wins over --paged-replay)
+    std::string gather;         // several devices: "rccl" | "host" (taxor_gpu_comm transports) | "none" (independent workers, each
+                                // fetching its own results); empty = rccl when the devices are distinct, host when one repeats
+};
+
+void usage()
+{
+    fprintf(stderr,
+            "taxor search - Queries files of DNA sequences against a list of HIXF index files (MI355X)\n"
+            "  --index-file <f[,f..]>   taxor index file(s) containing HIXF index and reference information (required); syncmer\n"
+            "                           indexes of k-mer size 2..32 and syncmer size 1..31 (below the k-mer size), minimiser indexes\n"
+            "                           of k-mer size 1..32\n"
+            "  --query-file <f[,f..]>   file(s) containing sequences to query against the index: FASTA or FASTQ, plain, .gz or .bz2, or BAM\n"
+            "                           (unaligned or aligned; recognised by content; secondary and supplementary records are left out and\n"
+            "                           reads stored reverse-complemented are restored, as `samtools fastq` does); kinds may be mixed\n"
+            "  --output-file <f>        file name for the resulting output\n"
+            "  --threads <1..32>        host threads parsing the query file (plain FASTA/FASTQ; gzip is one stream) and rendering\n"
+            "                           the report; default 4-16 by the size of the machine (the reference's default of 1 is its\n"
+            "                           classifying thread; here one host thread cannot feed the GPU)\n"
+            "  --percentage <0..1>      if set, this threshold is used instead of the syncmer model\n"
+            "  --error-rate <0..1>      expected error rate of the reads (default 0.04)\n"
+            "  --gpu <id>               device ordinal (default 0)\n"
+            "  --gpus <n>               use devices 0..n-1: the index is replicated, batches of reads are sharded\n"
+            "  --gpu-list <a,b,..>      explicit device list (a device may be listed twice)\n"
+            "  --gather <rccl|host|none> several devices: index broadcast + per-round gather of the results on the first device over\n"
+            "                           RCCL/xGMI (default), the same staged through host memory, or independent workers\n"
+            "  --batch-reads <n>        reads per parsed chunk (default: about 128 MB of query file, 65536 reads for gzip)\n"
+            "  --sequential             read every query file front to back on one thread (FASTQ whose records wrap their lines)\n"
+            "  --device-parse           plain FASTA / four-line FASTQ: the byte ranges go to the device as they are read and the records are\n"
+            "                           found there (the host parses a range only where the device reports it irregular); compressed\n"
+            "                           and --sequential input is parsed on the host as without the switch; a BAM file ignores it (its\n"
+            "                           records are walked on the host and its 4-bit sequences unpacked on the device in any case)\n"
+            "  --group-reads <n>        reads per GPU batch, made of whole chunks (default 131072; --batch-reads if that is given)\n"
+            "  --ixf-arithmetic <spec>  search an index whose fingerprints follow another reading of the IXF arithmetic than this\n"
+            "                           build's (the spec `taxor verify --variants` prints: kh=..,sm=..,rot=..,red=..,fp=..)\n"
+            "  --ixf-layout <spec>      search an index whose fingerprint vectors are laid out otherwise than data[row*stride + bin]\n"
+            "                           (the spec `taxor verify --variants` / `taxor pin` print, e.g. bin-major,unpadded,segment-major);\n"
+            "                           they are transposed on the device while the index is uploaded\n"
+            "  --expect <tsv>           compare the output per read with a TSV the reference wrote for the same input (exit 3 if it differs)\n"
+            "search to profile in one run (the options of `taxor profile`; results go from the device's search buffers into the profile's\n"
+            "device pipeline, no TSV is written or parsed in between):\n"
+            "  --cami-report-file <f>   CAMI profile of genomic abundances      } all three are required as soon as one of the options\n"
+            "  --binning-file <f>       CAMI binning file (read -> taxid)       } of this group is given; --output-file is then optional\n"
+            "  --sample-id <id>         identifier of the sample                } (given, the TSV is written as well)\n"
+            "  --seq-abundance-file <f> sequence abundances in CAMI format (including unclassified reads)\n"
+            "  --min-abundance <0..1>   minimum abundance to report (default 0.001)\n"
+            "  --em-steps <1..1000>     steps of the expectation maximisation (default 100)\n"
+            "                           Limits of this mode: ONE index file and ONE device (--gpus above 1, a --gpu-list of several\n"
+            "                           devices and a comma list of index files are refused), and every read id -- the header up to its\n"
+            "                           first space -- must occur once: `taxor profile` merges the lines of reads that share an id into\n"
+            "                           one read, this mode refuses such input and names the id.\n");
+}
+
+void advanced_help()
+{
+    usage();
+    fprintf(stderr, "advanced:\n"
+                    "  --device-index-budget <MiB> at most this many MiB of the index's fingerprints on the device at a time, in [1,16777216]: the root\n"
+                    "                           IXF stays resident, the subtrees under its merged bins are searched group by group (one pass\n"
+                    "                           over the query file per group, the file is parsed -- a .gz inflated -- once per pass) and every\n"
+                    "                           read's results are merged on the device.  Taken by itself when the index exceeds the device's\n"
+                    "                           free memory.  ONE device, a query file that can be read again (no pipe); the output is\n"
+                    "                           byte-identical to the resident search.  A BAM query file is read once per pass like any other.\n"
+                    "  --paged-replay           with --device-index-budget: read, inflate, pack and hash the query in the first pass only; every\n"
+                    "                           read's hash list is kept in host memory (8 bytes per hash) and the later passes replay the lists\n"
+                    "                           without opening the file.  Same output.  When the lists' bound does not fit the host's available\n"
+                    "                           memory the run reads the file again in every pass instead, and says so.  Not the default: it has\n"
+                    "                           not been measured against re-reading from a file yet (docs/EXPERIMENTS.md).\n"
+                    "  --paged-reread           the default said aloud: read the query file again in every pass; wins over --paged-replay.\n"
+                    "BAM input: the BGZF blocks are inflated on --threads threads, one thread walks the records (block_size, flag, l_seq, read_name)\n"
+                    "                           and copies the 4-bit SEQ fields into a page-locked buffer; CIGAR, QUAL and tags are never read.  A\n"
+                    "                           missing BGZF end-of-file block is a warning; CRAM and SAM text are refused.  With TAXOR_CLI_TRACE the\n"
+                    "                           run reports how many records were skipped as secondary or supplementary.\n");
+}
+
+// seqan3's FASTA/FASTQ readers drop white space and digits inside sequences (numbered or column-formatted files).  The
+// parsers here append sequence lines raw -- a scan per byte would halve their rate for files that never need it -- and
+// the device reports any character outside dna15 (TAXOR_E_ALPHABET); only then is the batch cleaned, in place, and run
+// again.  Returns false if there was nothing to remove (the batch really holds a foreign character).
+bool strip_space_and_digits(Batch &b)
+{
+    char *d = &b.bases[0];
+    size_t w = 0;
+    bool any = false;
+    for (size_t r = 0; r + 1 < b.offsets.size(); ++r) {
+        const size_t lo = b.offsets[r], hi = b.offsets[r + 1];
+        b.offsets[r] = w;
+        for (size_t i = lo; i < hi; ++i) {
+            const unsigned char c = (unsigned char)d[i];
+            if (c == ' ' || (c >= '\t' && c <= '\r') || (c >= '0' && c <= '9')) { any = true; continue; }
+            d[w++] = (char)c;
+        }
+    }
+    b.offsets.back() = w;
+    b.bases.resize(w);          // shrinks: never reallocates, a page-locked buffer stays where it is
+    return any;
+}
+
+// run() classifies `chunks` (anything whose elements point to a Batch); where the device met a character outside dna15, the chunks
+// are cleaned and, if that removed anything, run once more
+template <class Run, class Chunks> int run_with_alphabet_retry(Run &&run, Chunks &chunks)
+{
+    int rc = run();
+    if (rc == TAXOR_E_ALPHABET) {
+        bool any = false;
+        for (auto &bt : chunks) any = strip_space_and_digits(*bt) || any;
+        if (any) rc = run();
+    }
+    return rc;
+}
+
+// `--expect ref.tsv`: compare this run's output with a TSV the reference produced for the same reads and index
+// (the day a published .hixf and its reference output are at hand).  The reference writes the lines
+// of one read together but, with --threads > 1, the reads in no particular order (sync_out.hpp:24-29): reads are
+// matched by id, the lines of a read are compared in order (the HIXF's DFS order).  Returns the number of differing reads.
+uint64_t compare_tsv(const std::string &ours, const std::string &expect)
+{
+    auto load = [](const std::string &path, std::map<std::string, std::vector<std::string>> &by_read, std::vector<std::string> &order) {
+        FILE *f = fopen(path.c_str(), "rb");
+        if (!f) die("cannot open " + path);
+        std::string line;
+        std::vector<char> buf(1 << 20);
+        std::string carry;
+        size_t n;
+        auto take = [&](const std::string &l) {
+            if (l.empty() || l[0] == '#') return;
+            const size_t tab = l.find('\t');
+            const std::string id = l.substr(0, tab);
+            auto it = by_read.find(id);
+            if (it == by_read.end()) { it = by_read.emplace(id, std::vector<std::string>()).first; order.push_back(id); }
+            it->second.push_back(l);
+        };
+        while ((n = fread(buf.data(), 1, buf.size(), f)) > 0) {
+            size_t a = 0;
+            for (size_t i = 0; i < n; ++i)
+                if (buf[i] == '\n') {
+                    carry.append(buf.data() + a, i - a);
+                    if (!carry.empty() && carry.back() == '\r') carry.pop_back();
+                    take(carry);
+                    carry.clear();
+                    a = i + 1;
+                }
+            carry.append(buf.data() + a, n - a);
+        }
+        if (!carry.empty()) take(carry);
+        fclose(f);
+    };
+    std::map<std::string, std::vector<std::string>> a, b;
+    std::vector<std::string> oa, ob;
+    load(ours, a, oa);
+    load(expect, b, ob);
+    uint64_t same = 0, differ = 0, only_ours = 0, only_expect = 0, shown = 0;
+    for (const auto &id : oa) {
+        const auto it = b.find(id);
+        if (it == b.end()) { ++only_ours; continue; }
+        if (it->second == a[id]) { ++same; continue; }
+        ++differ;
+        if (shown++ < 10) {
+            printf("read %s differs:\n", id.c_str());
+            for (const auto &l : a[id]) printf("  ours    %s\n", l.c_str());
+            for (const auto &l : it->second) printf("  expect  %s\n", l.c_str());
+        }
+    }
+    for (const auto &id : ob)
+        if (!a.count(id)) ++only_expect;
+    printf("compared with %s: %llu reads identical, %llu differ, %llu only in this run, %llu only in the expected file\n", expect.c_str(),
+           (unsigned long long)same, (unsigned long long)differ, (unsigned long long)only_ours, (unsigned long long)only_expect);
+    const uint64_t bad = differ + only_ours + only_expect;
+    printf("%s\n", bad == 0 ? "PASS: per-read output identical to the expected TSV"
+                            : "FAIL: output differs from the expected TSV (run `taxor verify` to test the index arithmetic)");
+    return bad;
+}
+
+// ---- search to profile in one run (`taxor search --cami-report-file ... --binning-file ... --sample-id ...`).
+// The GPU workers hand every batch's device-resident results to a profile feed (profile_feed.hip); the host keeps the read ids, cut
+// at the first space (taxor_profile.cpp:124-125), in input order.  At the end: rank the ids byte-wise, finish the feed, run the
+// profile, write the three files through the part `taxor profile` writes them with (profile_write_outputs).
+struct FusedProfile {
+    taxor_gpu_profile_feed *feed = nullptr;
+    const taxor_hixf_meta *meta = nullptr;
+    std::atomic<uint64_t> next_read{0};        // the next batch's first index in the feed
+    double t_feed = 0;                         // seconds inside taxor_gpu_profile_feed_add_batch, summed over workers
+    std::vector<uint32_t> bin_species;         // user bin -> species (the first that names it, species[0] if none: taxor_search.cpp:172-178,289)
+    std::vector<int32_t> ref_of_bin;
+    std::vector<std::string_view> accs;        // distinct accessions of the index in byte-wise order: reference id -> accession
+    std::string id_data;                       // read ids in input order
+    std::vector<uint64_t> id_off{0}, feed_index;   // feed_index[i] = the index input read i has in the feed
+
+    void begin(const taxor_hixf_view *view, const taxor_hixf_meta *m, int device)
+    {
+        meta = m;
+        if (m->n_species == 0) die("the index names no species: nothing to profile against");
+        const uint64_t nb = view->n_user_bins;
+        bin_species.assign(nb, 0u);
+        for (uint64_t i = m->n_species; i-- > 0;)
+            if (m->species[i].user_bin < nb) bin_species[m->species[i].user_bin] = (uint32_t)i;
+        for (uint64_t u = 0; u < nb; ++u) accs.emplace_back(m->species[bin_species[u]].accession_id);
+        std::sort(accs.begin(), accs.end());
+        accs.erase(std::unique(accs.begin(), accs.end()), accs.end());
+        ref_of_bin.resize(nb);
+        std::vector<uint64_t> ref_len_of_bin(nb);
+        for (uint64_t u = 0; u < nb; ++u) {
+            const taxor_species &sp = m->species[bin_species[u]];
+            ref_of_bin[u] = (int32_t)(std::lower_bound(accs.begin(), accs.end(), std::string_view(sp.accession_id)) - accs.begin());
+            ref_len_of_bin[u] = sp.seq_len;
+        }
+        if (taxor_gpu_profile_feed_create(device, nb, ref_of_bin.data(), ref_len_of_bin.data(), accs.size(), &feed) != TAXOR_OK) die(taxor_gpu_last_error());
+    }
+
+    // one chunk, in input order (the sequencer)
+    void take_ids(const Batch &bt)
+    {
+        for (size_t r = 0; r < bt.ids.size(); ++r) {
+            const char *p = bt.ids.ptr(r);
+            size_t n = bt.ids.len(r);
+            if (const void *sp = memchr(p, ' ', n)) n = (size_t)((const char *)sp - p);
+            id_data.append(p, n);
+            id_off.push_back(id_data.size());
+            feed_index.push_back(bt.feed_first + r);
+        }
+    }
+
+    std::string_view id(uint64_t i) const { return std::string_view(id_data.data() + id_off[i], id_off[i + 1] - id_off[i]); }
+
+    // input reads in byte-wise order of their ids (bytes compared as unsigned, like std::string::operator<): ranges sorted on
+    // `threads` threads, then merged pairwise
+    std::vector<uint32_t> sorted_reads(unsigned threads) const
+    {
+        const uint64_t n = feed_index.size();
+        std::vector<uint32_t> order(n);
+        for (uint64_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
+        auto less = [&](uint32_t a, uint32_t b) { const int c = id(a).compare(id(b)); return c != 0 ? c < 0 : a < b; };
+        const uint64_t parts = std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)threads, 16, n / 65536 + 1}));
+        std::vector<uint64_t> cut(parts + 1);
+        for (uint64_t t = 0; t <= parts; ++t) cut[t] = n * t / parts;
+        {
+            std::vector<std::thread> th;
+            for (uint64_t t = 0; t < parts; ++t) th.emplace_back([&, t] { std::sort(order.begin() + (std::ptrdiff_t)cut[t], order.begin() + (std::ptrdiff_t)cut[t + 1], less); });
+            for (auto &x : th) x.join();
+        }
+        for (uint64_t w = 1; w < parts; w *= 2) {
+            std::vector<std::thread> th;
+            for (uint64_t t = 0; t + w < parts; t += 2 * w)
+                th.emplace_back([&, t, w] {
+                    std::inplace_merge(order.begin() + (std::ptrdiff_t)cut[t], order.begin() + (std::ptrdiff_t)cut[t + w],
+                                       order.begin() + (std::ptrdiff_t)cut[std::min(parts, t + 2 * w)], less);
+                });
+            for (auto &x : th) x.join();
+        }
+        return order;
+    }
+
+    void finish(const ProfileConfig &c, unsigned threads, double seconds_search)
+    {
+        const double t0 = now();
+        const uint64_t n = feed_index.size();
+        if (n != next_read.load()) die("internal: the profile feed was given " + std::to_string(next_read.load()) + " reads, the sequencer saw " + std::to_string(n));
+        if (n >= (1ull << 32)) die("more than 2^32 - 1 reads: search to profile in one run numbers reads in 32 bits");
+        const std::vector<uint32_t> order = sorted_reads(threads);
+        for (uint64_t k = 1; k < n; ++k)
+            if (id(order[k - 1]) == id(order[k]))
+                die("read id " + std::string(id(order[k])) + " occurs twice in the query (reads " + std::to_string(order[k - 1] + 1) + " and " + std::to_string(order[k] + 1) +
+                    "); search to profile in one run needs unique read ids -- write a TSV with --output-file alone and run `taxor profile`, which merges such reads");
+        std::vector<uint64_t> rank(n);                      // by feed index
+        for (uint64_t k = 0; k < n; ++k) rank[feed_index[order[k]]] = k;
+        const double t_ranked = now();
+        taxor_gpu_profile *gp = nullptr;
+        if (taxor_gpu_profile_feed_finish(feed, rank.data(), n, &gp) != TAXOR_OK) die(taxor_gpu_last_error());
+        std::vector<uint64_t>().swap(rank);
+        if (taxor_gpu_profile_run(gp, (uint32_t)c.em_steps, 0) != TAXOR_OK) die(taxor_gpu_last_error());
+        taxor_profile_results res{};
+        taxor_profile_csr csr{};
+        const int64_t *match_bin = nullptr;
+        if (taxor_gpu_profile_results(gp, &res) != TAXOR_OK || taxor_gpu_profile_feed_matches(feed, &csr, &match_bin) != TAXOR_OK) die(taxor_gpu_last_error());
+        printf("Number of EM steps needed: %u\n", res.em_steps_needed);
+        fflush(stdout);
+        const double t_device = now();
+        // the taxonomy strings of an accession are those of its first line in the TSV (taxor_profile.cpp:142-146): of the user bin
+        // whose match comes first in input order.  That needs a look at the matches only where user bins of different species
+        // share an accession
+        std::vector<uint32_t> ref_species(accs.size(), ~0u);
+        uint64_t open_refs = 0;
+        {
+            std::vector<uint8_t> shared(accs.size(), 0);
+            for (uint64_t u = 0; u < ref_of_bin.size(); ++u) {
+                uint32_t &sp = ref_species[(uint64_t)ref_of_bin[u]];
+                if (sp == ~0u) sp = bin_species[u];
+                else if (sp != bin_species[u]) shared[(uint64_t)ref_of_bin[u]] = 1;
+            }
+            for (uint8_t x : shared) open_refs += x;
+            if (open_refs) {
+                std::vector<uint32_t> rank_of_input(n);
+                for (uint64_t k = 0; k < n; ++k) rank_of_input[order[k]] = (uint32_t)k;
+                for (uint64_t i = 0; i < n && open_refs; ++i)
+                    for (uint64_t j = csr.read_off[rank_of_input[i]]; j < csr.read_off[rank_of_input[i] + 1] && open_refs; ++j) {
+                        if (match_bin[j] < 0) continue;
+                        const uint64_t x = (uint64_t)ref_of_bin[(uint64_t)match_bin[j]];
+                        if (!shared[x]) continue;
+                        ref_species[x] = bin_species[(uint64_t)match_bin[j]];
+                        shared[x] = 0;
+                        --open_refs;
+                    }
+            }
+        }
+        ProfileNames nm;
+        nm.n_reads = n;
+        nm.n_refs = accs.size();
+        nm.read_off = csr.read_off;
+        nm.read_id = [&](uint64_t r) { return id(order[r]); };
+        nm.accession = [&](uint64_t x) { return accs[x]; };
+        nm.tax_id_str = [&](uint64_t x) { return std::string_view(meta->species[ref_species[x]].taxid_string); };
+        nm.tax_str = [&](uint64_t x) { return std::string_view(meta->species[ref_species[x]].taxnames_string); };
+        nm.match_tax_id = [&](uint64_t i) { return match_bin[i] < 0 ? std::string_view() : std::string_view(meta->species[bin_species[(uint64_t)match_bin[i]]].taxid); };
+        const std::string err = profile_write_outputs(c, res, nm);
+        if (!err.empty()) die(err);
+        const double t_end = now();
+        fprintf(stderr, "taxor search (profile): %llu reads, %llu references, %llu matches, %llu reference pairs, %u EM iterations; seconds: search %.3f "
+                        "(feed %.3f inside), rank %.3f, device %.3f (rounds %.3f, EM %.3f), write %.3f, profile total %.3f\n",
+                (unsigned long long)n, (unsigned long long)accs.size(), (unsigned long long)csr.n_matches, (unsigned long long)res.n_pairs, res.em_iterations,
+                seconds_search, t_feed, t_ranked - t0, t_device - t_ranked, res.seconds_filter, res.seconds_em, t_end - t_device, t_end - t0);
+        taxor_gpu_profile_destroy(gp);
+        taxor_gpu_profile_feed_destroy(feed);
+        feed = nullptr;
+    }
+};
+
+// What outlives one index file: the options, the report, the profile feed, and the totals the run closes with.
+struct SearchRun {
+    Config cfg;
+    ProfileConfig prof;             // search to profile in one run: the options of `taxor profile` (profile_cmd.h)
+    bool profile_mode = false, write_tsv = true;
+    std::string gpus_option;        // --gpus / --gpu-list as given (named when the profile options refuse several devices)
+    FILE *out = nullptr;
+    FusedProfile fused;             // search to profile in one run (profile_mode)
+    double t_index = 0, t_reads = 0, t_compute = 0, t_pin = 0, t_search = 0, t_gather = 0, t_search_wall = 0;
+    uint64_t n_batches = 0, n_gpu_batches = 0;
+    uint64_t total_reads = 0, total_bases = 0;
+    std::mutex stat_mu;             // the GPU workers' sums above
+    void count_chunk(const Batch &bt) { std::lock_guard<std::mutex> lk(stat_mu); ++n_batches; total_reads += bt.ids.size(); total_bases += bt.offsets.back(); }
+};
+
+// The option loop and the checks that need nothing but the options.  False: help or the version was printed, there is nothing to run.
+bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
+{
+    Config &cfg = run.cfg;
+    ProfileConfig &prof = run.prof;
+    for (size_t ai = 0; ai < args.size(); ++ai) {
+        const std::string k = args[ai];
+        auto val = [&]() -> std::string {
+            if (ai + 1 >= args.size()) die("Missing value for option " + k);
+            return args[++ai];
+        };
+        auto num = [&](const std::string &v, bool integer) -> double {   // seqan3 rejects "4x" / "abc" instead of reading a prefix
+            char *end = nullptr;
+            const double d = integer ? (double)strtoll(v.c_str(), &end, 10) : strtod(v.c_str(), &end);
+            if (v.empty() || !end || *end != '\0') die("Value parse failed for " + k + ": Argument " + v + " could not be parsed as type " + (integer ? "unsigned 64 bit integer." : "double."));
+            return d;
+        };
+        if (k == "--index-file") cfg.index_file = val();
+        else if (k == "--query-file") cfg.query_file = val();
+        else if (k == "--output-file") cfg.report_file = val();
+        else if (k == "--threads") {
+            const long t = (long)num(val(), true);
+            if (t < 1 || t > 32) die("Validation failed for option --threads: Value not in range [1,32].");   // :51-55
+            cfg.threads = (unsigned)t;
+        } else if (k == "--percentage") {
+            cfg.threshold = num(val(), false);
+            if (cfg.threshold < 0.0 || cfg.threshold > 1.0) die("Validation failed for option --percentage: Value not in range [0,1]."); // :57-61
+        } else if (k == "--error-rate") {
+            cfg.error_rate = num(val(), false);
+            if (cfg.error_rate < 0.0 || cfg.error_rate > 1.0) die("Validation failed for option --error-rate: Value not in range [0,1]."); // :63-67
+        }
+        // hidden flags of the reference's parser (taxor_search.cpp:68-79): accepted, without effect there as here
+        else if (k == "--output-verbose-statistics" || k == "--debug") continue;
+        else if (k == "--version") { printf("taxor-search version: 0.2.0 (MI355X build)\n"); return false; }               // :34
+        else if (k == "--") break;
+        else if (k == "--gpu") cfg.gpus.assign(1, atoi(val().c_str()));
+        else if (k == "--gpus") {
+            const int n = atoi(val().c_str());
+            if (n < 1 || n > 64) die("Validation failed for option --gpus: Value not in range [1,64].");
+            run.gpus_option = k;
+            cfg.gpus.clear();
+            for (int i = 0; i < n; ++i) cfg.gpus.push_back(i);
+        } else if (k == "--gpu-list") {
+            cfg.gpus.clear();
+            for (const auto &t : str_split(val(), ',')) cfg.gpus.push_back(atoi(t.c_str()));
+            if (cfg.gpus.empty()) die("--gpu-list is empty");
+            run.gpus_option = k;
+        }
+        else if (k == "--cami-report-file" || k == "--binning-file" || k == "--sample-id" || k == "--seq-abundance-file" || k == "--min-abundance" ||
+                 k == "--em-steps") {
+            std::string err;
+            if (!profile_set_option(k, val(), prof, err)) die(err);
+            run.profile_mode = true;
+        }
+        else if (k == "--batch-reads") cfg.batch_reads = strtoull(val().c_str(), nullptr, 10);
+        else if (k == "--device-index-budget") {
+            const long long n = atoll(val().c_str());
+            if (n < 1 || n > (1ll << 24)) die("Validation failed for option --device-index-budget: Value not in range [1,16777216].");
+            cfg.index_budget_mib = (uint64_t)n;
+        }
+        else if (k == "--paged-replay") cfg.paged_replay = true;
+        else if (k == "--paged-reread") cfg.paged_reread = true;
+        else if (k == "--expect") cfg.expect_file = val();
+        else if (k == "--sequential") cfg.sequential = true;
+        else if (k == "--device-parse") cfg.device_parse = true;
+        else if (k == "--group-reads") cfg.group_reads = strtoull(val().c_str(), nullptr, 10);
+        else if (k == "--ixf-arithmetic") {
+            const std::string spec = val();
+            if (!parse_arith_spec(spec, &cfg.ixf_arith)) die("Validation failed for option --ixf-arithmetic: expected kh=<0-3>,sm=<0-3>,rot=<1-63>,red=<0-2>,fp=<0-3> (as printed by `taxor verify --variants`), got " + spec);
+        }
+        else if (k == "--ixf-layout") {
+            const std::string spec = val();
+            if (taxor_ixf_layout_parse(spec.c_str(), &cfg.ixf_layout) != TAXOR_OK) die(std::string("Validation failed for option --ixf-layout: ") + taxor_gpu_last_error());
+            cfg.layout_given = true;
+        }
+        else if (k == "--gather") {
+            cfg.gather = val();
+            if (cfg.gather != "rccl" && cfg.gather != "host" && cfg.gather != "none") die("Validation failed for option --gather: Value not in {rccl, host, none}.");
+        }
+        else if (k == "-hh" || k == "--advanced-help") { advanced_help(); return false; }
+        else if (k == "-h" || k == "--help") { usage(); return false; }
+        else die("Unknown option " + k + ". In case this is meant to be a non-option/argument/parameter, please specify the start of non-options with '--'.");
+    }
+    if (run.profile_mode) {            // like `taxor profile` (profile_cmd.h), and before any HIP call
+        if (!prof.have_report) die("Option --cami-report-file is required but not set.");
+        if (!prof.have_binning) die("Option --binning-file is required but not set.");
+        if (!prof.have_sample) die("Option --sample-id is required but not set.");
+    }
+    if (cfg.index_file.empty()) die("Option --index-file is required but not set.");
+    if (run.profile_mode) {
+        if (cfg.index_file.find(',') != std::string::npos)
+            die("Validation failed for option --index-file: the profile options (--cami-report-file, --binning-file, --sample-id) take ONE index file; "
+                "search the indexes one by one, or write a TSV per index and run `taxor profile`.");
+        if (cfg.gpus.size() > 1)
+            die("Validation failed for option " + run.gpus_option + ": the profile options (--cami-report-file, --binning-file, --sample-id) run on ONE device; "
+                "give --gpu <id>.");
+        if (!cfg.gather.empty() && cfg.gather != "none")
+            die("Validation failed for option --gather: the profile options run on ONE device, where nothing is gathered; leave --gather out.");
+        if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
+        prof.device = cfg.gpus[0];
+    }
+    run.write_tsv = !run.profile_mode || !cfg.report_file.empty();
+    if (cfg.threads == 0) {
+        // --threads not given.  The reference's default is one worker thread (taxor_search_configuration.hpp:17) -- there the
+        // thread that classifies; here host threads only parse the query file and render text for the GPU, and one of them
+        // delivers 1-3 Gbp/s to a device that classifies 25.  Default: a sixteenth of the machine, between 4 and 16 -- or what the
+        // container's CPU quota allows, if it has one (threads beyond it only make the cgroup stop all of them for the rest of each
+        // scheduler period).  A --threads the user gives is obeyed as it is.
+        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+        const double quota = cpu_quota();
+        cfg.threads = quota >= 1.0 ? std::min(16u, std::max(2u, (unsigned)quota)) : std::min(16u, std::max(4u, hw / 16u));
+    }
+    return true;
+}
+
+// ---- sanity checks (taxor_search.cpp:97-151): every file is there, the indexes agree, no query is CRAM or SAM -- before any HIP call
+void check_search_inputs(const Config &cfg, const std::vector<std::string> &index_files, const std::vector<std::string> &query_files)
+{
+    printf("checking input ... ");
+    fflush(stdout);
+    for (const auto &f : index_files)
+        if (!file_exists(f)) die("Please check the given index file(s). \nThe following index file does not exist: " + f);
+    if (index_files.size() > 1) {
+        uint8_t k0 = 1, s0 = 0, t0 = 0, syn0 = 0;
+        uint64_t w0 = 0;
+        uint16_t sc0 = 0;
+        for (const auto &f : index_files) {
+            taxor_hixf *h = nullptr;
+            if (taxor_hixf_load(f.c_str(), &h) != TAXOR_OK) die(taxor_gpu_last_error());
+            const taxor_hixf_view *v = taxor_hixf_get_view(h);
+            const taxor_hixf_meta *m = taxor_hixf_get_meta(h);
+            if (k0 == 1) { k0 = v->kmer_size; s0 = v->syncmer_size; t0 = v->t_syncmer; syn0 = v->use_syncmer; w0 = m->window_size; sc0 = v->scaling; }
+            else if (k0 != v->kmer_size || s0 != v->syncmer_size || t0 != v->t_syncmer || syn0 != v->use_syncmer || w0 != m->window_size || sc0 != v->scaling)
+                die("At least two index files have been created with different kmer selection schemes.\n Please provide only index files using the same kmer-/syncmer-/window-size!");
+            taxor_hixf_free(h);
+        }
+    }
+    for (const auto &f : query_files)
+        if (!file_exists(f)) die("Please check the given input query files. \nThe following query file does not exist: " + f);
+    for (const auto &f : query_files) {           // CRAM and SAM text are refused by name, before any HIP call
+        try { (void)bam::sniff(f); } catch (const std::exception &e) { die(e.what()); }
+    }
+    if (!cfg.expect_file.empty() && !file_exists(cfg.expect_file)) die("The expected-output file does not exist: " + cfg.expect_file);
+    printf("done!\n");
+    trace("input checked");
+}
+
+// ---- what both routes do with a chunk ----------------------------------------------------------------------------------------
+
+// a BAM chunk as the device takes it: ids and lengths are the reader's, the device unpacks the 4-bit sequences
+taxor_nibble_segment nibble_segment(const Batch &bt)
+{
+    return taxor_nibble_segment{(const uint8_t *)bt.raw.data(), bt.nib_off.data(), bt.nib_len.data(), bt.nib_rev.data(), bt.ids.size()};
+}
+
+// TSV text of `n` reads into `text`, grown where it is too small; returns the text's length
+uint64_t format_reads(const taxor_hixf *h, uint64_t n, const char *const *idp, const uint64_t *idl, const uint64_t *rl, const uint32_t *n_hashes,
+                      const uint64_t *read_off, const int64_t *user_bin, const uint32_t *count, std::vector<char> &text)
+{
+    uint64_t need = taxor_format_reads(h, n, idp, idl, rl, n_hashes, read_off, user_bin, count, text.data(), text.size());
+    if (need > text.size()) {
+        text.resize(need + need / 8 + 4096);
+        need = taxor_format_reads(h, n, idp, idl, rl, n_hashes, read_off, user_bin, count, text.data(), text.size());
+    }
+    return need;
+}
+
+// a file's size as the text it can hold: a compressed byte at four.  `bam_too`: the bound on bases counts .bam (4-bit sequences,
+// deflated) as packed and wants a name longer than the suffix; the bound on reads does not, and wants one longer than 3
+uint64_t unpacked_bound(const std::string &q, uint64_t size, bool bam_too)
+{
+    auto ends = [&](const char *e) { const size_t m = strlen(e); return q.size() > (bam_too ? m : 3) && q.size() >= m && q.compare(q.size() - m, m, e) == 0; };
+    return size * (ends(".gz") || ends(".bz2") || (bam_too && ends(".bam")) ? 4 : 1);
+}
+
+// ---- an index that does not fit the device (or --device-index-budget): searched in resident passes (DESIGN.md section 9,
+// "Search beyond device memory").  The outer loop runs over the passes, the inner one over the query file, cut into the SAME
+// batches in every pass (the sequential reader cuts at exactly --batch-reads records); a pass's CSR is kept per batch in host
+// memory with its DFS keys, the last pass merges them on the device and writes / feeds the profile as the resident route does.
+//
+// The query is read, inflated, packed and hashed in pass 0 only: with capture on, every batch leaves its reads' hash lists
+// in host memory (taxor_gpu_search_take_saved), kept here with the batch's ids and read offsets, and passes 1 .. n-1 replay
+// the kept batches (taxor_gpu_search_saved_begin) without opening the file.  The lists' store is metered like the results':
+// a bound from the file sizes up front (8 B per hash at the densest selection the index's k, s, t admit), MemAvailable
+// while it grows.  This is the route of --paged-replay; without it, and where the store does not fit, the run re-reads the file in
+// every pass.  Either way one line on stderr says what was done with the query.
+struct PagedPass {
+    SearchRun &run;
+    taxor_hixf *h;
+    taxor_gpu_searcher *s;
+    uint32_t passes;
+    struct Saved { std::vector<uint64_t> ro; std::vector<int64_t> ub; std::vector<uint32_t> cnt, key; };
+    std::vector<std::vector<Saved>> store;          // [batch][pass]
+    uint64_t stored = 0;
+    struct Kept { taxor_gpu_saved *lists = nullptr; fastx::IdList ids; std::vector<uint64_t> offsets; };
+    std::vector<Kept> kept;
+    uint64_t kept_bytes = 0, lists_bytes = 0;      // everything kept per batch / of it: the saved hash lists
+    bool replay = false;
+    bool last_pass = false, capturing = false;     // of the pass that is running
+    size_t bi = 0;                                  // the batch's number in its pass
+    std::vector<const char *> idp;
+    std::vector<uint64_t> idl, rl;
+    std::vector<char> text;
+    std::vector<taxor_gpu_prior> pri;
+    PagedPass(SearchRun &run_, taxor_hixf *h_, taxor_gpu_searcher *s_, uint32_t passes_) : run(run_), h(h_), s(s_), passes(passes_) {}
+
+    void drop_kept()
+    {
+        for (Kept &k : kept) taxor_gpu_saved_free(k.lists);
+        std::vector<Kept>().swap(kept);
+        kept_bytes = 0;
+    }
+    // pass 0 only: the store is given up -- what it held goes, pass 0's results stay, the file is read again from pass 1 on
+    void give_up_replay(const std::string &why_not)
+    {
+        fprintf(stderr, "taxor search: the query is read again in every pass (%s)\n", why_not.c_str());
+        drop_kept();
+        replay = false;
+        if (taxor_gpu_search_capture(s, 0) != TAXOR_OK) die(taxor_gpu_last_error());
+    }
+    // pass 0 with capture on: the batch's hash lists, ids and offsets are kept for the later passes
+    void keep_lists(const Batch &bt)
+    {
+        taxor_gpu_saved *sv = nullptr;
+        if (taxor_gpu_search_take_saved(s, &sv) != TAXOR_OK) die(taxor_gpu_last_error());
+        const uint64_t need = taxor_gpu_saved_bytes(sv) + bt.ids.data.size() + (bt.ids.off.size() + bt.offsets.size()) * 8;
+        const uint64_t avail = taxor::host_memory_available();
+        if (avail && avail < (1ull << 29)) {
+            // the lists are in memory already, so what is left is the figure: below half a gibibyte -- twice what the
+            // results' store below asks for, so that the lists go before the results' check can end the run
+            taxor_gpu_saved_free(sv);
+            give_up_replay("the reads' saved hash lists no longer fit host memory: " + std::to_string(kept_bytes + need) + " bytes kept so far, MemAvailable is " +
+                           std::to_string(avail) + " bytes");
+            return;
+        }
+        kept.emplace_back();
+        kept.back().lists = sv;
+        kept.back().ids = bt.ids;
+        kept.back().offsets = bt.offsets;
+        kept_bytes += need;
+        lists_bytes += taxor_gpu_saved_bytes(sv);
+    }
+    // every pass but the last: the batch's CSR and DFS keys go to host memory
+    void save_results(uint64_t n, const taxor_gpu_results &res)
+    {
+        const uint32_t *key = nullptr;
+        if (taxor_gpu_results_keys(s, &key) != TAXOR_OK) die(taxor_gpu_last_error());
+        const uint64_t need = (n + 1) * 8 + res.n_tuples * 16;
+        uint64_t avail = taxor::host_memory_available();
+        if (avail && need + (1ull << 28) > avail && capturing && replay) {      // the saved lists go first: the run does not end on their account
+            give_up_replay("the passes' results need the memory the reads' saved hash lists hold: " + std::to_string(kept_bytes) + " bytes of lists dropped, MemAvailable was " +
+                           std::to_string(avail) + " bytes");
+            avail = taxor::host_memory_available();
+        }
+        if (avail && need + (1ull << 28) > avail)
+            die("the passes' results no longer fit host memory: " + std::to_string(stored + need) + " bytes kept so far, MemAvailable is " + std::to_string(avail) + " bytes.");
+        stored += need;
+        Saved sv;
+        sv.ro.assign(res.read_off, res.read_off + n + 1);
+        sv.ub.assign(res.user_bin, res.user_bin + res.n_tuples);
+        sv.cnt.assign(res.count, res.count + res.n_tuples);
+        sv.key.assign(key, key + res.n_tuples);
+        store[bi].push_back(std::move(sv));
+    }
+    // the last pass: the earlier passes' results are merged in on the device; then the profile feed and the TSV, like the resident route
+    void merge_and_report(Batch &bt, taxor_gpu_results &res)
+    {
+        const uint64_t n = bt.ids.size();
+        if (store[bi].size() != passes - 1) die("internal: the query file was cut into other batches than in the pass before");
+        pri.clear();
+        for (const Saved &sv : store[bi]) {
+            if (sv.ro.size() != n + 1) die("internal: the query file was cut into other batches than in the pass before");
+            pri.push_back(taxor_gpu_prior{n, (uint64_t)sv.ub.size(), sv.ro.data(), sv.ub.data(), sv.cnt.data(), sv.key.data()});
+        }
+        if (taxor_gpu_search_merge_prior(s, pri.data(), (uint32_t)pri.size()) != TAXOR_OK) die(taxor_gpu_last_error());
+        std::vector<Saved>().swap(store[bi]);
+        if (run.profile_mode) {
+            bt.feed_first = run.fused.next_read.fetch_add(n);
+            run.fused.take_ids(bt);
+            const double f0 = now();
+            if (taxor_gpu_profile_feed_add_batch(run.fused.feed, s, bt.feed_first, 0) != TAXOR_OK) die(taxor_gpu_last_error());
+            run.fused.t_feed += now() - f0;
+        }
+        if (run.write_tsv) {
+            if (taxor_gpu_batch_fetch(s, &res) != TAXOR_OK) die(taxor_gpu_last_error());
+            idp.resize(n); idl.resize(n); rl.resize(n);
+            for (uint64_t r = 0; r < n; ++r) { idp[r] = bt.ids.ptr(r); idl[r] = bt.ids.len(r); rl[r] = bt.offsets[r + 1] - bt.offsets[r]; }
+            const uint64_t need = format_reads(h, n, idp.data(), idl.data(), rl.data(), res.n_hashes, res.read_off, res.user_bin, res.count, text);
+            if (need && fwrite(text.data(), 1, need, run.out) != need) die("cannot write to " + run.cfg.report_file + ": " + strerror(errno));
+        }
+        run.count_chunk(bt);
+        ++run.n_gpu_batches;
+    }
+    // one batch of one pass: from its bases (lists == nullptr) or from its saved hash lists
+    void process(Batch &bt, const taxor_gpu_saved *lists)
+    {
+        const uint64_t n = bt.ids.size();
+        const double t1 = now();
+        taxor_gpu_results res{};
+        const bool nibbles = bt.raw_kind == 'B';      // a BAM chunk: its 4-bit sequences are unpacked on the device
+        bt.raw_kind = 0;
+        auto once = [&]() -> int {
+            if (lists) {
+                const int rb = taxor_gpu_search_saved_begin(s, lists);
+                return rb != TAXOR_OK ? rb : taxor_gpu_search_batch_end(s, &res);
+            }
+            if (!nibbles) return taxor_gpu_search_batch(s, bt.bases.data(), bt.offsets.data(), n, &res);
+            const taxor_nibble_segment seg = nibble_segment(bt);
+            const int rb = taxor_gpu_search_nibbles_begin(s, &seg, 1);
+            return rb != TAXOR_OK ? rb : taxor_gpu_search_batch_end(s, &res);
+        };
+        Batch *const text_chunk[] = {&bt};
+        int rc = nibbles ? once() : run_with_alphabet_retry(once, text_chunk);
+        if (rc == TAXOR_E_NOMEM && capturing && replay) {      // (a kernel that commits every mapping in full refuses the lists' reservation)
+            give_up_replay("a batch's hash lists found no room: " + std::string(taxor_gpu_last_error()));
+            rc = once();
+        }
+        if (rc != TAXOR_OK) die(taxor_gpu_last_error());
+        if (capturing && replay) keep_lists(bt);          // (replay goes off when the store stops fitting: the rest of pass 0 keeps nothing)
+        if (store.size() <= bi) store.resize(bi + 1);
+        if (!last_pass) save_results(n, res);
+        else merge_and_report(bt, res);
+        ++bi;
+        run.t_compute += now() - t1;
+        run.t_search += now() - t1;
+    }
+};
+
+void search_paged(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view, const taxor_gpu_search_params &prm, const std::vector<std::string> &queries,
+                  uint64_t budget, const char *why, double t0)
+{
+    const Config &cfg = run.cfg;
+    if (cfg.gpus.size() > 1) die("paging an index through device memory (" + std::string(why) + ") runs on ONE device; give --gpu <id> instead of " + run.gpus_option + ".");
+    uint64_t query_bytes = 0;
+    for (const auto &q : queries) {
+        struct stat sb;
+        if (stat(q.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode))
+            die("paging an index through device memory (" + std::string(why) + ") reads the query once per pass: " + q + " is not a regular file and cannot be read again "
+                "(a pipe, standard input); write it to a file first.");
+        query_bytes += unpacked_bound(q, (uint64_t)sb.st_size, false);
+    }
+    taxor_gpu_index *idx = nullptr;
+    if (taxor_gpu_index_create_paged(view, cfg.gpus[0], budget, &idx) != TAXOR_OK) die(taxor_gpu_last_error());
+    const uint32_t passes = taxor_gpu_index_passes(idx);
+    fprintf(stderr, "taxor search: the index is searched in %u resident pass%s over the query (%s)\n", passes, passes == 1 ? "" : "es", why);
+    // host memory for the earlier passes' results: per pass 8 B per read (offsets) and 16 B per tuple (user bin, count, key).
+    // Bound: reads at one per 200 bytes of (inflated: x 4) query file, tuples at the 12 per read the library sizes a batch for
+    {
+        const uint64_t bound = (uint64_t)(passes - 1) * (query_bytes / 200 + 1) * (8 + 16 * 12), avail = taxor::host_memory_available();
+        if (passes > 1 && avail && bound > avail)
+            die("the results of " + std::to_string(passes - 1) + " passes are kept in host memory until the last one merges them: up to " + std::to_string(bound) +
+                " bytes (8 per read and 16 per tuple and pass), MemAvailable is " + std::to_string(avail) + " bytes.");
+    }
+    taxor_gpu_searcher *s = nullptr;
+    if (taxor_gpu_searcher_create(idx, &prm, &s) != TAXOR_OK) die(taxor_gpu_last_error());
+    if (run.profile_mode) run.fused.begin(view, taxor_hixf_get_meta(h), run.prof.device);
+    run.t_index += now() - t0;
+    Config seq_cfg = cfg;
+    if (!seq_cfg.batch_reads) seq_cfg.batch_reads = 131072;
+    BatchPool pool;
+    PagedPass pp(run, h, s, passes);
+    pp.replay = passes > 1 && cfg.paged_replay && !cfg.paged_reread;
+    std::string reread_why = cfg.paged_reread ? "--paged-reread" : "the default; --paged-replay keeps the reads' hash lists in host memory instead";
+    if (pp.replay) {
+        uint64_t bases = 0;         // what the files can hold: a compressed byte at four bases (BAM: 4-bit sequences, deflated)
+        for (const auto &q : queries) {
+            struct stat sb;
+            if (stat(q.c_str(), &sb) == 0) bases += unpacked_bound(q, (uint64_t)sb.st_size, true);
+        }
+        const uint64_t bound = taxor_saved_bytes_bound(bases, view->use_syncmer, view->kmer_size, view->syncmer_size, view->t_syncmer);
+        const uint64_t avail = taxor::host_memory_available();
+        if (!taxor_saved_store_fits(bound, avail)) {
+            pp.replay = false;
+            reread_why = "the reads' saved hash lists may need " + std::to_string(bound) + " bytes of host memory, MemAvailable is " + std::to_string(avail) + " bytes";
+        }
+    }
+    if (passes > 1 && !pp.replay) fprintf(stderr, "taxor search: the query is read again in every pass (%s)\n", reread_why.c_str());
+    const double t_search0 = now();
+    for (uint32_t p = 0; p < passes; ++p) {
+        const double tl = now();
+        if (taxor_gpu_index_load_pass(idx, view, p) != TAXOR_OK) die(taxor_gpu_last_error());
+        run.t_index += now() - tl;
+        pp.last_pass = p + 1 == passes;
+        pp.capturing = pp.replay && p == 0;
+        if (taxor_gpu_search_capture(s, pp.capturing ? 1 : 0) != TAXOR_OK) die(taxor_gpu_last_error());
+        pp.bi = 0;
+        if (p == 0 || !pp.replay) {
+            for (size_t f = 0; f < queries.size(); ++f)
+                run.t_reads += produce_batches(queries[f], seq_cfg, false, pool, [&](std::unique_ptr<Batch> b) {
+                    if (b->end_of_file) return;
+                    pp.process(*b, nullptr);
+                    pool.put(std::move(b));
+                }, (uint32_t)f, 1);
+        } else {
+            Batch bt;           // carries a kept batch's ids and offsets: what the last pass formats and feeds the profile with
+            for (PagedPass::Kept &k : pp.kept) {
+                bt.ids = std::move(k.ids);
+                bt.offsets = std::move(k.offsets);
+                pp.process(bt, k.lists);
+                if (pp.last_pass) {
+                    taxor_gpu_saved_free(k.lists);
+                    k.lists = nullptr;
+                } else {
+                    k.ids = std::move(bt.ids);
+                    k.offsets = std::move(bt.offsets);
+                }
+            }
+        }
+        if (p == 0 && pp.replay)
+            fprintf(stderr, "taxor search: passes 1 to %u replay %llu batch%s from %llu bytes of saved hash lists (the query file is read once)\n", passes - 1,
+                    (unsigned long long)pp.kept.size(), pp.kept.size() == 1 ? "" : "es", (unsigned long long)pp.lists_bytes);
+    }
+    pp.drop_kept();
+    run.t_search_wall += now() - t_search0;
+    if (tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] paged search: %u passes, %.3f s waiting for uploads, %.2f GB of earlier passes' results held at most\n", passes,
+                taxor_gpu_index_upload_wait_seconds(idx), pp.stored / 1e9);
+    taxor_gpu_searcher_destroy(s);
+    taxor_gpu_index_destroy(idx);
+    if (run.profile_mode) run.fused.finish(run.prof, cfg.threads, run.t_search_wall);
+    taxor_hixf_free(h);
+}
+
+// ---- the resident route: readers -> pinners -> GPU workers -> sequencer -> piece threads, overlapped ("CLI host":
+// the stages, the queues between them, and who owns which shared state)
+
+// a file that is not being written yet may run at most two chunks ahead, so that the file whose turn it is can
+// always get buffers
+struct FileTurns {
+    std::mutex fmu;
+    std::condition_variable fcv;
+    size_t current_file = 0;
+    std::vector<int> ahead;
+    void gate(size_t f)             // a reader of file f, before it takes a buffer
+    {
+        std::unique_lock<std::mutex> lk(fmu);
+        fcv.wait(lk, [&] { return f == current_file || ahead[f] < 2; });
+    }
+    void chunk_parsed(size_t f) { std::lock_guard<std::mutex> lk(fmu); ++ahead[f]; }
+    void chunk_written(size_t f) { std::lock_guard<std::mutex> lk(fmu); --ahead[f]; fcv.notify_all(); }
+    void turn_of(size_t f) { std::lock_guard<std::mutex> lk(fmu); current_file = f; fcv.notify_all(); }   // every chunk of the files before f is on its way to the report
+};
+
+// what connects the stages: parsers -> q_parsed -> pinners -> q_in -> GPU workers -> q_fmt -> sequencer; the pool every chunk
+// comes from and goes back to (it, not a queue's depth, bounds how far the parsers run ahead)
+struct Pipes {
+    BoundedQueue<std::unique_ptr<Batch>> q_parsed{4096}, q_in{4096}, q_fmt{8};
+    BatchPool pool;
+    FileTurns turns;
+};
+
+// Chunk buffers stay pageable ("CLI host", has the measurements); TAXOR_CLI_PIN_AFTER=n (under TAXOR_TUNING) registers
+// a buffer at its n-th fill, on the pinner stage (and, for a chunk that got past it, in the worker).
+void pin_bases(Batch &bt)       // recycled with the chunk: pinned once, DMA source from then on
+{
+    static const uint32_t pin_after = [] { const char *e = tune_env("TAXOR_CLI_PIN_AFTER"); const int v = e ? atoi(e) : 0; return v >= 1 ? (uint32_t)v : ~0u; }();
+    if (bt.may_pin && !bt.pinned && bt.fills >= pin_after && bt.bases.capacity() >= (1u << 20) &&
+        taxor_gpu_host_register(&bt.bases[0], bt.bases.capacity()) == TAXOR_OK)
+        bt.pinned = &bt.bases[0];
+}
+
+// the reader threads (each takes the next query file), the pinners behind them, and the thread that closes the queues after them
+struct QueryFeed {
+    const Config &cfg;
+    const std::vector<std::string> &queries;
+    Pipes &p;
+    unsigned readers, parse_threads;
+    std::atomic<size_t> next_file{0};
+    std::vector<double> reader_time;
+    std::vector<std::thread> reader_threads, pinners;
+    std::thread closer;
+    QueryFeed(const Config &c, const std::vector<std::string> &q, Pipes &p_, unsigned r, unsigned pt) : cfg(c), queries(q), p(p_), readers(r), parse_threads(pt) {}
+
+    void read_files(unsigned rt)
+    {
+        for (;;) {
+            const size_t f = next_file.fetch_add(1);
+            if (f >= queries.size()) break;
+            reader_time[rt] += produce_batches(queries[f], cfg, !cfg.sequential, p.pool, [this, f](std::unique_ptr<Batch> b) {
+                if (!b->end_of_file) p.turns.chunk_parsed(f);
+                p.q_parsed.push(std::move(b));
+            }, (uint32_t)f, parse_threads, [this, f] { p.turns.gate(f); });
+        }
+    }
+    void pin_chunks()
+    {
+        std::unique_ptr<Batch> b;
+        while (p.q_parsed.pop(b)) {
+            if (!b->end_of_file) pin_bases(*b);
+            // a BAM chunk's SEQ bytes go to the device as they are: page-locked here, beside the walker, once per buffer
+            if (!b->end_of_file && b->raw_kind == 'B' && !b->raw_pinned && b->raw.capacity() >= (1u << 20) &&
+                taxor_gpu_host_register(b->raw.data(), b->raw.capacity()) == TAXOR_OK)
+                b->raw_pinned = b->raw.data();
+            p.q_in.push(std::move(b));
+        }
+    }
+    void start()
+    {
+        reader_time.assign(readers, 0.0);
+        for (unsigned rt = 0; rt < readers; ++rt) reader_threads.emplace_back([this, rt] { read_files(rt); });
+        static const int n_pinners = [] { const char *e = tune_env("TAXOR_CLI_PINNERS"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 32 ? v : 2; }();
+        for (int pt = 0; pt < n_pinners; ++pt) pinners.emplace_back([this] { pin_chunks(); });
+        closer = std::thread([this] {
+            for (auto &t : reader_threads) t.join();
+            p.q_parsed.close();
+            for (auto &t : pinners) t.join();
+            p.q_in.close();
+            trace("readers done");
+        });
+    }
+};
+
+// ---- TSV text and the report file.  The report is ONE file and the kernel serialises a file's buffered writes, so there is one
+// stream of write() calls whatever the threads.  The text is made in PIECES of about a megabyte, each written by the thread that
+// formatted it while it is still in that core's cache ("CLI host": the measurements, and what else was tried):
+//   sequencer       : chunks (GPU workers, any order) -> file and chunk order -> pieces (ranges of a chunk's reads), numbered
+//   piece threads   : tuples -> 0.8*max filter -> TSV text of the piece (:266-306) -> wait for the piece's turn -> write()
+struct ReportWriter {
+    SearchRun &run;
+    const taxor_hixf *h;
+    Pipes &p;
+    unsigned formatters;
+    struct Hold { std::unique_ptr<Batch> b; std::atomic<uint32_t> left{0}; };
+    struct Piece { Hold *h = nullptr; uint32_t r0 = 0, r1 = 0; uint64_t ticket = 0; };
+    BoundedQueue<Piece> q_piece;
+    int out_fd = -1;
+    std::atomic<uint64_t> out_written{0};
+    double t_write = 0;            // seconds inside write()
+    std::mutex turn_mu;
+    std::condition_variable turn_cv[64];            // a waiting piece thread sleeps on the one of its ticket: passing the turn wakes one thread
+    uint64_t next_ticket = 0;
+    std::atomic<uint64_t> turn_now{0};              // next_ticket, readable without the lock: the thread whose turn is next spins on it
+    double t_first_write = 0, t_last_write = 0;
+    std::atomic<uint64_t> line_bytes_guess{192};   // bytes of text per tuple, learnt from the pieces formatted so far
+    std::thread sequencer;
+    std::vector<std::thread> fmt_threads;
+
+    ReportWriter(SearchRun &run_, const taxor_hixf *h_, Pipes &p_, unsigned formatters_) : run(run_), h(h_), p(p_), formatters(formatters_), q_piece(4 * formatters_ + 16) {}
+    const uint64_t piece_bytes = [] { static const uint64_t v = [] { const char *e = tune_env("TAXOR_CLI_PIECE_KB"); const int v = e ? atoi(e) : 0; return (uint64_t)(v >= 16 ? v : 1024) << 10; }(); return v; }();
+    void chunk_done(Hold *hd)
+    {
+        p.turns.chunk_written(hd->b->file);
+        p.pool.put(std::move(hd->b));
+        delete hd;
+    }
+    void sequence()
+    {
+        std::unique_ptr<Batch> b;
+        std::map<std::pair<uint32_t, uint64_t>, std::unique_ptr<Batch>> pending; // chunks that arrived ahead of their turn
+        uint32_t cur_file = 0;
+        uint64_t next_seq = 0, ticket = 0;
+        while (p.q_fmt.pop(b)) {
+            const auto key = std::make_pair(b->file, b->seq);
+            pending.emplace(key, std::move(b));
+            while (!pending.empty() && pending.begin()->first == std::make_pair(cur_file, next_seq)) {
+                std::unique_ptr<Batch> cur = std::move(pending.begin()->second);
+                pending.erase(pending.begin());
+                if (cur->end_of_file) {                 // every chunk of this file is on its way: the next file's turn
+                    next_seq = 0;
+                    p.turns.turn_of(++cur_file);
+                    continue;
+                }
+                ++next_seq;
+                Hold *hd = new Hold;
+                hd->b = std::move(cur);
+                const Batch &bt = *hd->b;
+                const size_t n = bt.ids.size();
+                if (run.profile_mode) run.fused.take_ids(bt);            // chunks pass here in input order
+                if (n == 0 || !run.write_tsv) { chunk_done(hd); continue; }
+                // cut where the estimated text passes piece_bytes
+                const uint64_t per_tuple = line_bytes_guess.load();
+                std::vector<uint32_t> cuts{0};
+                uint64_t est = 0;
+                for (size_t r = 0; r < n; ++r) {
+                    est += (bt.read_off[r + 1] - bt.read_off[r]) * per_tuple + bt.ids.len(r) + 32;
+                    if (est >= piece_bytes && r + 1 < n) { cuts.push_back((uint32_t)(r + 1)); est = 0; }
+                }
+                cuts.push_back((uint32_t)n);
+                hd->left = (uint32_t)(cuts.size() - 1);
+                for (size_t c = 0; c + 1 < cuts.size(); ++c) q_piece.push(Piece{hd, cuts[c], cuts[c + 1], ticket++});
+            }
+        }
+        q_piece.close();
+    }
+    // a piece's text goes to the file when its ticket comes up
+    void write_in_turn(const Piece &pc, const char *text, uint64_t need)
+    {
+        static const bool turn_spin = [] { const char *e = tune_env("TAXOR_CLI_TURN_SPIN"); return e ? atoi(e) != 0 : true; }();
+        // (the thread that is next in line does not go to sleep for the ~0.1 ms its predecessor writes: a wake-up costs
+        // 10-20 us of every 120)
+        if (turn_spin && pc.ticket - turn_now.load(std::memory_order_acquire) == 1)
+            for (int spin = 0; spin < 20000 && turn_now.load(std::memory_order_acquire) != pc.ticket; ++spin) _mm_pause();
+        std::unique_lock<std::mutex> lk(turn_mu);
+        turn_cv[pc.ticket % 64].wait(lk, [&] { return next_ticket == pc.ticket; });
+        const double w0 = now();
+        if (t_first_write == 0) t_first_write = w0;
+        for (uint64_t done = 0; done < need;) {
+            const ssize_t w = ::write(out_fd, text + done, need - done);
+            if (w < 0 && errno == EINTR) continue;            // a signal (SIGSTOP / SIGCONT, a debugger) is not an I/O error
+            if (w <= 0) die("cannot write to " + run.cfg.report_file + ": " + (w < 0 ? strerror(errno) : "write() returned 0"));
+            done += (uint64_t)w;
+        }
+        t_last_write = now();
+        t_write += t_last_write - w0;
+        ++next_ticket;
+        turn_now.store(next_ticket, std::memory_order_release);
+        turn_cv[next_ticket % 64].notify_all();
+    }
+    void format_pieces()
+    {
+        Piece pc;
+        std::vector<const char *> idp;
+        std::vector<uint64_t> idl, rl;
+        std::vector<char> text(piece_bytes + piece_bytes / 2);
+        while (q_piece.pop(pc)) {
+            const Batch &bt = *pc.h->b;
+            const size_t n = pc.r1 - pc.r0;
+            idp.resize(n); idl.resize(n); rl.resize(n);
+            for (size_t r = 0; r < n; ++r) {
+                idp[r] = bt.ids.ptr(pc.r0 + r);
+                idl[r] = bt.ids.len(pc.r0 + r);
+                rl[r] = bt.offsets[pc.r0 + r + 1] - bt.offsets[pc.r0 + r];
+            }
+            const uint64_t need = format_reads(h, n, idp.data(), idl.data(), rl.data(), bt.n_hashes.data() + pc.r0, bt.read_off.data() + pc.r0,
+                                               bt.user_bin.data(), bt.count.data(), text);
+            const uint64_t tuples = bt.read_off[pc.r1] - bt.read_off[pc.r0];
+            if (tuples > 64) line_bytes_guess = std::max<uint64_t>(64, need / tuples + 16);
+            write_in_turn(pc, text.data(), need);
+            out_written += need;
+            if (pc.h->left.fetch_sub(1) == 1) chunk_done(pc.h);
+        }
+    }
+    void start()
+    {
+        // from here on the report goes to the file descriptor: the header line was the last thing written through the FILE*
+        // (flushed now); nothing may use `out`'s stdio buffer again until the pieces are done, or it would land out of order
+        if (run.out) fflush(run.out);
+        out_fd = run.out ? fileno(run.out) : -1;
+        sequencer = std::thread([this] { sequence(); });
+        for (unsigned ft = 0; ft < formatters; ++ft) fmt_threads.emplace_back([this] { format_pieces(); });
+    }
+    void join()
+    {
+        sequencer.join();
+        for (auto &t : fmt_threads) t.join();
+    }
+};
+
+// How many queued chunks make one GPU batch: ~group_reads reads -- the kernels want >= 10^5 reads in flight, the parsers want
+// chunks small enough to hand out to many threads; short reads (`grow_short`: neither --batch-reads nor --group-reads given): more
+// of them, until the batch holds 2^29 bases -- the library's sub-batches then reach their full size
+struct GroupLimits {
+    uint64_t group_reads;
+    bool grow_short;
+    static constexpr size_t max_chunks = 32;
+    bool wants_more(uint64_t reads, uint64_t bases, size_t chunks) const
+    {
+        return (reads < group_reads || (grow_short && bases < (1ull << 29) && reads < (1u << 20))) && bases < (3ull << 30) && chunks < max_chunks;
+    }
+};
+
+// --device-parse, where the device reported a range irregular: the chunk's file bytes parsed by the reader a range thread would
+// have used (the same records, the same messages for a malformed file).  Returns the message, empty if all went well.
+std::string host_parse(Batch &bt)
+{
+    try {
+        ChunkParser ps;
+        std::deque<std::vector<char>> parts;
+        parts.emplace_back(bt.raw.data(), bt.raw.data() + bt.raw.size());
+        ps.rd.open_mem(std::move(parts), bt.raw_kind == '@');
+        bt.ids.clear();
+        bt.bases.clear();
+        bt.bases.reserve(fastx::bases_bound(bt.raw.size(), bt.raw_kind));
+        bt.offsets.assign(1, 0);
+        ps.parse(bt);
+    } catch (const std::exception &ex) { return ex.what(); }
+    bt.raw_kind = 0;
+    return std::string();
+}
+
+// ---- the devices: one index replica per device (reads are independent, taxor_search.cpp:214: the index is replicated,
+// batches are sharded), the searchers, and the workers that make GPU batches of the queued chunks.  Several devices (north star:
+// "reads sharded across the GPUs, per-read results gathered over RCCL/xGMI"): one communicator; the index crosses PCIe once and is
+// broadcast, rounds of ng batches are classified side by side and their results gathered on the first device (taxor_gpu.h,
+// "Several GPUs of one node").  The transport is decided in upload_index, once, by rule -- never by a failure.
+struct GpuStage {
+    using Chunks = std::vector<std::unique_ptr<Batch>>;
+    SearchRun &run;
+    Pipes &p;
+    size_t ng;
+    unsigned wpg;       // workers per device; with a communicator: that many searcher SETS (one searcher per device each), rounds alternate between them
+    GroupLimits limits;
+    std::vector<taxor_gpu_index *> gidx;
+    taxor_gpu_comm *comm = nullptr;
+    std::string gather;
+    std::vector<taxor_gpu_searcher *> sr;      // device-major: sr[g * wpg + w]
+    std::mutex comm_mu;     // a communicator is single-caller, and its result arrays live until its next gather
+    std::atomic<int> n_running{0};      // GPU batches in flight (single-device workers)
+    std::atomic<uint64_t> n_bam{0};        // BAM chunks unpacked on the device
+    std::atomic<uint64_t> n_scanned{0}, n_host_parsed{0}, n_pageable{0};   // n_pageable: chunks whose buffer could not be page-locked
+    std::vector<std::thread> workers;
+    GpuStage(SearchRun &run_, Pipes &p_, size_t ng_, unsigned wpg_, GroupLimits l) : run(run_), p(p_), ng(ng_), wpg(wpg_), limits(l) {}
+
+    void upload_index(const taxor_hixf_view *view)
+    {
+        const Config &cfg = run.cfg;
+        gidx.assign(ng, nullptr);
+        gather = cfg.gather;
+        if (gather.empty()) {
+            bool distinct = true;
+            for (size_t i = 0; i < ng; ++i)
+                for (size_t j = i + 1; j < ng; ++j) distinct = distinct && cfg.gpus[i] != cfg.gpus[j];
+            gather = ng == 1 ? "none" : (distinct ? "rccl" : "host");
+        }
+        if (gather != "none") {
+            if (taxor_gpu_comm_create(cfg.gpus.data(), (uint32_t)ng, gather == "rccl" ? TAXOR_COMM_RCCL : TAXOR_COMM_HOST, &comm) != TAXOR_OK)
+                die(std::string(taxor_gpu_last_error()) + "\n(--gather host stages the same transfers through host memory)");
+            if (taxor_gpu_index_create_replicated(comm, view, gidx.data()) != TAXOR_OK) die(taxor_gpu_last_error());
+            taxor_gpu_comm_stats cs{};
+            taxor_gpu_comm_info(comm, &cs);
+            if (tune_env("TAXOR_CLI_TRACE"))
+                fprintf(stderr, "[trace] index on %zu devices (%s): %.2f GB per replica, %.2f GB over PCIe, %.2f GB by ncclBroadcast, %.3f s\n", ng,
+                        gather.c_str(), cs.index_bytes / 1e9, cs.index_upload_bytes / 1e9, cs.index_broadcast_bytes / 1e9, cs.index_seconds);
+            return;
+        }
+        std::vector<std::thread> up;
+        std::vector<std::string> errs(ng);
+        for (size_t g = 0; g < ng; ++g)
+            up.emplace_back([this, view, g, &errs] {
+                const int rc = taxor_gpu_index_create(view, run.cfg.gpus[g], &gidx[g]);
+                if (rc != TAXOR_OK) errs[g] = std::string(taxor_gpu_last_error()) + (rc == TAXOR_E_NOMEM ? "\n(--device-index-budget <MiB> searches an index in resident passes: taxor search --advanced-help)" : "");
+            });
+        for (auto &t : up) t.join();
+        for (const auto &e : errs)
+            if (!e.empty()) die(e);
+    }
+    void create_searchers(const taxor_gpu_search_params &prm)
+    {
+        sr.assign(ng * wpg, nullptr);
+        for (size_t g = 0; g < ng; ++g)
+            for (unsigned w = 0; w < wpg; ++w)
+                if (taxor_gpu_searcher_create(gidx[g], &prm, &sr[g * wpg + w]) != TAXOR_OK) die(taxor_gpu_last_error());
+    }
+    // the CSR of several chunks classified as one batch -> each chunk's own CSR
+    void split_results(Chunks &chunks, const taxor_gpu_results &res)
+    {
+        uint64_t r0 = 0;
+        for (auto &bt : chunks) {
+            const uint64_t n = bt->ids.size(), lo = res.read_off[r0], hi = res.read_off[r0 + n];
+            bt->read_off.resize(n + 1);
+            for (uint64_t i = 0; i <= n; ++i) bt->read_off[i] = res.read_off[r0 + i] - lo;
+            bt->user_bin.assign(res.user_bin + lo, res.user_bin + hi);
+            bt->count.assign(res.count + lo, res.count + hi);
+            bt->n_hashes.assign(res.n_hashes + r0, res.n_hashes + r0 + n);
+            r0 += n;
+            run.count_chunk(*bt);
+        }
+        if (r0 != res.n_reads) die("internal: a batch's results do not cover its chunks");
+    }
+    // A chunk of file bytes (--device-parse) or of BAM sequences is a GPU batch by itself.  scan_begin hands it to the device: 0 =
+    // enqueued on s (file bytes: ids and offsets are filled from the scanner's table); 1 = the device reported the bytes irregular
+    // (or met a byte outside dna15, which the parsed path may still repair) and the chunk was parsed here (host_parse) -- it goes on
+    // like any parsed chunk; -1 = err says why
+    int scan_begin(taxor_gpu_searcher *s, Batch &bt, std::string &err)
+    {
+        if (bt.raw_kind == 'B') {
+            const taxor_nibble_segment seg = nibble_segment(bt);
+            if (taxor_gpu_search_nibbles_begin(s, &seg, 1) != TAXOR_OK) { err = taxor_gpu_last_error(); return -1; }
+            bt.raw_kind = 0;
+            ++n_bam;
+            return 0;
+        }
+        taxor_fastx_scan sc{};
+        if (!bt.raw_pinned) ++n_pageable;
+        const int rc = taxor_gpu_search_fastx_begin(s, bt.raw.data(), bt.raw.size(), bt.raw_kind, &sc);
+        if (rc != TAXOR_OK && rc != TAXOR_E_ALPHABET) { err = taxor_gpu_last_error(); return -1; }
+        if (rc != TAXOR_OK || sc.status != 0) {
+            err = host_parse(bt);
+            if (!err.empty()) return -1;
+            ++n_host_parsed;
+            return 1;
+        }
+        uint64_t id_bytes = 0;
+        for (uint64_t r = 0; r < sc.n_reads; ++r) id_bytes += sc.id_len[r];
+        bt.ids.clear();
+        bt.ids.reserve(sc.n_reads, id_bytes);
+        bt.offsets.assign(1, 0);
+        bt.offsets.reserve(sc.n_reads + 1);
+        for (uint64_t r = 0; r < sc.n_reads; ++r) {
+            bt.ids.data.append(bt.raw.data() + sc.id_off[r], sc.id_len[r]);
+            bt.ids.off.push_back(bt.ids.data.size());
+            bt.offsets.push_back(bt.offsets.back() + sc.read_len[r]);
+        }
+        bt.raw_kind = 0;
+        ++n_scanned;
+        return 0;
+    }
+    // one GPU batch: its chunks handed over as segments (unless the scanner enqueued it already, `scanned`), then waited for; the
+    // results come to *res, or (res == nullptr) stay on the device
+    int classify(taxor_gpu_searcher *s, Chunks &chunks, bool scanned, taxor_gpu_results *res)
+    {
+        std::vector<taxor_read_segment> segs;
+        auto once = [&]() -> int {
+            if (!scanned) {
+                segs.clear();
+                for (auto &bt : chunks) segs.push_back({bt->bases.data(), bt->offsets.data(), bt->ids.size()});
+                const int rc = taxor_gpu_search_segments_begin(s, segs.data(), segs.size());
+                if (rc != TAXOR_OK) return rc;
+            }
+            return res ? taxor_gpu_search_batch_end(s, res) : taxor_gpu_batch_sync(s);
+        };
+        return run_with_alphabet_retry(once, chunks);
+    }
+
+    // device g's share of a communicator round; an error message in err
+    void round_on_device(taxor_gpu_searcher *s, Chunks &chunks, std::string &err)
+    {
+        static const uint64_t zero_off[1] = {0};
+        if (chunks.empty()) {       // a device without a batch runs an empty one, so that every searcher has a finished run to gather
+            if (taxor_gpu_search_batch_begin(s, nullptr, zero_off, 0) != TAXOR_OK) err = taxor_gpu_last_error();
+            return;
+        }
+        const bool scanned = chunks[0]->raw_kind && scan_begin(s, *chunks[0], err) == 0;
+        if (!err.empty()) return;
+        for (auto &bt : chunks) pin_bases(*bt);
+        if (classify(s, chunks, scanned, nullptr) != TAXOR_OK) err = taxor_gpu_last_error();
+    }
+    // With a communicator, worker `set`.  One round = up to ng GPU batches, batch g on device g, classified side by side; then ONE
+    // gather of the round's per-read results on the first device and one copy to the host.  A GPU batch is made of queued chunks
+    // like in the single-device workers below (handed over as segments).
+    void gather_worker(unsigned set)
+    {
+        std::vector<taxor_gpu_searcher *> mine(ng);     // searcher of device g in this worker's set
+        for (size_t g = 0; g < ng; ++g) mine[g] = sr[g * wpg + set];
+        std::vector<Chunks> round(ng);
+        Chunks eofs, flat;
+        std::unique_ptr<Batch> b, held;         // held: a chunk of file bytes met while a batch of parsed chunks was being collected
+        bool open = true;
+        while (open || held) {
+            for (auto &g : round) g.clear();
+            eofs.clear();
+            size_t used = 0;
+            // the first chunk of a round is waited for; after that only what is already queued is taken
+            for (size_t g = 0; g < ng; ++g) {
+                uint64_t gr = 0, gb = 0;
+                while (limits.wants_more(gr, gb, round[g].size())) {
+                    bool got;
+                    if (held) { b = std::move(held); got = true; }
+                    else if (used == 0 && round[g].empty() && eofs.empty()) { got = p.q_in.pop(b); if (!got) open = false; }
+                    else got = p.q_in.try_pop(b);
+                    if (!got) break;
+                    if (b->end_of_file) { eofs.push_back(std::move(b)); continue; }
+                    if (b->raw_kind && !round[g].empty()) { held = std::move(b); break; }     // file bytes are a batch by themselves
+                    const bool alone = b->raw_kind != 0;
+                    gr += b->ids.size();
+                    gb += b->bases.size();
+                    round[g].push_back(std::move(b));
+                    ++used;
+                    if (alone) break;
+                }
+                if (round[g].empty()) break;
+            }
+            if (used == 0) {
+                for (auto &e : eofs) p.q_fmt.push(std::move(e));
+                continue;
+            }
+            const double t1 = now();
+            std::vector<std::thread> dev;
+            std::vector<std::string> errs(ng);
+            for (size_t g = 0; g < ng; ++g) dev.emplace_back([this, g, &mine, &round, &errs] { round_on_device(mine[g], round[g], errs[g]); });
+            for (auto &t : dev) t.join();
+            for (const auto &e : errs)
+                if (!e.empty()) die(e);
+            const double t2 = now();
+            flat.clear();                           // the gathered CSR is in device order, and in chunk order within a device
+            for (auto &g : round)
+                for (auto &bt : g) flat.push_back(std::move(bt));
+            double t3;
+            {
+                std::lock_guard<std::mutex> lk(comm_mu);      // the other set's round keeps the devices busy meanwhile
+                taxor_gpu_results res{};
+                if (taxor_gpu_gather_results(comm, mine.data(), &res) != TAXOR_OK) die(taxor_gpu_last_error());
+                t3 = now();
+                split_results(flat, res);
+            }
+            {
+                std::lock_guard<std::mutex> lk(run.stat_mu);
+                run.t_search += t2 - t1;
+                run.t_gather += t3 - t2;
+                run.t_compute += now() - t1;
+                run.n_gpu_batches += std::min(used, ng);
+            }
+            for (auto &bt : flat) p.q_fmt.push(std::move(bt));
+            for (auto &e : eofs) p.q_fmt.push(std::move(e));
+        }
+    }
+    // search to profile: the batch's results go into the profile's CSR where they lie.  Chunks reach a worker in any order, so a
+    // batch is numbered as it arrives; the sequencer, which sees the chunks in input order, notes which number each read got
+    // (FusedProfile::take_ids)
+    void feed_profile(taxor_gpu_searcher *s, Chunks &group)
+    {
+        uint64_t nr = 0;
+        for (auto &bt : group) nr += bt->ids.size();
+        const uint64_t first = run.fused.next_read.fetch_add(nr);
+        uint64_t at = first;
+        for (auto &bt : group) { bt->feed_first = at; at += bt->ids.size(); }
+        const double f0 = now();
+        if (taxor_gpu_profile_feed_add_batch(run.fused.feed, s, first, 0) != TAXOR_OK) die(taxor_gpu_last_error());
+        std::lock_guard<std::mutex> lk(run.stat_mu);
+        run.fused.t_feed += now() - f0;
+    }
+    // Without a communicator, worker wi on its own searcher.
+    void device_worker(size_t wi)
+    {
+        static const double fill_seconds = [] { const char *e = tune_env("TAXOR_CLI_FILL_MS"); return e ? atof(e) * 1e-3 : 0.020; }();
+        // (a third and fourth worker per device that copy their results out and collect the next batch while two "slots" stay taken:
+        // 25-32 Gbp/s against 33-35 with two workers, profiles/r04/cli_variants.txt -- more searchers share the same hardware queues)
+        static const int fill_running = [] { const char *e = tune_env("TAXOR_CLI_FILL_RUNNING"); return e ? atoi(e) : 1; }();
+        Chunks group, eofs;
+        std::unique_ptr<Batch> b, held;     // held: a chunk of file bytes met while a batch of parsed chunks was being collected
+        for (;;) {
+            if (held) b = std::move(held);
+            else if (!p.q_in.pop(b)) break;
+            if (b->end_of_file) { p.q_fmt.push(std::move(b)); continue; }
+            group.clear();
+            eofs.clear();
+            const bool raw = b->raw_kind != 0;      // file bytes: a batch by themselves
+            uint64_t gr = b->ids.size(), gb = b->bases.size();
+            group.push_back(std::move(b));
+            const double t_fill0 = now();
+            while (!raw && limits.wants_more(gr, gb, group.size())) {
+                if (!p.q_in.try_pop(b)) {
+                    // nothing queued: the GPU is the faster side right now.  Launching what there is makes the batches
+                    // small exactly then (a quarter of the size the kernels are fastest at); while enough OTHER batches
+                    // are in flight to keep the device busy this worker goes on collecting instead -- for a bounded
+                    // time, because the chunks it holds may be what the writer is waiting for
+                    if (!(gr < limits.group_reads && gb < (1ull << 29) && now() - t_fill0 < fill_seconds && n_running.load() >= fill_running)) break;
+                    if (!p.q_in.pop_for(b, 100e-6)) { if (p.q_in.done()) break; continue; }
+                }
+                if (b->end_of_file) { eofs.push_back(std::move(b)); continue; }
+                if (b->raw_kind) { held = std::move(b); break; }
+                gr += b->ids.size();
+                gb += b->bases.size();
+                group.push_back(std::move(b));
+            }
+            ++n_running;
+            const double t1 = now();
+            for (auto &bt : group) pin_bases(*bt);
+            const double t2 = now();
+            taxor_gpu_results res{};
+            bool scanned = false;
+            if (raw) {
+                std::string err;
+                scanned = scan_begin(sr[wi], *group[0], err) == 0;
+                if (!err.empty()) die(err);
+            }
+            // without a TSV nothing on the host reads the tuples: they stay on the device for the profile feed
+            if (classify(sr[wi], group, scanned, run.write_tsv ? &res : nullptr) != TAXOR_OK) die(taxor_gpu_last_error());
+            if (run.profile_mode) feed_profile(sr[wi], group);
+            --n_running;
+            const double t3 = now();
+            if (run.write_tsv) split_results(group, res);
+            else
+                for (auto &bt : group) run.count_chunk(*bt);
+            {
+                std::lock_guard<std::mutex> lk(run.stat_mu);
+                run.t_pin += t2 - t1;
+                run.t_search += t3 - t2;
+                ++run.n_gpu_batches;
+                run.t_compute += now() - t1;
+            }
+            for (auto &bt : group) p.q_fmt.push(std::move(bt));
+            for (auto &e : eofs) p.q_fmt.push(std::move(e));
+        }
+    }
+    void run_workers()
+    {
+        if (comm)
+            for (unsigned set = 0; set < wpg; ++set) workers.emplace_back([this, set] { gather_worker(set); });
+        else
+            for (size_t wi = 0; wi < ng * wpg; ++wi) workers.emplace_back([this, wi] { device_worker(wi); });
+        for (auto &t : workers) t.join();
+        trace("GPU workers done");
+        if (run.cfg.device_parse && tune_env("TAXOR_CLI_TRACE"))
+            fprintf(stderr, "[trace] --device-parse: %llu ranges scanned on the device, %llu parsed on the host; %llu copied from pageable memory\n",
+                    (unsigned long long)n_scanned.load(), (unsigned long long)n_host_parsed.load(), (unsigned long long)n_pageable.load());
+        if (n_bam.load() && tune_env("TAXOR_CLI_TRACE"))
+            fprintf(stderr, "[trace] BAM: %llu chunks of 4-bit sequences unpacked on the device\n", (unsigned long long)n_bam.load());
+    }
+    void release()
+    {
+        for (auto *x : sr) taxor_gpu_searcher_destroy(x);
+        if (comm) {
+            taxor_gpu_comm_stats cs{};
+            taxor_gpu_comm_info(comm, &cs);
+            if (tune_env("TAXOR_CLI_TRACE"))
+                fprintf(stderr, "[trace] %llu gathers (%s): %.1f MB from peer devices, %.3f s inside taxor_gpu_gather_results\n",
+                        (unsigned long long)cs.gathers, gather.c_str(), cs.gather_bytes / 1e6, cs.gather_seconds);
+            taxor_gpu_comm_destroy(comm);
+        }
+        for (size_t g = 0; g < ng; ++g) taxor_gpu_index_destroy(gidx[g]);
+        trace("GPU memory released");
+    }
+};
+
+void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view, const taxor_gpu_search_params &prm, const std::vector<std::string> &queries,
+                     bool last, double t0)
+{
+    const Config &cfg = run.cfg;
+    const size_t ng = cfg.gpus.size(), nf = queries.size();
+    const unsigned readers = (unsigned)std::max<size_t>(1, std::min<size_t>({nf, cfg.threads, 8}));
+    const unsigned parse_threads = std::max(1u, std::min(cfg.threads, 32u) / readers);
+    static const unsigned fmt_div = [] { const char *e = tune_env("TAXOR_CLI_FORMATTER_DIV"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 32 ? (unsigned)v : 4u; }();
+    const unsigned formatters = std::max(1u, std::min(cfg.threads, 32u) / fmt_div);
+    static const unsigned workers_per_gpu = [] { const char *e = tune_env("TAXOR_CLI_WORKERS_PER_GPU"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 4 ? (unsigned)v : 2u; }();
+    const GroupLimits limits{cfg.group_reads ? cfg.group_reads : (cfg.batch_reads ? cfg.batch_reads : 131072), !cfg.batch_reads && !cfg.group_reads};
+    Pipes p;
+    BatchPool &pool = p.pool;
+    pool.cap = readers * parse_threads + 16 + 2 + 32 + ng * workers_per_gpu * GroupLimits::max_chunks + 8 + formatters + 8 + 8 + 2 * readers;
+    // ... by count for small chunks; by bytes for the usual ~128 MB ones: 6 GiB for the host stages + 6 GiB per device (two GPU
+    // batches of ~1.3 GB in flight per device, the chunks being parsed, formatted and written) instead of cap x 128 MB
+    // = 19 GB at one device and 75 GB at eight.  The floor lets every stage hold one buffer whatever the budget.
+    pool.floor = readers * parse_threads + 2 * readers + ng * workers_per_gpu + formatters + 8;
+    {
+        const char *e = tune_env("TAXOR_CLI_POOL_GB");
+        const double gb = e ? atof(e) : 0.0;
+        pool.byte_budget = gb > 0.0 ? (uint64_t)(gb * (double)(1ull << 30)) : (6ull + 6ull * ng) << 30;
+    }
+    p.turns.ahead.assign(nf, 0);
+    QueryFeed feed(cfg, queries, p, readers, parse_threads);
+    feed.start();
+    ReportWriter writer(run, h, p, formatters);
+    writer.start();
+    GpuStage gpu(run, p, ng, workers_per_gpu, limits);
+    gpu.upload_index(view);
+    run.t_index += now() - t0;
+    trace("index resident in HBM");
+    const CpuMark cpu0 = cpu_mark();
+    if (tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] index: %.2f GB per replica in %.3f s = %.1f GB/s (file open to resident)\n", taxor_gpu_index_data_bytes(gpu.gidx[0]) / 1e9,
+                now() - t0, taxor_gpu_index_data_bytes(gpu.gidx[0]) / 1e9 / (now() - t0));
+    // the host mapping of the index is not needed any more: its pages go back on a helper thread, beside the search
+    std::thread releaser([h] { taxor_hixf_release_data(h); });
+    const double t_search0 = now();
+    if (run.profile_mode) run.fused.begin(view, taxor_hixf_get_meta(h), run.prof.device);
+    gpu.create_searchers(prm);
+    gpu.run_workers();
+    run.t_search_wall += now() - t_search0;
+    if (tune_env("TAXOR_CLI_TRACE")) {
+        const CpuMark c1 = cpu_mark();
+        const double w = now() - t_search0;
+        fprintf(stderr, "[trace] search phase: %.3f s wall, %.2f s user + %.2f s system CPU = %.1f CPUs busy (allowance %.0f); the cgroup throttled the process in %llu of %llu periods, %.2f thread-seconds\n",
+                w, c1.user - cpu0.user, c1.sys - cpu0.sys, w > 0 ? (c1.user - cpu0.user + c1.sys - cpu0.sys) / w : 0.0, cpu_allowance(),
+                (unsigned long long)(c1.throttled_periods - cpu0.throttled_periods), (unsigned long long)(c1.periods - cpu0.periods), c1.throttled - cpu0.throttled);
+    }
+    p.q_fmt.close();
+    writer.join();
+    feed.closer.join();
+    trace("writer done");
+    if (tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] report: %.2f GB in %llu pieces by %u threads, %.3f s from the first write to the last = %.1f GB/s (%.3f s inside write() = %.1f GB/s)\n",
+                writer.out_written.load() / 1e9, (unsigned long long)writer.next_ticket, formatters, writer.t_last_write - writer.t_first_write,
+                writer.t_last_write > writer.t_first_write ? writer.out_written.load() / 1e9 / (writer.t_last_write - writer.t_first_write) : 0.0, writer.t_write,
+                writer.t_write > 0 ? writer.out_written.load() / 1e9 / writer.t_write : 0.0);
+    run.t_reads += *std::max_element(feed.reader_time.begin(), feed.reader_time.end());
+    gpu.release();
+    if (run.profile_mode) {
+        run.fused.finish(run.prof, cfg.threads, run.t_search_wall);
+        trace("profile written");
+    }
+    releaser.join();
+    taxor_hixf_free(h);
+    trace("host index released");
+    if (last) {
+        // the process is about to end: unpinning and unmapping gigabytes of staging buffers page by page
+        // would only delay the exit (~0.1 s per GB)
+        for (auto &b : pool.free_) (void)b.release();
+    } else {
+        for (auto &b : pool.free_) unpin_buffers(*b);
+    }
+    pool.free_.clear();
+    if (tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] chunk buffers: %zu made (floor %zu, cap %zu), peak %.2f GB on the books against a budget of %.2f GB, %llu released early\n",
+                pool.made, pool.floor, pool.cap, pool.peak_bytes / 1073741824.0, pool.byte_budget / 1073741824.0, (unsigned long long)pool.trimmed);
+    trace("batch buffers released");
+}
+
+// One index, all of `queries`: the index is loaded and uploaded once; query files are read concurrently (a gzip
+// stream inflates on one thread, so several files are the only way to read gzip input faster) and written in the
+// order they were given.
+void search_files(SearchRun &run, const std::string &hixf_file, const std::vector<std::string> &queries, bool last)
+{
+    const Config &cfg = run.cfg;
+    const double t0 = now();
+    taxor_hixf *h = nullptr;
+    if (taxor_hixf_load(hixf_file.c_str(), &h) != TAXOR_OK) die(taxor_gpu_last_error());
+    trace("index file loaded");
+    if (cfg.ixf_arith) {
+        taxor_hixf_set_arith(h, cfg.ixf_arith);
+        taxor_ixf_variant av{};
+        taxor_ixf_arith_decode(cfg.ixf_arith, &av);
+        char desc[512];
+        taxor_ixf_variant_describe(&av, desc, sizeof desc);
+        fprintf(stderr, "[TAXOR SEARCH WARNING] %s is searched under --ixf-arithmetic %s, not under this build's own reading of the\n"
+                        "  un-vendored IXF arithmetic: %s (seed, segment length and row stride per IXF from the file)\n", hixf_file.c_str(),
+                arith_spec(av).c_str(), desc);
+    }
+    if (cfg.layout_given) {
+        if (taxor_hixf_set_layout(h, cfg.ixf_layout) != TAXOR_OK) die(taxor_gpu_last_error());
+        char ld[128];
+        taxor_ixf_layout_describe(cfg.ixf_layout, ld, sizeof ld);
+        fprintf(stderr, "[TAXOR SEARCH WARNING] %s is read under --ixf-layout %s: its fingerprint vectors are transposed into the search layout on the device\n",
+                hixf_file.c_str(), ld);
+    }
+    const taxor_hixf_view *view = taxor_hixf_get_view(h);
+    if (taxor_hixf_get_meta(h)->foreign_schema)
+        fprintf(stderr, "[TAXOR SEARCH WARNING] %s was not written by this library (its IXF records follow another layout, read by probing).\n"
+                        "  The arithmetic of seqan3's interleaved_xor_filter is not part of the reference sources; this build's reading of it has\n"
+                        "  not been checked against this file.  Run `taxor verify --index-file %s --genome-file <a genome in the index>` first:\n"
+                        "  a wrong reading still loads and classifies at the false-positive floor.\n", hixf_file.c_str(), hixf_file.c_str());
+    // threshold model (threshold.hpp:22-47)
+    taxor_gpu_search_params prm{};
+    if (taxor_threshold_select(view, cfg.error_rate, cfg.threshold, &prm) != TAXOR_OK)
+        die("no threshold model for k=" + std::to_string(view->kmer_size) + " and error rate " + std::to_string(cfg.error_rate));
+    switch (prm.model) {                                            // the reference's messages, threshold.hpp:32-46
+    case TAXOR_THR_PERCENTAGE: printf("use percentage-model\t%g\n", cfg.threshold); break;
+    case TAXOR_THR_SYNCMER: printf("use syncmer model\n"); break;
+    case TAXOR_THR_KMER: printf("use kmer-model\n"); break;
+    default: printf("use frac minhash\n"); break;
+    }
+    // paged (--device-index-budget, or an index that does not fit the device) or resident
+    taxor_pass_plan whole{};
+    if (taxor_index_plan_passes(view, ~0ull >> 1, &whole, nullptr, nullptr) != TAXOR_OK) die(taxor_gpu_last_error());
+    uint64_t budget = cfg.index_budget_mib << 20;
+    char why[256] = "";
+    if (budget) snprintf(why, sizeof why, "--device-index-budget %llu MiB", (unsigned long long)cfg.index_budget_mib);
+    else if (whole.index_bytes >= (1ull << 30)) {
+        // (asked only for an index of a gigabyte or more: the question starts the HIP runtime on this thread, before the reader
+        // threads exist, and a reader that dies on a malformed file then ends the process while the runtime is up -- its exit
+        // handlers ran into this thread's index upload.  A smaller index on a device that is full fails as before, and the
+        // message names the option)
+        uint64_t fr = 0, tot = 0;
+        if (taxor_gpu_device_memory(cfg.gpus[0], &fr, &tot) != TAXOR_OK) die(taxor_gpu_last_error());
+        if (whole.index_bytes > fr) {
+            budget = fr - std::min<uint64_t>(4ull << 30, fr / 4);       // the searcher's own buffers live beside the index
+            snprintf(why, sizeof why, "the index needs %llu MiB on the device, %llu MiB are free", (unsigned long long)(whole.index_bytes >> 20), (unsigned long long)(fr >> 20));
+        }
+    }
+    if (budget) search_paged(run, h, view, prm, queries, budget, why, t0);
+    else search_resident(run, h, view, prm, queries, last, t0);
+}

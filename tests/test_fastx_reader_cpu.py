@@ -199,7 +199,7 @@ def test_multi_member_gzip_is_inflated_in_parallel_and_in_order(tmp_path):
 
 def test_bgzip_like_members_through_the_cutter_and_the_parser_pool(tmp_path):
     """Members of 64 KB and less (bgzip), boundaries anywhere -- inside lines, inside reads longer than a member -- quality lines that
-    start with '@' and '+': the members are the chunks the cutter collects into parser jobs (search_main.cpp), small jobs here so that
+    start with '@' and '+': the members are the chunks the cutter collects into parser jobs (query_reader.h), small jobs here so that
     many cuts fall into parts that begin in the middle of a line."""
     rng = np.random.default_rng(21)
     recs = make_records(rng, 260, lo=1, hi=3000) + make_records(rng, 6, lo=90000, hi=150000) + make_records(rng, 200, lo=0, hi=9000)
