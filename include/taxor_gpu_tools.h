@@ -610,6 +610,47 @@ int taxor_gpu_profile_feed_finish(taxor_gpu_profile_feed *f, const uint64_t *ran
 int taxor_gpu_profile_feed_matches(const taxor_gpu_profile_feed *f, taxor_profile_csr *csr, const int64_t **user_bin);
 void taxor_gpu_profile_feed_destroy(taxor_gpu_profile_feed *f);
 
+/* ---- distinct matched hashes per reference (`taxor search --coverage-file`; taxor_amd/csrc/coverage.hip, DESIGN.md section 10,
+ * "Distinct-hash coverage").  QHASH_MATCH summed over reads grows with depth whether the hits spread over a genome or pile up on one
+ * repeat; the accumulator keeps, per user bin and for the whole run, a HyperLogLog sketch of the DISTINCT query hashes that matched it,
+ * beside the number of reads that reported it and the sum of their counts.
+ * A (read, user bin) pair counts when the read's tuple for that bin survives the search's output filter -- taxor_classify_filter's
+ * !((double)count < (double)max * 0.8) -- so reads[b] and hash_matches[b] are what one gets by counting and summing the TSV's lines of
+ * user bin b.  For such a pair every hash h of the read's saved list is looked up in every leaf technical bin (x, j) of b (each bin
+ * with fname_idx == b anywhere in the hierarchy; a split user bin has several): h matches when the three fingerprints of IXF x at h's
+ * rows in column j xor to h's fingerprint, under the index's arithmetic code and x's seed.  A hash that matches in at least one of
+ * them goes into b's sketch: (i, rho) = taxor_hll_slot(h, P), registers[b][i] = max(registers[b][i], rho).
+ * _create: precision P in [4, 16], 0 = 12; `view` is the one the index was created from (only bins and fname_idx are read).  The
+ * registers (n_user_bins << P bytes) and the two counters are held against the device's free memory first: TAXOR_E_NOMEM with both
+ * figures.  A paged index is refused by name (TAXOR_E_ARG): its leaf bins are not all resident.
+ * _add_batch: after taxor_gpu_search_batch_end (or _batch_sync) of a batch that ran with capture on, with that batch's saved lists
+ * (taxor_gpu_search_take_saved), before the next batch on the searcher.  Checked before any launch, TAXOR_E_ARG naming the field:
+ * the saved batch's n_reads is the searcher's, its n_hashes are the searcher's, the searcher's index is the accumulator's.  The lists
+ * are staged through a bounded device buffer; the searcher's device-resident CSR is read where it lies.  Calls may come from
+ * several threads.  The result does not depend on the order of the calls nor on how reads are cut into batches.
+ * _results: host pointers, valid until _destroy or the next _add_batch. */
+typedef struct taxor_gpu_coverage taxor_gpu_coverage;
+typedef struct {
+    uint64_t n_user_bins;
+    uint32_t precision, reserved;
+    const uint64_t *reads;         /* [n_user_bins] surviving tuples of the user bin (lines of the TSV) */
+    const uint64_t *hash_matches;  /* [n_user_bins] their counts summed (QHASH_MATCH summed) */
+    const uint8_t *registers;      /* [n_user_bins << precision] user bin b's sketch at registers + (b << precision) */
+    double seconds_kernels;        /* HIP-event time of the accumulation kernel, summed over the batches */
+    uint64_t probes;               /* (hash, leaf bin) lookups made: three one-byte gathers each */
+} taxor_coverage_results;
+int taxor_gpu_coverage_create(taxor_gpu_index *idx, const taxor_hixf_view *view, uint32_t precision, taxor_gpu_coverage **out);
+int taxor_gpu_coverage_add_batch(taxor_gpu_coverage *c, taxor_gpu_searcher *s, const taxor_gpu_saved *saved);
+int taxor_gpu_coverage_results(taxor_gpu_coverage *c, taxor_coverage_results *out);
+void taxor_gpu_coverage_destroy(taxor_gpu_coverage *c);
+/* Host only.  The slot of a hash: w = wyhash(hash ^ 0x9E3779B97F4A7C15), index = w >> (64 - P), rest = w << P,
+ * rho = rest ? clz64(rest) + 1 : 64 - P + 1 -- the function the device uses (taxor_amd/csrc/hll.h).  The estimate: m = 2^P,
+ * alpha = 0.673, 0.697, 0.709 for m = 16, 32, 64, else 0.7213 / (1 + 1.079 / m); E = alpha m^2 / sum_j 2^-registers[j] in index
+ * order; E = m log(m / V) when E <= 2.5 m and V > 0 registers are zero; no large-range correction (the hashes are 64-bit).  A
+ * precision outside [4, 16]: index 0 and rho 0, NaN. */
+double taxor_hll_estimate(const uint8_t *registers, uint32_t precision);
+void taxor_hll_slot(uint64_t hash, uint32_t precision, uint32_t *index, uint8_t *rho);
+
 /* ---- search straight from file bytes (taxor_amd/csrc/fastx_scan.hip): raw[0, n_bytes) holds whole records of one
  * kind, '>' (FASTA) or '@' (four-line FASTQ) -- what a reader cuts at record boundaries.  The device finds the records, packs their
  * sequences into the searcher's batch and runs the search; taxor_gpu_search_batch_end follows as after any _begin.  raw may be pageable

@@ -190,6 +190,12 @@ class SavedView(C.Structure):
                 ("scaling", C.c_uint32), ("model", C.c_uint32), ("window_size", C.c_uint64), ("error_rate", C.c_double), ("ratio", C.c_double)]
 
 
+class CoverageResults(C.Structure):
+    _fields_ = [("n_user_bins", C.c_uint64), ("precision", C.c_uint32), ("reserved", C.c_uint32), ("reads", C.POINTER(C.c_uint64)),
+                ("hash_matches", C.POINTER(C.c_uint64)), ("registers", C.POINTER(C.c_uint8)), ("seconds_kernels", C.c_double),
+                ("probes", C.c_uint64)]
+
+
 SIGNATURES = {
     "taxor_gpu_last_error": (C.c_char_p, []),
     "taxor_gpu_index_create": (C.c_int, [C.POINTER(HixfView), C.c_int, C.POINTER(_P)]),
@@ -234,6 +240,12 @@ SIGNATURES = {
     "taxor_gpu_profile_feed_finish": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P)]),
     "taxor_gpu_profile_feed_matches": (C.c_int, [_P, C.POINTER(ProfileCsr), C.POINTER(C.POINTER(C.c_int64))]),
     "taxor_gpu_profile_feed_destroy": (None, [_P]),
+    "taxor_gpu_coverage_create": (C.c_int, [_P, C.POINTER(HixfView), C.c_uint32, C.POINTER(_P)]),
+    "taxor_gpu_coverage_add_batch": (C.c_int, [_P, _P, _P]),
+    "taxor_gpu_coverage_results": (C.c_int, [_P, C.POINTER(CoverageResults)]),
+    "taxor_gpu_coverage_destroy": (None, [_P]),
+    "taxor_hll_estimate": (C.c_double, [_P, C.c_uint32]),
+    "taxor_hll_slot": (None, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
     "taxor_gpu_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "taxor_build_layout": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(Layout))]),
     "taxor_layout_free": (None, [C.POINTER(Layout)]),

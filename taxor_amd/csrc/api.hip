@@ -2780,6 +2780,22 @@ extern "C" __attribute__((visibility("hidden"))) int taxor_searcher_device_read_
     return TAXOR_OK;
 }
 
+// library-internal (coverage.hip): the index a searcher works on; an index's IXF descriptors on its device (the seeds as the builder
+// last set them) and their host copies, read-only
+extern "C" __attribute__((visibility("hidden"))) taxor_gpu_index *taxor_searcher_index(taxor_gpu_searcher *s) { return s ? s->idx : nullptr; }
+extern "C" __attribute__((visibility("hidden"))) int taxor_index_descs(const taxor_gpu_index *idx, const IxfDesc **d_ixf, const IxfDesc **h_ixf,
+                                                                       uint64_t *n_ixf, uint64_t *n_user_bins, uint32_t *n_passes, int *device)
+{
+    if (!idx) return -1;
+    *d_ixf = idx->d_ixf;
+    *h_ixf = idx->h_ixf.data();
+    *n_ixf = idx->h_ixf.size();
+    *n_user_bins = idx->n_user_bins;
+    *n_passes = idx->n_passes;
+    *device = idx->device;
+    return 0;
+}
+
 extern "C" int taxor_gpu_batch_fetch(taxor_gpu_searcher *s, taxor_gpu_results *out)
 {
     if (!s || !out) return fail(TAXOR_E_ARG, "batch_fetch: null argument");

@@ -3,6 +3,7 @@
 #include "../../include/taxor_gpu_tools.h"
 #include "ixf_arith.h"
 #include "saved_batch.h"
+#include "hll.h"
 
 #include <algorithm>
 #include <cmath>
@@ -171,6 +172,22 @@ void taxor_classify_filter(const uint32_t *count, uint64_t n, uint8_t *keep)
 }
 
 uint64_t taxor_ixf_seg_len(uint64_t max_bin_elements) { return taxor::ixf_seg_len(max_bin_elements); }
+
+// the sketch of `taxor search --coverage-file` (hll.h): the slot function the device uses, and the estimator.  A precision outside
+// [4, 16] has no sketch: slot 0 / rho 0, estimate NaN
+void taxor_hll_slot(uint64_t hash, uint32_t precision, uint32_t *index, uint8_t *rho)
+{
+    taxor::hll_slot_t s{0, 0};
+    if (precision >= taxor::HLL_MIN_PRECISION && precision <= taxor::HLL_MAX_PRECISION) s = taxor::hll_slot(hash, precision);
+    if (index) *index = s.index;
+    if (rho) *rho = (uint8_t)s.rho;
+}
+
+double taxor_hll_estimate(const uint8_t *registers, uint32_t precision)
+{
+    if (!registers || precision < taxor::HLL_MIN_PRECISION || precision > taxor::HLL_MAX_PRECISION) return std::nan("");
+    return taxor::hll_estimate(registers, precision);
+}
 
 // XOR-filter construction for one bin: peel the 3-uniform hypergraph, assign fingerprints in reverse
 // (the algorithm family of src/main/xorfilter.hpp:142-334; queue formulation).  The dense per-row scratch is

@@ -16,6 +16,8 @@ struct Config : ReaderOptions {              // taxor_search_configuration.hpp:8
     uint64_t index_budget_mib = 0;   // hidden --device-index-budget: fingerprint bytes on the device at a time; the index is searched in resident passes
     bool paged_replay = false;       // hidden --paged-replay: the query file is read in the first resident pass only, the later ones replay the reads' saved hash lists
     bool paged_reread = false;       // hidden --paged-reread: every resident pass reads the query file again (the default, said aloud; wins over --paged-replay)
+    std::string coverage_file;  // --coverage-file: per user bin the reads, the hash matches and the DISTINCT matched hashes of the whole run (coverage.hip)
+    uint32_t coverage_precision = 0;   // hidden --coverage-precision: registers per sketch = 2^this, in [4,16] (0: the library's 12)
     std::string gather;         // several devices: "rccl" | "host" (taxor_gpu_comm transports) | "none" (independent workers, each
                                 // fetching its own results); empty = rccl when the devices are distinct, host when one repeats
 };
@@ -53,6 +55,8 @@ void usage()
             "  --ixf-layout <spec>      search an index whose fingerprint vectors are laid out otherwise than data[row*stride + bin]\n"
             "                           (the spec `taxor verify --variants` / `taxor pin` print, e.g. bin-major,unpadded,segment-major);\n"
             "                           they are transposed on the device while the index is uploaded\n"
+            "  --coverage-file <f>      per reference that any read reported: the reads, their QHASH_MATCH summed, the number of DISTINCT\n"
+            "                           index hashes they matched (a sketch's estimate) and the ratio of the two; ONE index file, ONE device\n"
             "  --expect <tsv>           compare the output per read with a TSV the reference wrote for the same input (exit 3 if it differs)\n"
             "search to profile in one run (the options of `taxor profile`; results go from the device's search buffers into the profile's\n"
             "device pipeline, no TSV is written or parsed in between):\n"
@@ -83,6 +87,17 @@ void advanced_help()
                     "                           without opening the file.  Same output.  When the lists' bound does not fit the host's available\n"
                     "                           memory the run reads the file again in every pass instead, and says so.  Not the default: it has\n"
                     "                           not been measured against re-reading from a file yet (docs/EXPERIMENTS.md).\n"
+                    "  --coverage-file <f>      columns ACCESSION, REFERENCE_NAME, TAXID, REF_LEN, READS, HASH_MATCHES, DISTINCT_HASHES, DUPLICITY; one line per\n"
+                    "                           user bin with READS > 0, in the index's user-bin order.  READS and HASH_MATCHES are by construction what one\n"
+                    "                           gets by counting the lines of --output-file per accession and user bin and summing their QHASH_MATCH (the\n"
+                    "                           lines that survive the 0.8 * max filter).  DISTINCT_HASHES: for every such line the read's hashes are looked\n"
+                    "                           up in the reference's own leaf bins, and those found go into a HyperLogLog sketch per user bin (4096 byte\n"
+                    "                           registers, standard error 1.6 %%); the column is its rounded estimate, at least 1 where HASH_MATCHES > 0.\n"
+                    "                           DUPLICITY = HASH_MATCHES / DISTINCT_HASHES (0.00 where both are 0): near the depth for a genome that is\n"
+                    "                           there, in the thousands for a handful of shared hashes hit again and again.  The searchers keep every\n"
+                    "                           batch's hash lists in host memory until the batch is accumulated.  Refused: a comma list of index files,\n"
+                    "                           several devices, a --gather transport, and an index that has to be paged (--device-index-budget below\n"
+                    "                           the index's size, or an index larger than the device's free memory).\n"
                     "  --paged-reread           the default said aloud: read the query file again in every pass; wins over --paged-replay.\n"
                     "BAM input: the BGZF blocks are inflated on --threads threads, one thread walks the records (block_size, flag, l_seq, read_name)\n"
                     "                           and copies the 4-bit SEQ fields into a page-locked buffer; CIGAR, QUAL and tags are never read.  A\n"
@@ -349,6 +364,8 @@ struct SearchRun {
     std::string gpus_option;        // --gpus / --gpu-list as given (named when the profile options refuse several devices)
     FILE *out = nullptr;
     FusedProfile fused;             // search to profile in one run (profile_mode)
+    taxor_gpu_coverage *coverage = nullptr;   // --coverage-file: the accumulator beside the resident index, for the whole run
+    double t_coverage = 0;          // seconds inside taxor_gpu_coverage_add_batch (taking and freeing the saved lists included), summed over workers
     double t_index = 0, t_reads = 0, t_compute = 0, t_pin = 0, t_search = 0, t_gather = 0, t_search_wall = 0;
     uint64_t n_batches = 0, n_gpu_batches = 0;
     uint64_t total_reads = 0, total_bases = 0;
@@ -419,6 +436,15 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
         else if (k == "--paged-replay") cfg.paged_replay = true;
         else if (k == "--paged-reread") cfg.paged_reread = true;
         else if (k == "--expect") cfg.expect_file = val();
+        else if (k == "--coverage-file") {
+            cfg.coverage_file = val();
+            if (cfg.coverage_file.empty()) die("Validation failed for option --coverage-file: the file name is empty.");
+        }
+        else if (k == "--coverage-precision") {
+            const long n = (long)num(val(), true);
+            if (n < 4 || n > 16) die("Validation failed for option --coverage-precision: Value not in range [4,16].");
+            cfg.coverage_precision = (uint32_t)n;
+        }
         else if (k == "--sequential") cfg.sequential = true;
         else if (k == "--device-parse") cfg.device_parse = true;
         else if (k == "--group-reads") cfg.group_reads = strtoull(val().c_str(), nullptr, 10);
@@ -456,6 +482,16 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             die("Validation failed for option --gather: the profile options run on ONE device, where nothing is gathered; leave --gather out.");
         if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
         prof.device = cfg.gpus[0];
+    }
+    if (cfg.coverage_precision && cfg.coverage_file.empty()) die("Option --coverage-precision sizes the sketches of --coverage-file: it needs that option.");
+    if (!cfg.coverage_file.empty()) {   // before any HIP call
+        if (cfg.index_file.find(',') != std::string::npos)
+            die("Validation failed for option --index-file: --coverage-file takes ONE index file (a user bin's leaf bins are looked up in the index it belongs to); "
+                "search the indexes one by one.");
+        if (cfg.gpus.size() > 1)
+            die("Validation failed for option " + run.gpus_option + ": --coverage-file accumulates on ONE device (the sketches of several would have to be merged); give --gpu <id>.");
+        if (!cfg.gather.empty() && cfg.gather != "none")
+            die("Validation failed for option --gather: --coverage-file runs on ONE device, where nothing is gathered; leave --gather out.");
     }
     run.write_tsv = !run.profile_mode || !cfg.report_file.empty();
     if (cfg.threads == 0) {
@@ -1036,6 +1072,40 @@ std::string host_parse(Batch &bt)
     return std::string();
 }
 
+// ---- `--coverage-file`: the run's table, fetched once.  One line per user bin that any read reported, in user-bin order; the species
+// of a user bin as the TSV names it (the first that carries it, species[0] if none: taxor_search.cpp:172-178,289).
+void write_coverage_file(SearchRun &run, const taxor_hixf_meta *meta)
+{
+    taxor_coverage_results cr{};
+    if (taxor_gpu_coverage_results(run.coverage, &cr) != TAXOR_OK) die(taxor_gpu_last_error());
+    const std::string &path = run.cfg.coverage_file;
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) die("cannot open coverage file " + path);
+    std::vector<uint32_t> bin_species(cr.n_user_bins, 0u);
+    for (uint64_t i = meta->n_species; i-- > 0;)
+        if (meta->species[i].user_bin < cr.n_user_bins) bin_species[meta->species[i].user_bin] = (uint32_t)i;
+    fputs("#ACCESSION\tREFERENCE_NAME\tTAXID\tREF_LEN\tREADS\tHASH_MATCHES\tDISTINCT_HASHES\tDUPLICITY\n", f);
+    uint64_t lines = 0;
+    for (uint64_t b = 0; b < cr.n_user_bins; ++b) {
+        if (cr.reads[b] == 0) continue;
+        long long distinct = llround(taxor_hll_estimate(cr.registers + (b << cr.precision), cr.precision));
+        if (cr.hash_matches[b] > 0 && distinct < 1) distinct = 1;
+        static const taxor_species none{"-", "-", "-", "-", "-", 0, 0};
+        const taxor_species &sp = meta->n_species ? meta->species[bin_species[b]] : none;
+        fprintf(f, "%s\t%s\t%s\t%llu\t%llu\t%llu\t%lld\t%.2f\n", sp.accession_id, sp.organism_name, sp.taxid, (unsigned long long)sp.seq_len,
+                (unsigned long long)cr.reads[b], (unsigned long long)cr.hash_matches[b], distinct, distinct ? (double)cr.hash_matches[b] / (double)distinct : 0.0);
+        ++lines;
+    }
+    if (ferror(f) || fclose(f) != 0) die("cannot write to " + path + ": " + strerror(errno));
+    if (tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] coverage: %llu of %llu user bins reported, precision %u; %.3f s inside the accumulation (summed over workers), %.3f s in its kernel, "
+                        "%llu lookups of a hash in a leaf bin = %.2f G gathers/s, %.1f GB/s of 128-B lines\n",
+                (unsigned long long)lines, (unsigned long long)cr.n_user_bins, cr.precision, run.t_coverage, cr.seconds_kernels, (unsigned long long)cr.probes,
+                cr.seconds_kernels > 0 ? 3.0 * cr.probes / cr.seconds_kernels / 1e9 : 0.0, cr.seconds_kernels > 0 ? 3.0 * 128.0 * cr.probes / cr.seconds_kernels / 1e9 : 0.0);
+    taxor_gpu_coverage_destroy(run.coverage);
+    run.coverage = nullptr;
+}
+
 // ---- the devices: one index replica per device (reads are independent, taxor_search.cpp:214: the index is replicated,
 // batches are sharded), the searchers, and the workers that make GPU batches of the queued chunks.  Several devices (north star:
 // "reads sharded across the GPUs, per-read results gathered over RCCL/xGMI"): one communicator; the index crosses PCIe once and is
@@ -1098,6 +1168,26 @@ struct GpuStage {
         for (size_t g = 0; g < ng; ++g)
             for (unsigned w = 0; w < wpg; ++w)
                 if (taxor_gpu_searcher_create(gidx[g], &prm, &sr[g * wpg + w]) != TAXOR_OK) die(taxor_gpu_last_error());
+    }
+    // --coverage-file: the accumulator beside the (one) index, and every searcher leaves its batches' hash lists for it
+    void begin_coverage(const taxor_hixf_view *view)
+    {
+        if (taxor_gpu_coverage_create(gidx[0], view, run.cfg.coverage_precision, &run.coverage) != TAXOR_OK) die(taxor_gpu_last_error());
+        for (auto *s : sr)
+            if (taxor_gpu_search_capture(s, 1) != TAXOR_OK) die(taxor_gpu_last_error());
+    }
+    // after a batch's end: its saved lists are taken, accumulated and freed -- none is kept across batches, so host memory stays
+    // bounded by the batches in flight
+    void add_coverage(taxor_gpu_searcher *s)
+    {
+        const double c0 = now();
+        taxor_gpu_saved *sv = nullptr;
+        if (taxor_gpu_search_take_saved(s, &sv) != TAXOR_OK) die(taxor_gpu_last_error());
+        const int rc = taxor_gpu_coverage_add_batch(run.coverage, s, sv);
+        taxor_gpu_saved_free(sv);
+        if (rc != TAXOR_OK) die(taxor_gpu_last_error());
+        std::lock_guard<std::mutex> lk(run.stat_mu);
+        run.t_coverage += now() - c0;
     }
     // the CSR of several chunks classified as one batch -> each chunk's own CSR
     void split_results(Chunks &chunks, const taxor_gpu_results &res)
@@ -1315,6 +1405,7 @@ struct GpuStage {
             // without a TSV nothing on the host reads the tuples: they stay on the device for the profile feed
             if (classify(sr[wi], group, scanned, run.write_tsv ? &res : nullptr) != TAXOR_OK) die(taxor_gpu_last_error());
             if (run.profile_mode) feed_profile(sr[wi], group);
+            if (run.coverage) add_coverage(sr[wi]);
             --n_running;
             const double t3 = now();
             if (run.write_tsv) split_results(group, res);
@@ -1402,8 +1493,13 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
     const double t_search0 = now();
     if (run.profile_mode) run.fused.begin(view, taxor_hixf_get_meta(h), run.prof.device);
     gpu.create_searchers(prm);
+    if (!cfg.coverage_file.empty()) gpu.begin_coverage(view);
     gpu.run_workers();
     run.t_search_wall += now() - t_search0;
+    if (run.coverage) {
+        write_coverage_file(run, taxor_hixf_get_meta(h));
+        trace("coverage written");
+    }
     if (tune_env("TAXOR_CLI_TRACE")) {
         const CpuMark c1 = cpu_mark();
         const double w = now() - t_search0;
@@ -1503,6 +1599,14 @@ void search_files(SearchRun &run, const std::string &hixf_file, const std::vecto
             budget = fr - std::min<uint64_t>(4ull << 30, fr / 4);       // the searcher's own buffers live beside the index
             snprintf(why, sizeof why, "the index needs %llu MiB on the device, %llu MiB are free", (unsigned long long)(whole.index_bytes >> 20), (unsigned long long)(fr >> 20));
         }
+    }
+    if (!cfg.coverage_file.empty()) {
+        // the accumulator looks a user bin's hashes up in ALL its leaf bins: they must be resident together.  A budget the index fits
+        // within pages nothing: the resident route is taken
+        if (budget && cfg.index_budget_mib && whole.index_bytes <= budget) budget = 0;
+        if (budget)
+            die("Validation failed for option --coverage-file: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
+                std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; accumulating pass by pass is not built.");
     }
     if (budget) search_paged(run, h, view, prm, queries, budget, why, t0);
     else search_resident(run, h, view, prm, queries, last, t0);

@@ -648,6 +648,75 @@ def saved_store_fits(bound_bytes, available_bytes):
     return bool(_lib.lib().taxor_saved_store_fits(int(bound_bytes), int(available_bytes)))
 
 
+def hll_slot(h, precision=12):
+    """taxor_hll_slot (host only): (register index, rho) of one hash -- the function the device uses"""
+    i, rho = C.c_uint32(), C.c_uint8()
+    _lib.lib().taxor_hll_slot(int(h) & (2**64 - 1), int(precision), C.byref(i), C.byref(rho))
+    return int(i.value), int(rho.value)
+
+
+def hll_estimate(registers, precision=12):
+    """taxor_hll_estimate (host only): the distinct count a sketch's 2^precision byte registers stand for"""
+    r = np.ascontiguousarray(registers, dtype=np.uint8)
+    assert r.size == 1 << int(precision)
+    return float(_lib.lib().taxor_hll_estimate(_p(r), int(precision)))
+
+
+@dataclass
+class CoverageTable:
+    """Coverage.results(): per user bin the surviving tuples, their counts summed, and the sketch of the distinct matched hashes"""
+    precision: int
+    reads: np.ndarray          # uint64[n_user_bins]
+    hash_matches: np.ndarray   # uint64[n_user_bins]
+    registers: np.ndarray      # uint8[n_user_bins, 2^precision]
+    seconds_kernels: float
+    probes: int
+
+    def distinct(self, b):
+        """DISTINCT_HASHES of `taxor search --coverage-file`: the rounded estimate, at least 1 where anything matched"""
+        d = int(np.floor(hll_estimate(self.registers[b], self.precision) + 0.5))      # llround: halves away from zero
+        return max(d, 1) if self.hash_matches[b] else d
+
+
+class Coverage:
+    """Distinct matched hashes per user bin over a whole run (taxor_amd/csrc/coverage.hip).  `ixfs` is the list the GpuIndex was made
+    from (only bins and fname_idx are read).  add_batch follows a batch that ran with Searcher.capture() on and takes its
+    SavedBatch, which stays the caller's."""
+
+    def __init__(self, index: GpuIndex, ixfs, precision=0):
+        view, keep = GpuIndex._view([dict(f, data=None) for f in ixfs], index.n_user_bins, index.k, index.s, index.t, index.use_syncmer, 1,
+                                    index.window_size)
+        self._L = _lib.lib()
+        self._h = C.c_void_p()
+        self.index = index
+        check(self._L.taxor_gpu_coverage_create(index._h, C.byref(view), int(precision), C.byref(self._h)))
+        del keep
+
+    def add_batch(self, searcher: Searcher, saved: "SavedBatch"):
+        check(self._L.taxor_gpu_coverage_add_batch(self._h, searcher._h, saved._h if saved is not None else None))
+
+    def results(self) -> CoverageTable:
+        res = _lib.CoverageResults()
+        check(self._L.taxor_gpu_coverage_results(self._h, C.byref(res)))
+        n, p = int(res.n_user_bins), int(res.precision)
+        arr = lambda ptr, m, dt: np.ctypeslib.as_array(ptr, shape=(m,)).copy() if m else np.zeros(0, dt)
+        return CoverageTable(p, arr(res.reads, n, np.uint64), arr(res.hash_matches, n, np.uint64),
+                             arr(res.registers, n << p, np.uint8).reshape(n, 1 << p), float(res.seconds_kernels), int(res.probes))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.taxor_gpu_coverage_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Comm:
     """Several GPUs of one node driven by this one process (the C++ host's `taxor search --gpus N` shape): the index is
     replicated (one upload + ncclBroadcast), every device classifies its own batch, results are gathered on devices[0].
