@@ -651,6 +651,78 @@ void taxor_gpu_coverage_destroy(taxor_gpu_coverage *c);
 double taxor_hll_estimate(const uint8_t *registers, uint32_t precision);
 void taxor_hll_slot(uint64_t hash, uint32_t precision, uint32_t *index, uint8_t *rho);
 
+/* ---- per-read lowest common ancestor and per-taxon tallies (`taxor search --lca-file / --report-file`; taxor_amd/csrc/lineage.h and
+ * lca.hip).
+ * The lineage (host only).  User bin b's species is the first species whose user_bin == b, species[0] if there is none
+ * (taxor_format_read's rule).  ids = split(taxid_string, ';'), names = split(taxnames_string, ';'), no trailing empty field; position d
+ * of ids pairs with position d of names.  A node is a distinct non-empty id string; node numbers are dense, in byte-wise order of the
+ * id strings.  A node's name is names[d] without its first three characters (empty if shorter than 3), its rank letter names[d][0]
+ * ('-' if the field is empty); the first occurrence in user-bin order decides.  The compacted path of b is its non-empty ids as node
+ * numbers, root-down; a node's parent is its predecessor, the first node's parent is ROOT.  ROOT is a virtual node with id string "1",
+ * name "root", rank 'R'; a compacted path whose first id is "1" starts at ROOT itself, and that id is not stored in path[].  Refused
+ * (TAXOR_E_ARG, the message names the ids and the accessions): an id with two different parents in two paths, an id twice in one path
+ * (a "1" anywhere but first included), a compacted path of more than 64 ids (a leading "1" counts), names shorter than ids.  A user bin
+ * without a non-empty id has the empty path and sits directly under ROOT.
+ * The accumulator lives beside a resident index for a whole run.  _create uploads the paths as a CSR (path_off, path): real paths
+ * hold seven or eight nodes, and a fixed pitch of the maximum depth would let ONE deep path multiply the table of every user bin by up
+ * to eight; the CSR costs one more 4-byte load per surviving tuple.  It allocates direct_reads and direct_bases, 64-bit, for the nodes
+ * plus ROOT plus UNCLASSIFIED.  TAXOR_E_ARG naming the field: the lineage's n_user_bins is not the index's; a paged index is refused by
+ * name (its final tuples exist only after the last pass's merge).
+ * For read r with tuples T: m = the maximum count; the survivors are the tuples with !((double)count < (double)m * 0.8), fp64 as
+ * written (taxor_classify_filter's expression).  T empty or m == 0: UNCLASSIFIED, n_refs = 0, best = 0 -- a read without a hash
+ * reports every leaf with count 0 and the TSV prints those lines; here nothing matched, so the read is unclassified.  Otherwise node =
+ * the last node of the longest common prefix of the survivors' compacted paths, ROOT for the empty prefix; best = m; n_refs = the
+ * survivors.  direct_reads[node] += 1, direct_bases[node] += the read's length.
+ * _add_batch: after taxor_gpu_search_batch_end (or _batch_sync), before the next batch on the searcher.  Reads the searcher's
+ * device-resident CSR where it lies, the read lengths from the batch's offsets; one kernel (one wave per read).  No capture is needed.
+ * calls: page-locked host memory, valid until the next _add_batch on THAT searcher (or _destroy); n_hashes is the searcher's QHASH_COUNT
+ * per read, copied beside the three words of the call.  first_read numbers the batch's first read among all reads and is handed back
+ * in calls.  Checked before any launch, TAXOR_E_ARG naming the field: the searcher's `index` is the accumulator's.
+ * _add_csr: the same over host arrays (tuples of read r at [read_off[r], read_off[r+1]) of user_bin / count; query_len[n_reads]);
+ * a `user_bin` outside the lineage is refused before any launch; calls.n_hashes is NULL; valid until the next _add_csr.
+ * _add calls may come from several threads.  Sums are order-free: the tallies do not depend on the order of the calls, on how reads are
+ * cut into batches, or on the launch geometry.
+ * _results: host pointers, valid until _destroy or the next _results. */
+typedef struct taxor_lineage taxor_lineage;
+typedef struct {
+    uint64_t n_user_bins, n_nodes;
+    uint32_t max_depth, reserved;   /* the longest stored path */
+    const uint32_t *bin_species;    /* [n_user_bins] */
+    const uint64_t *path_off;       /* [n_user_bins + 1] */
+    const int32_t *path;            /* [path_off[n_user_bins]] node numbers, root-down */
+    const int32_t *parent;          /* [n_nodes] node number or TAXOR_LCA_ROOT */
+    const uint32_t *depth;          /* [n_nodes] 1 for ROOT's children */
+    const char *const *id;          /* [n_nodes] */
+    const char *const *name;        /* [n_nodes] */
+    const char *rank;               /* [n_nodes] one letter each, not NUL-terminated */
+} taxor_lineage_view;
+int taxor_lineage_create(const taxor_hixf_meta *meta, uint64_t n_user_bins, taxor_lineage **out);
+int taxor_lineage_get_view(const taxor_lineage *l, taxor_lineage_view *out);
+void taxor_lineage_free(taxor_lineage *l);
+#define TAXOR_LCA_ROOT (-1)
+#define TAXOR_LCA_UNCLASSIFIED (-2)
+typedef struct taxor_gpu_lca taxor_gpu_lca;
+typedef struct {
+    uint64_t n_reads, first_read;
+    const int32_t *node;       /* [n_reads] node number, TAXOR_LCA_ROOT or TAXOR_LCA_UNCLASSIFIED */
+    const uint32_t *best;      /* [n_reads] the read's maximum count, 0 for an unclassified read */
+    const uint32_t *n_refs;    /* [n_reads] surviving tuples, 0 for an unclassified read */
+    const uint32_t *n_hashes;  /* [n_reads] QHASH_COUNT (_add_batch), NULL (_add_csr) */
+} taxor_lca_calls;
+typedef struct {
+    uint64_t n_nodes;
+    const uint64_t *direct_reads;  /* [n_nodes + 2]: the nodes, then ROOT at n_nodes, UNCLASSIFIED at n_nodes + 1 */
+    const uint64_t *direct_bases;  /* [n_nodes + 2] likewise: read lengths summed */
+    uint64_t n_reads;              /* reads added so far */
+    double seconds_kernel;         /* HIP-event time of the kernel, summed over the calls */
+} taxor_lca_results;
+int taxor_gpu_lca_create(taxor_gpu_index *idx, const taxor_lineage *lineage, taxor_gpu_lca **out);
+int taxor_gpu_lca_add_batch(taxor_gpu_lca *lca, taxor_gpu_searcher *s, uint64_t first_read, taxor_lca_calls *calls);
+int taxor_gpu_lca_add_csr(taxor_gpu_lca *lca, uint64_t n_reads, const uint64_t *read_off, const int64_t *user_bin, const uint32_t *count,
+                          const uint64_t *query_len, taxor_lca_calls *calls);
+int taxor_gpu_lca_results(taxor_gpu_lca *lca, taxor_lca_results *out);
+void taxor_gpu_lca_destroy(taxor_gpu_lca *lca);
+
 /* ---- search straight from file bytes (taxor_amd/csrc/fastx_scan.hip): raw[0, n_bytes) holds whole records of one
  * kind, '>' (FASTA) or '@' (four-line FASTQ) -- what a reader cuts at record boundaries.  The device finds the records, packs their
  * sequences into the searcher's batch and runs the search; taxor_gpu_search_batch_end follows as after any _begin.  raw may be pageable

@@ -196,6 +196,26 @@ class CoverageResults(C.Structure):
                 ("probes", C.c_uint64)]
 
 
+class LineageView(C.Structure):
+    _fields_ = [("n_user_bins", C.c_uint64), ("n_nodes", C.c_uint64), ("max_depth", C.c_uint32), ("reserved", C.c_uint32),
+                ("bin_species", C.POINTER(C.c_uint32)), ("path_off", C.POINTER(C.c_uint64)), ("path", C.POINTER(C.c_int32)),
+                ("parent", C.POINTER(C.c_int32)), ("depth", C.POINTER(C.c_uint32)), ("id", C.POINTER(C.c_char_p)),
+                ("name", C.POINTER(C.c_char_p)), ("rank", C.POINTER(C.c_char))]
+
+
+LCA_ROOT, LCA_UNCLASSIFIED = -1, -2
+
+
+class LcaCalls(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("first_read", C.c_uint64), ("node", C.POINTER(C.c_int32)), ("best", C.POINTER(C.c_uint32)),
+                ("n_refs", C.POINTER(C.c_uint32)), ("n_hashes", C.POINTER(C.c_uint32))]
+
+
+class LcaResults(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint64), ("direct_reads", C.POINTER(C.c_uint64)), ("direct_bases", C.POINTER(C.c_uint64)),
+                ("n_reads", C.c_uint64), ("seconds_kernel", C.c_double)]
+
+
 SIGNATURES = {
     "taxor_gpu_last_error": (C.c_char_p, []),
     "taxor_gpu_index_create": (C.c_int, [C.POINTER(HixfView), C.c_int, C.POINTER(_P)]),
@@ -244,6 +264,14 @@ SIGNATURES = {
     "taxor_gpu_coverage_add_batch": (C.c_int, [_P, _P, _P]),
     "taxor_gpu_coverage_results": (C.c_int, [_P, C.POINTER(CoverageResults)]),
     "taxor_gpu_coverage_destroy": (None, [_P]),
+    "taxor_lineage_create": (C.c_int, [C.POINTER(HixfMeta), C.c_uint64, C.POINTER(_P)]),
+    "taxor_lineage_get_view": (C.c_int, [_P, C.POINTER(LineageView)]),
+    "taxor_lineage_free": (None, [_P]),
+    "taxor_gpu_lca_create": (C.c_int, [_P, _P, C.POINTER(_P)]),
+    "taxor_gpu_lca_add_batch": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(LcaCalls)]),
+    "taxor_gpu_lca_add_csr": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, C.POINTER(LcaCalls)]),
+    "taxor_gpu_lca_results": (C.c_int, [_P, C.POINTER(LcaResults)]),
+    "taxor_gpu_lca_destroy": (None, [_P]),
     "taxor_hll_estimate": (C.c_double, [_P, C.c_uint32]),
     "taxor_hll_slot": (None, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
     "taxor_gpu_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

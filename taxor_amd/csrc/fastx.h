@@ -142,6 +142,9 @@ struct Batch {
     uint64_t pool_bytes = 0;    // what the CLI's buffer pool has on its books for this batch (query_reader.h, BatchPool)
     uint32_t fills = 0;         // how often this buffer has been filled by a parser: it is page-locked when it comes round again
     uint64_t feed_first = 0;    // search-to-profile in one run: the index its first read was given in the profile feed
+    // --lca-file / --report-file: the reads' calls copied out of the accumulator (lca.hip); n_hashes above comes with them when no TSV is written
+    std::vector<int32_t> lca_node;
+    std::vector<uint32_t> lca_best, lca_refs;
     // --device-parse: the chunk is a byte range of the file as read (whole records of kind raw_kind, '>' or '@'); the device finds
     // the records, ids and offsets are filled from its table and bases stays empty.  raw_kind 0: a parsed chunk, as above
     BaseBuf raw;

@@ -4,6 +4,7 @@
 #include "ixf_arith.h"
 #include "saved_batch.h"
 #include "hll.h"
+#include "lineage.h"
 
 #include <algorithm>
 #include <cmath>
@@ -189,8 +190,7 @@ double taxor_hll_estimate(const uint8_t *registers, uint32_t precision)
     return taxor::hll_estimate(registers, precision);
 }
 
-// XOR-filter construction for one bin: peel the 3-uniform hypergraph, assign fingerprints in reverse
-// (the algorithm family of src/main/xorfilter.hpp:142-334; queue formulation).  The dense per-row scratch is
+// XOR-filter construction for one bin: peel the 3-uniform hypergraph, assign fingerprints in reverse// (the algorithm family of src/main/xorfilter.hpp:142-334; queue formulation).  The dense per-row scratch is
 // kept per thread and only the touched rows are cleared, so sparse bins of a very tall IXF cost O(n).
 int taxor_ixf_build_bin(const uint64_t *keys, uint64_t n, uint64_t seed, uint64_t seg_len, uint8_t *column)
 {
@@ -710,5 +710,53 @@ uint64_t taxor_saved_bytes_bound(uint64_t bases, int use_syncmer, uint32_t kmer_
 }
 
 int taxor_saved_store_fits(uint64_t bound_bytes, uint64_t available_bytes) { return taxor::saved_store_fits(bound_bytes, available_bytes) ? 1 : 0; }
+
+} // extern "C"
+
+// ---- the lineage table of `taxor search --lca-file / --report-file` (lineage.h).  Host only.
+struct taxor_lineage {
+    taxor::Lineage l;
+    std::vector<const char *> id_p, name_p;
+};
+
+extern "C" {
+
+int taxor_lineage_create(const taxor_hixf_meta *meta, uint64_t n_user_bins, taxor_lineage **out)
+{
+    if (!out) return plan_fail(TAXOR_E_ARG, "lineage_create: null argument");
+    *out = nullptr;
+    if (!meta || (meta->n_species && !meta->species)) return plan_fail(TAXOR_E_ARG, "lineage_create: null argument");
+    if (n_user_bins >= (1ull << 31)) return plan_fail(TAXOR_E_ARG, "lineage_create: user bins are numbered in 31 bits");
+    auto *t = new taxor_lineage;
+    const std::string err = taxor::lineage_build(*meta, n_user_bins, t->l);
+    if (!err.empty()) {
+        delete t;
+        return plan_fail(TAXOR_E_ARG, "%s", err.c_str());
+    }
+    for (const auto &s : t->l.id) t->id_p.push_back(s.c_str());
+    for (const auto &s : t->l.name) t->name_p.push_back(s.c_str());
+    *out = t;
+    return TAXOR_OK;
+}
+
+int taxor_lineage_get_view(const taxor_lineage *t, taxor_lineage_view *v)
+{
+    if (!t || !v) return plan_fail(TAXOR_E_ARG, "lineage_get_view: null argument");
+    v->n_user_bins = t->l.n_bins;
+    v->n_nodes = t->l.id.size();
+    v->max_depth = t->l.max_depth;
+    v->reserved = 0;
+    v->bin_species = t->l.bin_species.data();
+    v->path_off = t->l.path_off.data();
+    v->path = t->l.path.data();
+    v->parent = t->l.parent.data();
+    v->depth = t->l.depth.data();
+    v->id = t->id_p.data();
+    v->name = t->name_p.data();
+    v->rank = t->l.rank.data();
+    return TAXOR_OK;
+}
+
+void taxor_lineage_free(taxor_lineage *t) { delete t; }
 
 } // extern "C"

@@ -18,6 +18,10 @@ struct Config : ReaderOptions {              // taxor_search_configuration.hpp:8
     bool paged_reread = false;       // hidden --paged-reread: every resident pass reads the query file again (the default, said aloud; wins over --paged-replay)
     std::string coverage_file;  // --coverage-file: per user bin the reads, the hash matches and the DISTINCT matched hashes of the whole run (coverage.hip)
     uint32_t coverage_precision = 0;   // hidden --coverage-precision: registers per sketch = 2^this, in [4,16] (0: the library's 12)
+    std::string lca_file;       // --lca-file: one line per read, its lowest common ancestor (lca.hip)
+    std::string kraken_file;    // --report-file: Kraken-style clade report of the whole run
+    std::string report_unit;    // --report-unit reads | bases (empty: reads): which tally fills the report's first three columns
+    bool lca_mode() const { return !lca_file.empty() || !kraken_file.empty(); }
     std::string gather;         // several devices: "rccl" | "host" (taxor_gpu_comm transports) | "none" (independent workers, each
                                 // fetching its own results); empty = rccl when the devices are distinct, host when one repeats
 };
@@ -57,6 +61,10 @@ void usage()
             "                           they are transposed on the device while the index is uploaded\n"
             "  --coverage-file <f>      per reference that any read reported: the reads, their QHASH_MATCH summed, the number of DISTINCT\n"
             "                           index hashes they matched (a sketch's estimate) and the ratio of the two; ONE index file, ONE device\n"
+            "  --lca-file <f>           one line per read: C or U, the read, the taxid of the lowest common ancestor of the references it\n"
+            "                           matched, its length, hash count, best match and the number of references  } ONE index file, ONE\n"
+            "  --report-file <f>        Kraken-style report: per taxon the reads of its clade and its own            } device; --output-file\n"
+            "  --report-unit <reads|bases> what --report-file counts (default reads)                                } is then optional\n"
             "  --expect <tsv>           compare the output per read with a TSV the reference wrote for the same input (exit 3 if it differs)\n"
             "search to profile in one run (the options of `taxor profile`; results go from the device's search buffers into the profile's\n"
             "device pipeline, no TSV is written or parsed in between):\n"
@@ -98,6 +106,20 @@ void advanced_help()
                     "                           batch's hash lists in host memory until the batch is accumulated.  Refused: a comma list of index files,\n"
                     "                           several devices, a --gather transport, and an index that has to be paged (--device-index-budget below\n"
                     "                           the index's size, or an index larger than the device's free memory).\n"
+                    "  --lca-file <f>           columns STATUS, QUERY_NAME, TAXID, QUERY_LEN, QHASH_COUNT, BEST_QHASH_MATCH, REFERENCES; one line per read in the\n"
+                    "                           order --output-file lists the reads in.  The references of a read are the lines --output-file prints for\n"
+                    "                           it (the tuples that survive the 0.8 * max filter); each reference's path is the non-empty ids of its\n"
+                    "                           TAX_ID_STR, and TAXID is the last id of the paths' longest common prefix: 1 (root) where they share none.\n"
+                    "                           A read whose best match is 0 is unclassified (U, TAXID 0, and 0 in the last three columns): a read\n"
+                    "                           without a hash reports every reference with QHASH_MATCH 0, and --output-file prints those lines, but\n"
+                    "                           nothing matched.  The index's taxonomy must be a tree: an id with two parents, an id twice in one path,\n"
+                    "                           more than 64 ids or fewer names than ids in one path are refused with the ids and accessions involved.\n"
+                    "  --report-file <f>        six tab-separated columns per taxon: percentage of the clade (%%6.2f of all reads), reads (or bases) of the clade,\n"
+                    "                           reads called exactly there, rank code (U, R, D, P, C, O, F, G, S from the k p c o f g s prefixes of TAX_STR,\n"
+                    "                           - otherwise), taxid, name indented by two spaces per depth.  unclassified first, then the tree from the\n"
+                    "                           root, depth-first, children by clade count descending and taxid ascending; empty clades are left out.\n"
+                    "                           Both options: a comma list of index files, several devices, a --gather transport and an index that has\n"
+                    "                           to be paged are refused; without --output-file the per-read tuples never leave the device.\n"
                     "  --paged-reread           the default said aloud: read the query file again in every pass; wins over --paged-replay.\n"
                     "BAM input: the BGZF blocks are inflated on --threads threads, one thread walks the records (block_size, flag, l_seq, read_name)\n"
                     "                           and copies the 4-bit SEQ fields into a page-locked buffer; CIGAR, QUAL and tags are never read.  A\n"
@@ -365,6 +387,12 @@ struct SearchRun {
     FILE *out = nullptr;
     FusedProfile fused;             // search to profile in one run (profile_mode)
     taxor_gpu_coverage *coverage = nullptr;   // --coverage-file: the accumulator beside the resident index, for the whole run
+    taxor_lineage_view lineage_view{};
+    taxor_lineage *lineage = nullptr;         // --lca-file / --report-file: the index's taxonomy as a tree (lineage.h) ...
+    taxor_gpu_lca *lca = nullptr;             // ... and the accumulator beside the resident index, for the whole run (lca.hip)
+    FILE *lca_out = nullptr;                  // --lca-file; written by the sequencer, which sees the chunks in input order
+    std::atomic<uint64_t> lca_next_read{0};   // the next batch's first read as the accumulator numbers it
+    double t_lca = 0;               // seconds inside taxor_gpu_lca_add_batch, summed over workers
     double t_coverage = 0;          // seconds inside taxor_gpu_coverage_add_batch (taking and freeing the saved lists included), summed over workers
     double t_index = 0, t_reads = 0, t_compute = 0, t_pin = 0, t_search = 0, t_gather = 0, t_search_wall = 0;
     uint64_t n_batches = 0, n_gpu_batches = 0;
@@ -445,6 +473,18 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             if (n < 4 || n > 16) die("Validation failed for option --coverage-precision: Value not in range [4,16].");
             cfg.coverage_precision = (uint32_t)n;
         }
+        else if (k == "--lca-file") {
+            cfg.lca_file = val();
+            if (cfg.lca_file.empty()) die("Validation failed for option --lca-file: the file name is empty.");
+        }
+        else if (k == "--report-file") {
+            cfg.kraken_file = val();
+            if (cfg.kraken_file.empty()) die("Validation failed for option --report-file: the file name is empty.");
+        }
+        else if (k == "--report-unit") {
+            cfg.report_unit = val();
+            if (cfg.report_unit != "reads" && cfg.report_unit != "bases") die("Validation failed for option --report-unit: Value not in {reads, bases}.");
+        }
         else if (k == "--sequential") cfg.sequential = true;
         else if (k == "--device-parse") cfg.device_parse = true;
         else if (k == "--group-reads") cfg.group_reads = strtoull(val().c_str(), nullptr, 10);
@@ -493,7 +533,19 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
         if (!cfg.gather.empty() && cfg.gather != "none")
             die("Validation failed for option --gather: --coverage-file runs on ONE device, where nothing is gathered; leave --gather out.");
     }
-    run.write_tsv = !run.profile_mode || !cfg.report_file.empty();
+    if (!cfg.report_unit.empty() && cfg.kraken_file.empty()) die("Option --report-unit says what --report-file counts: it needs that option.");
+    if (cfg.lca_mode()) {   // before any HIP call
+        const std::string opt = !cfg.lca_file.empty() ? "--lca-file" : "--report-file";
+        if (cfg.index_file.find(',') != std::string::npos)
+            die("Validation failed for option --index-file: " + opt + " takes ONE index file (a read's references are reduced within the taxonomy of the index they come from); "
+                "search the indexes one by one.");
+        if (cfg.gpus.size() > 1)
+            die("Validation failed for option " + run.gpus_option + ": " + opt + " tallies on ONE device (the tallies of several would have to be merged); give --gpu <id>.");
+        if (!cfg.gather.empty() && cfg.gather != "none")
+            die("Validation failed for option --gather: " + opt + " runs on ONE device, where nothing is gathered; leave --gather out.");
+        if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
+    }
+    run.write_tsv = !(run.profile_mode || cfg.lca_mode()) || !cfg.report_file.empty();
     if (cfg.threads == 0) {
         // --threads not given.  The reference's default is one worker thread (taxor_search_configuration.hpp:17) -- there the
         // thread that classifies; here host threads only parse the query file and render text for the GPU, and one of them
@@ -960,6 +1012,7 @@ struct ReportWriter {
                 const Batch &bt = *hd->b;
                 const size_t n = bt.ids.size();
                 if (run.profile_mode) run.fused.take_ids(bt);            // chunks pass here in input order
+                if (run.lca_out) write_lca_lines(bt);
                 if (n == 0 || !run.write_tsv) { chunk_done(hd); continue; }
                 // cut where the estimated text passes piece_bytes
                 const uint64_t per_tuple = line_bytes_guess.load();
@@ -975,6 +1028,32 @@ struct ReportWriter {
             }
         }
         q_piece.close();
+    }
+    // --lca-file: the chunk's reads, one line each, by the sequencer (one line per read is little next to the TSV's six and more)
+    std::string lca_text;
+    void write_lca_lines(const Batch &bt)
+    {
+        const taxor_lineage_view &lv = run.lineage_view;
+        const size_t n = bt.ids.size();
+        if (bt.lca_node.size() != n || bt.n_hashes.size() != n) die("internal: a chunk reached the writer without its reads' calls");
+        lca_text.clear();
+        char num[4][24];
+        for (size_t r = 0; r < n; ++r) {
+            const int32_t node = bt.lca_node[r];
+            const bool u = node == TAXOR_LCA_UNCLASSIFIED;
+            lca_text += u ? "U\t" : "C\t";
+            lca_text.append(bt.ids.ptr(r), bt.ids.len(r));
+            lca_text += '\t';
+            lca_text += u ? "0" : node == TAXOR_LCA_ROOT ? "1" : lv.id[node];
+            snprintf(num[0], sizeof num[0], "%llu", (unsigned long long)(bt.offsets[r + 1] - bt.offsets[r]));
+            snprintf(num[1], sizeof num[1], "%u", u ? 0u : bt.n_hashes[r]);
+            snprintf(num[2], sizeof num[2], "%u", bt.lca_best[r]);
+            snprintf(num[3], sizeof num[3], "%u", bt.lca_refs[r]);
+            for (const auto &x : num) { lca_text += '\t'; lca_text += x; }
+            lca_text += '\n';
+        }
+        if (!lca_text.empty() && fwrite(lca_text.data(), 1, lca_text.size(), run.lca_out) != lca_text.size())
+            die("cannot write to " + run.cfg.lca_file + ": " + strerror(errno));
     }
     // a piece's text goes to the file when its ticket comes up
     void write_in_turn(const Piece &pc, const char *text, uint64_t need)
@@ -1106,6 +1185,73 @@ void write_coverage_file(SearchRun &run, const taxor_hixf_meta *meta)
     run.coverage = nullptr;
 }
 
+// ---- `--report-file`: the run's tallies, fetched once, rolled up the tree on the host (a few hundred thousand nodes at most, once per
+// run) and written as a Kraken-style report; `--lca-file` is closed here as well.  The layout: percentage of
+// the clade, clade count, direct count, rank code, taxid, name indented by two spaces per depth; unclassified first, then the tree from
+// the root depth-first, children by clade count descending, ties by id string byte-wise ascending; empty clades are left out.
+void finish_lca(SearchRun &run)
+{
+    const Config &cfg = run.cfg;
+    if (run.lca_out) {
+        if (ferror(run.lca_out) || fclose(run.lca_out) != 0) die("cannot write to " + cfg.lca_file + ": " + strerror(errno));
+        run.lca_out = nullptr;
+    }
+    taxor_lca_results lr{};
+    if (taxor_gpu_lca_results(run.lca, &lr) != TAXOR_OK) die(taxor_gpu_last_error());
+    const taxor_lineage_view &lv = run.lineage_view;
+    const uint64_t nn = lr.n_nodes;
+    if (!cfg.kraken_file.empty()) {
+        const uint64_t *direct = cfg.report_unit == "bases" ? lr.direct_bases : lr.direct_reads;
+        FILE *f = fopen(cfg.kraken_file.c_str(), "wb");
+        if (!f) die("cannot open report file " + cfg.kraken_file);
+        // clade counts: a node's parent has the smaller depth, so deepest first
+        std::vector<uint64_t> clade(direct, direct + nn + 1);           // [nn] = ROOT
+        std::vector<uint32_t> by_depth(nn);
+        for (uint64_t x = 0; x < nn; ++x) by_depth[x] = (uint32_t)x;
+        std::stable_sort(by_depth.begin(), by_depth.end(), [&](uint32_t a, uint32_t b) { return lv.depth[a] > lv.depth[b]; });
+        for (uint32_t x : by_depth) clade[lv.parent[x] < 0 ? nn : (uint64_t)lv.parent[x]] += clade[x];
+        const uint64_t total = clade[nn] + direct[nn + 1];
+        // children of every node (ROOT at nn), in the order they are printed; node numbers ascend with the id strings
+        std::vector<uint64_t> child_off(nn + 2, 0);
+        for (uint64_t x = 0; x < nn; ++x)
+            if (clade[x]) ++child_off[(lv.parent[x] < 0 ? nn : (uint64_t)lv.parent[x]) + 1];
+        for (uint64_t x = 0; x <= nn; ++x) child_off[x + 1] += child_off[x];
+        std::vector<uint32_t> child(child_off[nn + 1]);
+        {
+            std::vector<uint64_t> at(child_off.begin(), child_off.end() - 1);
+            for (uint64_t x = 0; x < nn; ++x)
+                if (clade[x]) child[at[lv.parent[x] < 0 ? nn : (uint64_t)lv.parent[x]]++] = (uint32_t)x;
+        }
+        for (uint64_t x = 0; x <= nn; ++x)
+            std::stable_sort(child.begin() + (std::ptrdiff_t)child_off[x], child.begin() + (std::ptrdiff_t)child_off[x + 1], [&](uint32_t a, uint32_t b) { return clade[a] > clade[b]; });
+        auto rank_code = [](char r) { switch (r) { case 'k': return 'D'; case 'p': return 'P'; case 'c': return 'C'; case 'o': return 'O'; case 'f': return 'F'; case 'g': return 'G'; case 's': return 'S'; default: return '-'; } };
+        if (total) {
+            if (direct[nn + 1]) fprintf(f, "%6.2f\t%llu\t%llu\tU\t0\tunclassified\n", 100.0 * (double)direct[nn + 1] / (double)total, (unsigned long long)direct[nn + 1], (unsigned long long)direct[nn + 1]);
+            if (clade[nn]) {
+                fprintf(f, "%6.2f\t%llu\t%llu\tR\t1\troot\n", 100.0 * (double)clade[nn] / (double)total, (unsigned long long)clade[nn], (unsigned long long)direct[nn]);
+                std::vector<std::pair<uint64_t, uint64_t>> stack;      // (node, next child) -- depth-first without recursion
+                stack.emplace_back(nn, child_off[nn]);
+                while (!stack.empty()) {
+                    auto &top = stack.back();
+                    if (top.second == child_off[top.first + 1]) { stack.pop_back(); continue; }
+                    const uint32_t x = child[top.second++];
+                    fprintf(f, "%6.2f\t%llu\t%llu\t%c\t%s\t%*s%s\n", 100.0 * (double)clade[x] / (double)total, (unsigned long long)clade[x], (unsigned long long)direct[x],
+                            rank_code(lv.rank[x]), lv.id[x], (int)(2 * lv.depth[x]), "", lv.name[x]);
+                    stack.emplace_back(x, child_off[x]);
+                }
+            }
+        }
+        if (ferror(f) || fclose(f) != 0) die("cannot write to " + cfg.kraken_file + ": " + strerror(errno));
+    }
+    if (tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] lca: %llu nodes, %llu reads called, %llu of them unclassified; %.3f s inside the accumulation (summed over workers), %.6f s in its kernel\n",
+                (unsigned long long)nn, (unsigned long long)lr.n_reads, (unsigned long long)lr.direct_reads[nn + 1], run.t_lca, lr.seconds_kernel);
+    taxor_gpu_lca_destroy(run.lca);
+    run.lca = nullptr;
+    taxor_lineage_free(run.lineage);
+    run.lineage = nullptr;
+}
+
 // ---- the devices: one index replica per device (reads are independent, taxor_search.cpp:214: the index is replicated,
 // batches are sharded), the searchers, and the workers that make GPU batches of the queued chunks.  Several devices (north star:
 // "reads sharded across the GPUs, per-read results gathered over RCCL/xGMI"): one communicator; the index crosses PCIe once and is
@@ -1188,6 +1334,28 @@ struct GpuStage {
         if (rc != TAXOR_OK) die(taxor_gpu_last_error());
         std::lock_guard<std::mutex> lk(run.stat_mu);
         run.t_coverage += now() - c0;
+    }
+    // --lca-file / --report-file: the batch's reads are called where its results lie on the device; the calls (and, without a TSV,
+    // QHASH_COUNT) go to the chunks
+    void add_lca(taxor_gpu_searcher *s, Chunks &group)
+    {
+        const double c0 = now();
+        uint64_t nr = 0;
+        for (auto &bt : group) nr += bt->ids.size();
+        taxor_lca_calls calls{};
+        if (taxor_gpu_lca_add_batch(run.lca, s, run.lca_next_read.fetch_add(nr), &calls) != TAXOR_OK) die(taxor_gpu_last_error());
+        if (calls.n_reads != nr) die("internal: a batch's calls do not cover its chunks");
+        uint64_t r0 = 0;
+        for (auto &bt : group) {
+            const uint64_t n = bt->ids.size();
+            bt->lca_node.assign(calls.node + r0, calls.node + r0 + n);
+            bt->lca_best.assign(calls.best + r0, calls.best + r0 + n);
+            bt->lca_refs.assign(calls.n_refs + r0, calls.n_refs + r0 + n);
+            if (!run.write_tsv) bt->n_hashes.assign(calls.n_hashes + r0, calls.n_hashes + r0 + n);
+            r0 += n;
+        }
+        std::lock_guard<std::mutex> lk(run.stat_mu);
+        run.t_lca += now() - c0;
     }
     // the CSR of several chunks classified as one batch -> each chunk's own CSR
     void split_results(Chunks &chunks, const taxor_gpu_results &res)
@@ -1406,6 +1574,7 @@ struct GpuStage {
             if (classify(sr[wi], group, scanned, run.write_tsv ? &res : nullptr) != TAXOR_OK) die(taxor_gpu_last_error());
             if (run.profile_mode) feed_profile(sr[wi], group);
             if (run.coverage) add_coverage(sr[wi]);
+            if (run.lca) add_lca(sr[wi], group);
             --n_running;
             const double t3 = now();
             if (run.write_tsv) split_results(group, res);
@@ -1494,6 +1663,7 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
     if (run.profile_mode) run.fused.begin(view, taxor_hixf_get_meta(h), run.prof.device);
     gpu.create_searchers(prm);
     if (!cfg.coverage_file.empty()) gpu.begin_coverage(view);
+    if (run.lineage && taxor_gpu_lca_create(gpu.gidx[0], run.lineage, &run.lca) != TAXOR_OK) die(taxor_gpu_last_error());
     gpu.run_workers();
     run.t_search_wall += now() - t_search0;
     if (run.coverage) {
@@ -1517,6 +1687,10 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
                 writer.t_last_write > writer.t_first_write ? writer.out_written.load() / 1e9 / (writer.t_last_write - writer.t_first_write) : 0.0, writer.t_write,
                 writer.t_write > 0 ? writer.out_written.load() / 1e9 / writer.t_write : 0.0);
     run.t_reads += *std::max_element(feed.reader_time.begin(), feed.reader_time.end());
+    if (run.lca) {
+        finish_lca(run);
+        trace("calls and report written");
+    }
     gpu.release();
     if (run.profile_mode) {
         run.fused.finish(run.prof, cfg.threads, run.t_search_wall);
@@ -1607,6 +1781,16 @@ void search_files(SearchRun &run, const std::string &hixf_file, const std::vecto
         if (budget)
             die("Validation failed for option --coverage-file: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
                 std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; accumulating pass by pass is not built.");
+    }
+    if (cfg.lca_mode()) {
+        // a read is called from its FINAL tuples, which a paged search has only after the last pass's merge
+        const std::string opt = !cfg.lca_file.empty() ? "--lca-file" : "--report-file";
+        if (budget && cfg.index_budget_mib && whole.index_bytes <= budget) budget = 0;
+        if (budget)
+            die("Validation failed for option " + opt + ": the index would be searched in resident passes (" + std::string(why) + "; it holds " +
+                std::to_string(whole.index_bytes >> 20) + " MiB), and a read's final tuples then exist only after the last pass's merge; calling reads there is not built.");
+        if (taxor_lineage_create(taxor_hixf_get_meta(h), view->n_user_bins, &run.lineage) != TAXOR_OK || taxor_lineage_get_view(run.lineage, &run.lineage_view) != TAXOR_OK)
+            die(std::string("Validation failed for option ") + opt + ": the index's taxonomy is not a tree: " + taxor_gpu_last_error());
     }
     if (budget) search_paged(run, h, view, prm, queries, budget, why, t0);
     else search_resident(run, h, view, prm, queries, last, t0);

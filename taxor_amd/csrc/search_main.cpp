@@ -105,6 +105,11 @@ int main(int argc, char **argv)
     run.out = run.write_tsv ? fopen(cfg.report_file.c_str(), "wb") : nullptr;  // search_hixf, :340-343
     if (run.write_tsv && !run.out) die("cannot open output file " + cfg.report_file);
     if (run.out) fputs("#QUERY_NAME\tACCESSION\tREFERENCE_NAME\tTAXID\tREF_LEN\tQUERY_LEN\tQHASH_COUNT\tQHASH_MATCH\tTAX_STR\tTAX_ID_STR\n", run.out);
+    if (!cfg.lca_file.empty()) {
+        run.lca_out = fopen(cfg.lca_file.c_str(), "wb");
+        if (!run.lca_out) die("cannot open call file " + cfg.lca_file);
+        fputs("#STATUS\tQUERY_NAME\tTAXID\tQUERY_LEN\tQHASH_COUNT\tBEST_QHASH_MATCH\tREFERENCES\n", run.lca_out);
+    }
     if (index_files.size() == 1) {
         search_files(run, index_files[0], query_files, true);
     } else {

@@ -717,6 +717,120 @@ class Coverage:
         self.close()
 
 
+class Lineage:
+    """The taxonomy of an index as a tree (taxor_lineage_*, host only; taxor_amd/csrc/lineage.h): built from a list of species dicts
+    {organism_name, accession_id, taxid, taxnames_string, taxid_string, user_bin, seq_len}, the form hixf_file.py uses.  Node numbers
+    are dense in byte-wise order of the id strings; parent -1 is ROOT."""
+
+    def __init__(self, species, n_user_bins):
+        L = _lib.lib()
+        sp = (_lib.Species * max(1, len(species)))()
+        for i, x in enumerate(species):
+            sp[i] = _lib.Species(x["organism_name"].encode(), x["accession_id"].encode(), x["taxid"].encode(), x["taxnames_string"].encode(),
+                                 x["taxid_string"].encode(), x["user_bin"], x["seq_len"])
+        meta = _lib.HixfMeta(0, 1, 0, len(species), sp, 0, None)
+        self._h = C.c_void_p()
+        check(L.taxor_lineage_create(C.byref(meta), int(n_user_bins), C.byref(self._h)))
+        v = _lib.LineageView()
+        check(L.taxor_lineage_get_view(self._h, C.byref(v)))
+        nb, nn = int(v.n_user_bins), int(v.n_nodes)
+        arr = lambda ptr, m, dt: np.ctypeslib.as_array(ptr, shape=(m,)).copy() if m else np.zeros(0, dt)
+        self.n_user_bins, self.n_nodes, self.max_depth = nb, nn, int(v.max_depth)
+        self.bin_species = arr(v.bin_species, nb, np.uint32)
+        self.path_off = np.ctypeslib.as_array(v.path_off, shape=(nb + 1,)).copy()
+        self.path = arr(v.path, int(self.path_off[nb]), np.int32)
+        self.parent = arr(v.parent, nn, np.int32)
+        self.depth = arr(v.depth, nn, np.uint32)
+        self.ids = [v.id[i].decode("utf-8", "replace") for i in range(nn)]
+        self.names = [v.name[i].decode("utf-8", "replace") for i in range(nn)]
+        self.ranks = [v.rank[i].decode("latin-1") for i in range(nn)]
+
+    def path_of(self, b):
+        return [int(x) for x in self.path[int(self.path_off[b]):int(self.path_off[b + 1])]]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().taxor_lineage_free(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+
+@dataclass
+class LcaCalls:
+    """per read of one add: node (a node number, _lib.LCA_ROOT or _lib.LCA_UNCLASSIFIED), the maximum count, the surviving tuples, and
+    (add_batch only) QHASH_COUNT"""
+    first_read: int
+    node: np.ndarray        # int32[n_reads]
+    best: np.ndarray        # uint32[n_reads]
+    n_refs: np.ndarray      # uint32[n_reads]
+    n_hashes: np.ndarray    # uint32[n_reads] or None
+
+
+@dataclass
+class LcaTallies:
+    """Lca.results(): per node, then ROOT at [n_nodes] and UNCLASSIFIED at [n_nodes + 1]"""
+    n_nodes: int
+    direct_reads: np.ndarray   # uint64[n_nodes + 2]
+    direct_bases: np.ndarray   # uint64[n_nodes + 2]
+    n_reads: int
+    seconds_kernel: float
+
+
+class Lca:
+    """Per-read lowest common ancestor and per-taxon tallies over a whole run (taxor_amd/csrc/lca.hip).  add_batch follows a batch on
+    a Searcher of the same index; add_csr takes host arrays."""
+
+    def __init__(self, index: GpuIndex, lineage: Lineage):
+        self._L = _lib.lib()
+        self._h = C.c_void_p()
+        self.index, self.lineage = index, lineage
+        check(self._L.taxor_gpu_lca_create(index._h, lineage._h, C.byref(self._h)))
+
+    @staticmethod
+    def _calls(c):
+        n = int(c.n_reads)
+        arr = lambda ptr, dt: np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return LcaCalls(int(c.first_read), arr(c.node, np.int32), arr(c.best, np.uint32), arr(c.n_refs, np.uint32),
+                        arr(c.n_hashes, np.uint32) if c.n_hashes else None)
+
+    def add_batch(self, searcher: Searcher, first_read=0) -> LcaCalls:
+        c = _lib.LcaCalls()
+        check(self._L.taxor_gpu_lca_add_batch(self._h, searcher._h, int(first_read), C.byref(c)))
+        return self._calls(c)
+
+    def add_csr(self, read_off, user_bin, count, query_len) -> LcaCalls:
+        ro = np.ascontiguousarray(read_off, dtype=np.uint64)
+        ub = np.ascontiguousarray(user_bin, dtype=np.int64)
+        ct = np.ascontiguousarray(count, dtype=np.uint32)
+        ql = np.ascontiguousarray(query_len, dtype=np.uint64)
+        assert ro.size >= 1 and ql.size == ro.size - 1 and ub.size == ct.size and int(ro[-1]) <= ub.size
+        c = _lib.LcaCalls()
+        check(self._L.taxor_gpu_lca_add_csr(self._h, ro.size - 1, _p(ro), _p(ub) if ub.size else None, _p(ct) if ct.size else None,
+                                            _p(ql) if ql.size else None, C.byref(c)))
+        return self._calls(c)
+
+    def results(self) -> LcaTallies:
+        res = _lib.LcaResults()
+        check(self._L.taxor_gpu_lca_results(self._h, C.byref(res)))
+        n = int(res.n_nodes)
+        return LcaTallies(n, np.ctypeslib.as_array(res.direct_reads, shape=(n + 2,)).copy(), np.ctypeslib.as_array(res.direct_bases, shape=(n + 2,)).copy(),
+                          int(res.n_reads), float(res.seconds_kernel))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.taxor_gpu_lca_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Comm:
     """Several GPUs of one node driven by this one process (the C++ host's `taxor search --gpus N` shape): the index is
     replicated (one upload + ncclBroadcast), every device classifies its own batch, results are gathered on devices[0].
