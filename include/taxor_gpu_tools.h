@@ -723,6 +723,47 @@ int taxor_gpu_lca_add_csr(taxor_gpu_lca *lca, uint64_t n_reads, const uint64_t *
 int taxor_gpu_lca_results(taxor_gpu_lca *lca, taxor_lca_results *out);
 void taxor_gpu_lca_destroy(taxor_gpu_lca *lca);
 
+/* ---- where along a read each reference matched (`taxor search --hitmap-file`; taxor_amd/csrc/hitmap.hip and hitmap_format.h, DESIGN.md
+ * section 10.4).  The TSV gives a (read, reference) pair ONE number; a chimeric read, a prophage inside a chromosome read and a read
+ * that matches a genome through one conserved operon look alike in it.  The hit map says in which part of the read the hits lie.
+ * For read r: n = its saved hash count (the searcher's QHASH_COUNT), T its tuples, m the maximum count over T.  A tuple SURVIVES when
+ * !((double)count < (double)m * 0.8), fp64 as written (taxor_classify_filter's expression); a survivor is MAPPED when n > 0 -- a read
+ * without a hash reports every leaf with count 0 and the TSV prints those lines, but there is nothing to locate.  Mapped tuples keep the
+ * CSR's order, the order of the TSV's lines.
+ * Hash i of the read is the i-th entry of its saved list, from 0: the lists are kept in first-insertion order, the order of first
+ * occurrence along the read.  It lies in segment seg(i) = floor(i * S / n), 64-bit; segment j holds ceil((j+1) * n / S) - ceil(j * n / S)
+ * hashes, none for some j when n < S.  Segments cut the ORDERED HASH LIST, not the bases: a hash list carries no positions.
+ * Hash h MATCHES user bin b when the three fingerprints of IXF x at h's rows in column j xor to h's fingerprint -- under the index's
+ * arithmetic code and x's seed -- for at least one leaf technical bin (x, j) of b: every bin with fname_idx == b anywhere in the
+ * hierarchy, root included (the leaf bins of the coverage accumulator).  hits[t * S + j] = the hashes of segment j that match the user
+ * bin of mapped tuple t.  The sum over j may differ from the tuple's count: the search counts per technical bin and adds the parts of a
+ * split user bin, a hash found in two parts is one hit here; for a user bin with one leaf technical bin the two are equal.
+ * _create: segments S in [1, 64]; `view` is the one the index was created from (only bins and fname_idx are read).  TAXOR_E_ARG naming
+ * the reason: segments outside the range; a paged index, by name (its leaf bins are not all resident).
+ * _add_batch: after taxor_gpu_search_batch_end (or _batch_sync) of a batch that ran with capture on, with that batch's saved lists
+ * (taxor_gpu_search_take_saved, which stay the caller's), before the next batch on the searcher.  Checked before any launch,
+ * TAXOR_E_ARG naming the field: the saved batch is sound, its n_reads is the searcher's, its n_hashes are the searcher's, the searcher's
+ * index is the hit map's.  The searcher's device-resident CSR is read where it lies; only the lists of reads that have a mapped tuple
+ * are staged, through a bounded device buffer.  The result lies in page-locked host memory kept per searcher: valid until the next
+ * _add_batch on THAT searcher (or _destroy).  Calls may come from several threads.  hits are integer sums: they do not depend on the
+ * launch geometry nor on how reads are cut into pieces, staged groups and batches. */
+typedef struct taxor_gpu_hitmap taxor_gpu_hitmap;
+typedef struct {
+    uint64_t n_reads, n_mapped;
+    uint32_t segments, reserved;
+    const uint64_t *map_off;       /* [n_reads + 1] read r's mapped tuples are [map_off[r], map_off[r + 1]) of the arrays below */
+    const uint64_t *tuple;         /* [n_mapped] the tuple's index in the batch CSR (user_bin / count of taxor_gpu_results) */
+    const int64_t *user_bin;       /* [n_mapped] */
+    const uint32_t *count;         /* [n_mapped] QHASH_MATCH */
+    const uint32_t *hits;          /* [n_mapped * segments] */
+    const uint32_t *n_hashes;      /* [n_reads] QHASH_COUNT */
+    double seconds_kernels;        /* HIP-event time of this call's kernels */
+    uint64_t probes;               /* (hash, leaf bin) lookups made by this call: three one-byte gathers each */
+} taxor_hitmap_batch;
+int taxor_gpu_hitmap_create(taxor_gpu_index *idx, const taxor_hixf_view *view, uint32_t segments, taxor_gpu_hitmap **out);
+int taxor_gpu_hitmap_add_batch(taxor_gpu_hitmap *hm, taxor_gpu_searcher *s, const taxor_gpu_saved *saved, taxor_hitmap_batch *out);
+void taxor_gpu_hitmap_destroy(taxor_gpu_hitmap *hm);
+
 /* ---- search straight from file bytes (taxor_amd/csrc/fastx_scan.hip): raw[0, n_bytes) holds whole records of one
  * kind, '>' (FASTA) or '@' (four-line FASTQ) -- what a reader cuts at record boundaries.  The device finds the records, packs their
  * sequences into the searcher's batch and runs the search; taxor_gpu_search_batch_end follows as after any _begin.  raw may be pageable

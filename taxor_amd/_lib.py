@@ -216,6 +216,13 @@ class LcaResults(C.Structure):
                 ("n_reads", C.c_uint64), ("seconds_kernel", C.c_double)]
 
 
+class HitmapBatch(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_mapped", C.c_uint64), ("segments", C.c_uint32), ("reserved", C.c_uint32),
+                ("map_off", C.POINTER(C.c_uint64)), ("tuple", C.POINTER(C.c_uint64)), ("user_bin", C.POINTER(C.c_int64)),
+                ("count", C.POINTER(C.c_uint32)), ("hits", C.POINTER(C.c_uint32)), ("n_hashes", C.POINTER(C.c_uint32)),
+                ("seconds_kernels", C.c_double), ("probes", C.c_uint64)]
+
+
 SIGNATURES = {
     "taxor_gpu_last_error": (C.c_char_p, []),
     "taxor_gpu_index_create": (C.c_int, [C.POINTER(HixfView), C.c_int, C.POINTER(_P)]),
@@ -272,6 +279,9 @@ SIGNATURES = {
     "taxor_gpu_lca_add_csr": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, C.POINTER(LcaCalls)]),
     "taxor_gpu_lca_results": (C.c_int, [_P, C.POINTER(LcaResults)]),
     "taxor_gpu_lca_destroy": (None, [_P]),
+    "taxor_gpu_hitmap_create": (C.c_int, [_P, C.POINTER(HixfView), C.c_uint32, C.POINTER(_P)]),
+    "taxor_gpu_hitmap_add_batch": (C.c_int, [_P, _P, _P, C.POINTER(HitmapBatch)]),
+    "taxor_gpu_hitmap_destroy": (None, [_P]),
     "taxor_hll_estimate": (C.c_double, [_P, C.c_uint32]),
     "taxor_hll_slot": (None, [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
     "taxor_gpu_device_memory": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -145,6 +145,11 @@ struct Batch {
     // --lca-file / --report-file: the reads' calls copied out of the accumulator (lca.hip); n_hashes above comes with them when no TSV is written
     std::vector<int32_t> lca_node;
     std::vector<uint32_t> lca_best, lca_refs;
+    // --hitmap-file: the chunk's share of the batch's hit maps (hitmap.hip): read r's mapped tuples are [hm_off[r], hm_off[r + 1]) of
+    // hm_user_bin / hm_count, tuple t's counters hm_hits[t * S .. (t + 1) * S); n_hashes above comes with them when no TSV is written
+    std::vector<uint64_t> hm_off;
+    std::vector<int64_t> hm_user_bin;
+    std::vector<uint32_t> hm_count, hm_hits;
     // --device-parse: the chunk is a byte range of the file as read (whole records of kind raw_kind, '>' or '@'); the device finds
     // the records, ids and offsets are filled from its table and bases stays empty.  raw_kind 0: a parsed chunk, as above
     BaseBuf raw;

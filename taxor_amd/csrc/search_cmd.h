@@ -22,6 +22,8 @@ struct Config : ReaderOptions {              // taxor_search_configuration.hpp:8
     std::string kraken_file;    // --report-file: Kraken-style clade report of the whole run
     std::string report_unit;    // --report-unit reads | bases (empty: reads): which tally fills the report's first three columns
     bool lca_mode() const { return !lca_file.empty() || !kraken_file.empty(); }
+    std::string hitmap_file;    // --hitmap-file: one line per (read, reference) line of the TSV, the hits along the read's hash list (hitmap.hip)
+    uint32_t hitmap_segments = 0;      // hidden --hitmap-segments: parts the ordered hash list is cut into, in [1,64] (0: 16)
     std::string gather;         // several devices: "rccl" | "host" (taxor_gpu_comm transports) | "none" (independent workers, each
                                 // fetching its own results); empty = rccl when the devices are distinct, host when one repeats
 };
@@ -65,6 +67,9 @@ void usage()
             "                           matched, its length, hash count, best match and the number of references  } ONE index file, ONE\n"
             "  --report-file <f>        Kraken-style report: per taxon the reads of its clade and its own            } device; --output-file\n"
             "  --report-unit <reads|bases> what --report-file counts (default reads)                                } is then optional\n"
+            "  --hitmap-file <f>        per line of --output-file that a read with hashes produced: in which sixteenth of the read's ordered hash\n"
+            "                           list the reference's hits lie (a chimeric read, an inserted element, one conserved operon); ONE index\n"
+            "                           file, ONE device; --output-file is then optional\n"
             "  --expect <tsv>           compare the output per read with a TSV the reference wrote for the same input (exit 3 if it differs)\n"
             "search to profile in one run (the options of `taxor profile`; results go from the device's search buffers into the profile's\n"
             "device pipeline, no TSV is written or parsed in between):\n"
@@ -120,6 +125,19 @@ void advanced_help()
                     "                           root, depth-first, children by clade count descending and taxid ascending; empty clades are left out.\n"
                     "                           Both options: a comma list of index files, several devices, a --gather transport and an index that has\n"
                     "                           to be paged are refused; without --output-file the per-read tuples never leave the device.\n"
+                    "  --hitmap-file <f>        columns QUERY_NAME, ACCESSION, TAXID, QUERY_LEN, QHASH_COUNT, QHASH_MATCH, LOCATED, SEGMENT_SIZES, SEGMENT_HITS; one\n"
+                    "                           line per line of --output-file (the tuples that survive the 0.8 * max filter), in its order, except the\n"
+                    "                           lines of a read without a hash (QHASH_COUNT 0: nothing to locate).  The read's hashes are kept in the order\n"
+                    "                           of their first occurrence along the read; hash i of n lies in segment floor(i * S / n), and segment j\n"
+                    "                           holds ceil((j+1) * n / S) - ceil(j * n / S) of them (SEGMENT_SIZES; zeros where n < S).  The segments cut\n"
+                    "                           the ORDERED HASH LIST, not the bases: a hash list carries no positions, so a segment is a stretch of the\n"
+                    "                           read only as far as its hashes are spread evenly.  SEGMENT_HITS: per segment the hashes found in at least\n"
+                    "                           one of the reference's own leaf bins; LOCATED is their sum (QHASH_MATCH for a reference stored in one bin;\n"
+                    "                           a reference split over several bins counts a hash once here and once per part there).  Both last columns\n"
+                    "                           are comma lists of S numbers.  The searchers keep every batch's hash lists in host memory until the batch\n"
+                    "                           is located.  Refused: a comma list of index files, several devices, a --gather transport, and an index\n"
+                    "                           that has to be paged.\n"
+                    "  --hitmap-segments <S>    with --hitmap-file: the number of segments, in [1,64] (default 16).\n"
                     "  --paged-reread           the default said aloud: read the query file again in every pass; wins over --paged-replay.\n"
                     "BAM input: the BGZF blocks are inflated on --threads threads, one thread walks the records (block_size, flag, l_seq, read_name)\n"
                     "                           and copies the 4-bit SEQ fields into a page-locked buffer; CIGAR, QUAL and tags are never read.  A\n"
@@ -391,6 +409,11 @@ struct SearchRun {
     taxor_lineage *lineage = nullptr;         // --lca-file / --report-file: the index's taxonomy as a tree (lineage.h) ...
     taxor_gpu_lca *lca = nullptr;             // ... and the accumulator beside the resident index, for the whole run (lca.hip)
     FILE *lca_out = nullptr;                  // --lca-file; written by the sequencer, which sees the chunks in input order
+    taxor_gpu_hitmap *hitmap = nullptr;       // --hitmap-file: the hit map beside the resident index, for the whole run (hitmap.hip)
+    FILE *hitmap_out = nullptr;               // --hitmap-file; written by the sequencer as well
+    std::vector<uint32_t> hitmap_species;     // user bin -> the species the TSV names for it
+    double t_hitmap = 0, t_hitmap_kernels = 0;   // seconds inside taxor_gpu_hitmap_add_batch and in its kernels, summed over workers
+    uint64_t hitmap_probes = 0, hitmap_lines = 0;
     std::atomic<uint64_t> lca_next_read{0};   // the next batch's first read as the accumulator numbers it
     double t_lca = 0;               // seconds inside taxor_gpu_lca_add_batch, summed over workers
     double t_coverage = 0;          // seconds inside taxor_gpu_coverage_add_batch (taking and freeing the saved lists included), summed over workers
@@ -477,6 +500,15 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             cfg.lca_file = val();
             if (cfg.lca_file.empty()) die("Validation failed for option --lca-file: the file name is empty.");
         }
+        else if (k == "--hitmap-file") {
+            cfg.hitmap_file = val();
+            if (cfg.hitmap_file.empty()) die("Validation failed for option --hitmap-file: the file name is empty.");
+        }
+        else if (k == "--hitmap-segments") {
+            const long n = (long)num(val(), true);
+            if (n < 1 || n > 64) die("Validation failed for option --hitmap-segments: Value not in range [1,64].");
+            cfg.hitmap_segments = (uint32_t)n;
+        }
         else if (k == "--report-file") {
             cfg.kraken_file = val();
             if (cfg.kraken_file.empty()) die("Validation failed for option --report-file: the file name is empty.");
@@ -545,7 +577,18 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             die("Validation failed for option --gather: " + opt + " runs on ONE device, where nothing is gathered; leave --gather out.");
         if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
     }
-    run.write_tsv = !(run.profile_mode || cfg.lca_mode()) || !cfg.report_file.empty();
+    if (cfg.hitmap_segments && cfg.hitmap_file.empty()) die("Option --hitmap-segments cuts the hash lists of --hitmap-file: it needs that option.");
+    if (!cfg.hitmap_file.empty()) {   // before any HIP call
+        if (cfg.index_file.find(',') != std::string::npos)
+            die("Validation failed for option --index-file: --hitmap-file takes ONE index file (a reference's hits are looked up in the leaf bins of the index it belongs to); "
+                "search the indexes one by one.");
+        if (cfg.gpus.size() > 1)
+            die("Validation failed for option " + run.gpus_option + ": --hitmap-file locates on ONE device (a batch's hash lists and its results must lie on the same one); give --gpu <id>.");
+        if (!cfg.gather.empty() && cfg.gather != "none")
+            die("Validation failed for option --gather: --hitmap-file runs on ONE device, where nothing is gathered; leave --gather out.");
+        if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
+    }
+    run.write_tsv = !(run.profile_mode || cfg.lca_mode() || !cfg.hitmap_file.empty()) || !cfg.report_file.empty();
     if (cfg.threads == 0) {
         // --threads not given.  The reference's default is one worker thread (taxor_search_configuration.hpp:17) -- there the
         // thread that classifies; here host threads only parse the query file and render text for the GPU, and one of them
@@ -1013,6 +1056,7 @@ struct ReportWriter {
                 const size_t n = bt.ids.size();
                 if (run.profile_mode) run.fused.take_ids(bt);            // chunks pass here in input order
                 if (run.lca_out) write_lca_lines(bt);
+                if (run.hitmap_out) write_hitmap_lines(bt);
                 if (n == 0 || !run.write_tsv) { chunk_done(hd); continue; }
                 // cut where the estimated text passes piece_bytes
                 const uint64_t per_tuple = line_bytes_guess.load();
@@ -1054,6 +1098,27 @@ struct ReportWriter {
         }
         if (!lca_text.empty() && fwrite(lca_text.data(), 1, lca_text.size(), run.lca_out) != lca_text.size())
             die("cannot write to " + run.cfg.lca_file + ": " + strerror(errno));
+    }
+    // --hitmap-file: the chunk's mapped tuples, one line each, by the sequencer (hitmap_format.h)
+    std::string hitmap_text;
+    void write_hitmap_lines(const Batch &bt)
+    {
+        const size_t n = bt.ids.size();
+        const uint32_t S = run.cfg.hitmap_segments ? run.cfg.hitmap_segments : taxor::HITMAP_DEFAULT_SEGMENTS;
+        if (bt.hm_off.size() != n + 1 || bt.n_hashes.size() != n || bt.hm_hits.size() != bt.hm_count.size() * S)
+            die("internal: a chunk reached the writer without its reads' hit maps");
+        const taxor_hixf_meta *meta = taxor_hixf_get_meta(h);
+        hitmap_text.clear();
+        for (size_t r = 0; r < n; ++r)
+            for (uint64_t t = bt.hm_off[r]; t < bt.hm_off[r + 1]; ++t) {
+                const uint64_t b = (uint64_t)bt.hm_user_bin[t];
+                const taxor_species *sp = meta->n_species ? &meta->species[b < run.hitmap_species.size() ? run.hitmap_species[b] : 0] : nullptr;
+                taxor::hitmap_line(hitmap_text, bt.ids.ptr(r), bt.ids.len(r), sp ? sp->accession_id : nullptr, sp ? sp->taxid : nullptr, bt.offsets[r + 1] - bt.offsets[r],
+                                   bt.n_hashes[r], bt.hm_count[t], bt.hm_hits.data() + t * S, S);
+            }
+        run.hitmap_lines += bt.hm_count.size();
+        if (!hitmap_text.empty() && fwrite(hitmap_text.data(), 1, hitmap_text.size(), run.hitmap_out) != hitmap_text.size())
+            die("cannot write to " + run.cfg.hitmap_file + ": " + strerror(errno));
     }
     // a piece's text goes to the file when its ticket comes up
     void write_in_turn(const Piece &pc, const char *text, uint64_t need)
@@ -1183,6 +1248,23 @@ void write_coverage_file(SearchRun &run, const taxor_hixf_meta *meta)
                 cr.seconds_kernels > 0 ? 3.0 * cr.probes / cr.seconds_kernels / 1e9 : 0.0, cr.seconds_kernels > 0 ? 3.0 * 128.0 * cr.probes / cr.seconds_kernels / 1e9 : 0.0);
     taxor_gpu_coverage_destroy(run.coverage);
     run.coverage = nullptr;
+}
+
+// ---- `--hitmap-file`: the lines were written chunk by chunk; the file is closed here
+void finish_hitmap(SearchRun &run)
+{
+    if (run.hitmap_out) {
+        if (ferror(run.hitmap_out) || fclose(run.hitmap_out) != 0) die("cannot write to " + run.cfg.hitmap_file + ": " + strerror(errno));
+        run.hitmap_out = nullptr;
+    }
+    if (tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] hitmap: %llu lines; %.3f s inside the locating (summed over workers), %.3f s in its kernels, "
+                        "%llu lookups of a hash in a leaf bin = %.2f G gathers/s, %.1f GB/s of 128-B lines\n",
+                (unsigned long long)run.hitmap_lines, run.t_hitmap, run.t_hitmap_kernels, (unsigned long long)run.hitmap_probes,
+                run.t_hitmap_kernels > 0 ? 3.0 * run.hitmap_probes / run.t_hitmap_kernels / 1e9 : 0.0,
+                run.t_hitmap_kernels > 0 ? 3.0 * 128.0 * run.hitmap_probes / run.t_hitmap_kernels / 1e9 : 0.0);
+    taxor_gpu_hitmap_destroy(run.hitmap);
+    run.hitmap = nullptr;
 }
 
 // ---- `--report-file`: the run's tallies, fetched once, rolled up the tree on the host (a few hundred thousand nodes at most, once per
@@ -1315,25 +1397,61 @@ struct GpuStage {
             for (unsigned w = 0; w < wpg; ++w)
                 if (taxor_gpu_searcher_create(gidx[g], &prm, &sr[g * wpg + w]) != TAXOR_OK) die(taxor_gpu_last_error());
     }
-    // --coverage-file: the accumulator beside the (one) index, and every searcher leaves its batches' hash lists for it
-    void begin_coverage(const taxor_hixf_view *view)
+    // --coverage-file / --hitmap-file: the consumers beside the (one) index, and every searcher leaves its batches' hash lists for them
+    void begin_saved_consumers(const taxor_hixf_view *view, const taxor_hixf_meta *meta)
     {
-        if (taxor_gpu_coverage_create(gidx[0], view, run.cfg.coverage_precision, &run.coverage) != TAXOR_OK) die(taxor_gpu_last_error());
+        const Config &cfg = run.cfg;
+        if (!cfg.coverage_file.empty() && taxor_gpu_coverage_create(gidx[0], view, cfg.coverage_precision, &run.coverage) != TAXOR_OK) die(taxor_gpu_last_error());
+        if (!cfg.hitmap_file.empty()) {
+            if (taxor_gpu_hitmap_create(gidx[0], view, cfg.hitmap_segments ? cfg.hitmap_segments : taxor::HITMAP_DEFAULT_SEGMENTS, &run.hitmap) != TAXOR_OK) die(taxor_gpu_last_error());
+            // the species of a user bin as the TSV names it (the first that carries it, species[0] if none: taxor_search.cpp:172-178,289)
+            run.hitmap_species.assign(view->n_user_bins, 0u);
+            for (uint64_t i = meta->n_species; i-- > 0;)
+                if (meta->species[i].user_bin < view->n_user_bins) run.hitmap_species[meta->species[i].user_bin] = (uint32_t)i;
+        }
         for (auto *s : sr)
             if (taxor_gpu_search_capture(s, 1) != TAXOR_OK) die(taxor_gpu_last_error());
     }
-    // after a batch's end: its saved lists are taken, accumulated and freed -- none is kept across batches, so host memory stays
-    // bounded by the batches in flight
-    void add_coverage(taxor_gpu_searcher *s)
+    // after a batch's end: its saved lists are taken ONCE, used by the consumers that are on and freed -- none is kept across batches,
+    // so host memory stays bounded by the batches in flight.  The hit map's share goes to each chunk of the batch
+    void use_saved(taxor_gpu_searcher *s, Chunks &group)
     {
         const double c0 = now();
         taxor_gpu_saved *sv = nullptr;
         if (taxor_gpu_search_take_saved(s, &sv) != TAXOR_OK) die(taxor_gpu_last_error());
-        const int rc = taxor_gpu_coverage_add_batch(run.coverage, s, sv);
+        const double c1 = now();
+        int rc = run.coverage ? taxor_gpu_coverage_add_batch(run.coverage, s, sv) : TAXOR_OK;
+        const double c2 = now();
+        taxor_hitmap_batch hb{};
+        if (rc == TAXOR_OK && run.hitmap) rc = taxor_gpu_hitmap_add_batch(run.hitmap, s, sv, &hb);
+        if (rc == TAXOR_OK && run.hitmap) {
+            uint64_t nr = 0;
+            for (auto &bt : group) nr += bt->ids.size();
+            if (hb.n_reads != nr) die("internal: a batch's hit maps do not cover its chunks");
+            const uint64_t S = hb.segments;
+            uint64_t r0 = 0;
+            for (auto &bt : group) {
+                const uint64_t n = bt->ids.size(), lo = hb.map_off[r0], hi = hb.map_off[r0 + n];
+                bt->hm_off.resize(n + 1);
+                for (uint64_t i = 0; i <= n; ++i) bt->hm_off[i] = hb.map_off[r0 + i] - lo;
+                bt->hm_user_bin.assign(hb.user_bin + lo, hb.user_bin + hi);
+                bt->hm_count.assign(hb.count + lo, hb.count + hi);
+                bt->hm_hits.assign(hb.hits + lo * S, hb.hits + hi * S);
+                if (!run.write_tsv) bt->n_hashes.assign(hb.n_hashes + r0, hb.n_hashes + r0 + n);
+                r0 += n;
+            }
+        }
+        const double c3 = now();
         taxor_gpu_saved_free(sv);
         if (rc != TAXOR_OK) die(taxor_gpu_last_error());
+        const double c4 = now(), shared = (c1 - c0) + (c4 - c3);        // taking and freeing the lists: the first consumer's
         std::lock_guard<std::mutex> lk(run.stat_mu);
-        run.t_coverage += now() - c0;
+        if (run.coverage) run.t_coverage += c2 - c1 + shared;
+        if (run.hitmap) {
+            run.t_hitmap += c3 - c2 + (run.coverage ? 0.0 : shared);
+            run.t_hitmap_kernels += hb.seconds_kernels;
+            run.hitmap_probes += hb.probes;
+        }
     }
     // --lca-file / --report-file: the batch's reads are called where its results lie on the device; the calls (and, without a TSV,
     // QHASH_COUNT) go to the chunks
@@ -1573,7 +1691,7 @@ struct GpuStage {
             // without a TSV nothing on the host reads the tuples: they stay on the device for the profile feed
             if (classify(sr[wi], group, scanned, run.write_tsv ? &res : nullptr) != TAXOR_OK) die(taxor_gpu_last_error());
             if (run.profile_mode) feed_profile(sr[wi], group);
-            if (run.coverage) add_coverage(sr[wi]);
+            if (run.coverage || run.hitmap) use_saved(sr[wi], group);
             if (run.lca) add_lca(sr[wi], group);
             --n_running;
             const double t3 = now();
@@ -1662,7 +1780,7 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
     const double t_search0 = now();
     if (run.profile_mode) run.fused.begin(view, taxor_hixf_get_meta(h), run.prof.device);
     gpu.create_searchers(prm);
-    if (!cfg.coverage_file.empty()) gpu.begin_coverage(view);
+    if (!cfg.coverage_file.empty() || !cfg.hitmap_file.empty()) gpu.begin_saved_consumers(view, taxor_hixf_get_meta(h));
     if (run.lineage && taxor_gpu_lca_create(gpu.gidx[0], run.lineage, &run.lca) != TAXOR_OK) die(taxor_gpu_last_error());
     gpu.run_workers();
     run.t_search_wall += now() - t_search0;
@@ -1690,6 +1808,10 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
     if (run.lca) {
         finish_lca(run);
         trace("calls and report written");
+    }
+    if (run.hitmap) {
+        finish_hitmap(run);
+        trace("hit maps written");
     }
     gpu.release();
     if (run.profile_mode) {
@@ -1781,6 +1903,13 @@ void search_files(SearchRun &run, const std::string &hixf_file, const std::vecto
         if (budget)
             die("Validation failed for option --coverage-file: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
                 std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; accumulating pass by pass is not built.");
+    }
+    if (!cfg.hitmap_file.empty()) {
+        // a reference's hits are looked up in ALL its leaf bins, and a read's final tuples exist only after the last pass's merge
+        if (budget && cfg.index_budget_mib && whole.index_bytes <= budget) budget = 0;
+        if (budget)
+            die("Validation failed for option --hitmap-file: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
+                std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; locating hits pass by pass is not built.");
     }
     if (cfg.lca_mode()) {
         // a read is called from its FINAL tuples, which a paged search has only after the last pass's merge

@@ -13,6 +13,7 @@
 #include "tuning.h"
 #include "ixf_arith.h"
 #include "ixf_layout.h"
+#include "hitmap_format.h"
 #include "key_store.h"
 using taxor::tune_env;
 extern char **environ;
@@ -109,6 +110,11 @@ int main(int argc, char **argv)
         run.lca_out = fopen(cfg.lca_file.c_str(), "wb");
         if (!run.lca_out) die("cannot open call file " + cfg.lca_file);
         fputs("#STATUS\tQUERY_NAME\tTAXID\tQUERY_LEN\tQHASH_COUNT\tBEST_QHASH_MATCH\tREFERENCES\n", run.lca_out);
+    }
+    if (!cfg.hitmap_file.empty()) {
+        run.hitmap_out = fopen(cfg.hitmap_file.c_str(), "wb");
+        if (!run.hitmap_out) die("cannot open hit map file " + cfg.hitmap_file);
+        fputs(taxor::hitmap_header(), run.hitmap_out);
     }
     if (index_files.size() == 1) {
         search_files(run, index_files[0], query_files, true);

@@ -831,6 +831,56 @@ class Lca:
         self.close()
 
 
+@dataclass
+class HitmapBatch:
+    """Hitmap.add_batch(): read r's mapped tuples are [map_off[r], map_off[r + 1]) of tuple / user_bin / count / hits"""
+    segments: int
+    map_off: np.ndarray     # uint64[n_reads + 1]
+    tuple: np.ndarray       # uint64[n_mapped] index in the batch CSR
+    user_bin: np.ndarray    # int64[n_mapped]
+    count: np.ndarray       # uint32[n_mapped]
+    hits: np.ndarray        # uint32[n_mapped, segments]
+    n_hashes: np.ndarray    # uint32[n_reads]
+    seconds_kernels: float
+    probes: int
+
+
+class Hitmap:
+    """Where along a read each reference matched (taxor_amd/csrc/hitmap.hip).  `ixfs` is the list the GpuIndex was made from (only bins
+    and fname_idx are read).  add_batch follows a batch that ran with Searcher.capture() on and takes its SavedBatch, which stays the
+    caller's; the arrays it returns are copies."""
+
+    def __init__(self, index: GpuIndex, ixfs, segments=16):
+        view, keep = GpuIndex._view([dict(f, data=None) for f in ixfs], index.n_user_bins, index.k, index.s, index.t, index.use_syncmer, 1,
+                                    index.window_size)
+        self._L = _lib.lib()
+        self._h = C.c_void_p()
+        self.index, self.segments = index, int(segments)
+        check(self._L.taxor_gpu_hitmap_create(index._h, C.byref(view), int(segments), C.byref(self._h)))
+        del keep
+
+    def add_batch(self, searcher: Searcher, saved: "SavedBatch") -> HitmapBatch:
+        b = _lib.HitmapBatch()
+        check(self._L.taxor_gpu_hitmap_add_batch(self._h, searcher._h, saved._h if saved is not None else None, C.byref(b)))
+        n, m, S = int(b.n_reads), int(b.n_mapped), int(b.segments)
+        arr = lambda ptr, k, dt: np.ctypeslib.as_array(ptr, shape=(k,)).copy() if k else np.zeros(0, dt)
+        return HitmapBatch(S, arr(b.map_off, n + 1, np.uint64), arr(b.tuple, m, np.uint64), arr(b.user_bin, m, np.int64), arr(b.count, m, np.uint32),
+                           arr(b.hits, m * S, np.uint32).reshape(m, S), arr(b.n_hashes, n, np.uint32), float(b.seconds_kernels), int(b.probes))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.taxor_gpu_hitmap_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Comm:
     """Several GPUs of one node driven by this one process (the C++ host's `taxor search --gpus N` shape): the index is
     replicated (one upload + ncclBroadcast), every device classifies its own batch, results are gathered on devices[0].
