@@ -764,6 +764,65 @@ int taxor_gpu_hitmap_create(taxor_gpu_index *idx, const taxor_hixf_view *view, u
 int taxor_gpu_hitmap_add_batch(taxor_gpu_hitmap *hm, taxor_gpu_searcher *s, const taxor_gpu_saved *saved, taxor_hitmap_batch *out);
 void taxor_gpu_hitmap_destroy(taxor_gpu_hitmap *hm);
 
+/* ---- how much of a read stands behind its LCA call, and the call a threshold on that leaves (`taxor search --lca-confidence`;
+ * taxor_amd/csrc/confidence.hip and confidence_format.h).  The call above comes from the survivors of the
+ * 0.8 * max filter alone: a read whose best reference holds 12 % of its hashes is called like one that matches at 95 %, and the
+ * QHASH_MATCH columns cannot be added up to tell them apart (a hash shared by two references, or found in two parts of a split user
+ * bin, counts twice there).
+ * For read r: n = its saved hash count (QHASH_COUNT), T = ALL its tuples in the batch CSR, m the maximum count.  The call above stands
+ * as defined there: the survivors are the tuples with !((double)count < (double)m * 0.8), P is the longest common prefix of the
+ * survivors' compacted paths, D = len(P), the LCA node is P[D-1], ROOT for D = 0.  T empty or m == 0: UNCLASSIFIED, and every word
+ * below is 0 for such a read.
+ * For a classified read: agree(t), for every tuple t of T, = the length of the common prefix of t's user bin's compacted path and P,
+ * in [0, D]; survivors have D.  Hash i (the i-th entry of the read's saved list) MATCHES tuple t when it matches t's user bin by the
+ * hit map's lookup above: at least one leaf technical bin of the user bin, under the index's arithmetic code and the IXF's seed.
+ * a(i) = the maximum of agree(t) over the tuples hash i matches, undefined if it matches none.  support[d], d = 0..D, = the number of
+ * hashes i with a(i) defined and a(i) >= d: a hash counts ONCE, however many references or parts of a split user bin it is found in;
+ * support is non-increasing in d; support[0] = the read's hashes found in any reported reference.
+ * Given C in [0, 1], depth d HOLDS when !((double)support[d] < C * (double)n), fp64 as written (the object is built with
+ * -ffp-contract=off).  The confident call is the deepest d <= D that holds: P[d-1], ROOT for d = 0; if not even d = 0 holds the read
+ * is UNCLASSIFIED.  C = 0 gives the call above for every read.  direct_reads / direct_bases are tallied at the confident node.
+ * _create: `view` is the one the index was created from (only bins and fname_idx are read).  TAXOR_E_ARG naming the reason: a
+ * `confidence` outside [0, 1] or NaN; a paged index, by name; a lineage whose n_user_bins is not the index's.
+ * _add_batch: after taxor_gpu_search_batch_end (or _batch_sync) of a batch that ran with capture on, with that batch's saved lists
+ * (which stay the caller's), before the next batch on the searcher.  Checked before any launch, TAXOR_E_ARG naming the field: the
+ * saved batch is sound, its n_reads is the searcher's, its n_hashes are the searcher's, the searcher's index is the object's.  The
+ * searcher's device-resident CSR is read where it lies, the read lengths from the batch's offsets; only the lists of classified reads
+ * are staged, through a bounded device buffer.  calls: page-locked host memory kept per searcher, valid until the next _add_batch on
+ * THAT searcher (or _destroy).
+ * _add_csr: the same over host arrays (tuples of read r at [read_off[r], read_off[r+1]) of user_bin / count; query_len[n_reads]; the
+ * read's hash list at [hash_off[r], hash_off[r+1]) of hashes); a `user_bin` outside the lineage is refused before any launch; valid
+ * until the next _add_csr.
+ * _add calls may come from several threads.  Every word is an integer sum or decided from integer sums: nothing depends on the launch
+ * geometry, on the cut into pieces, staged groups and batches, or on the order of the calls.
+ * _results: the tallies at the confident nodes, as taxor_gpu_lca_results gives them; seconds_kernel sums this object's kernels. */
+typedef struct taxor_gpu_confidence taxor_gpu_confidence;
+typedef struct {
+    uint64_t n_reads, first_read;
+    const int32_t *node;           /* [n_reads] the confident call: node number, TAXOR_LCA_ROOT or TAXOR_LCA_UNCLASSIFIED */
+    const uint32_t *depth;         /* [n_reads] its depth d (0 for ROOT and for an unclassified read) */
+    const int32_t *lca_node;       /* [n_reads] the call without a threshold */
+    const uint32_t *lca_depth;     /* [n_reads] D */
+    const uint32_t *support;       /* [n_reads] support[d] at the confident depth; support[0] for a read the threshold made unclassified */
+    const uint32_t *lca_support;   /* [n_reads] support[D] */
+    const uint32_t *any_support;   /* [n_reads] support[0] */
+    const uint32_t *best;          /* [n_reads] the read's maximum count, 0 for a read without an LCA */
+    const uint32_t *n_refs;        /* [n_reads] surviving tuples, 0 for a read without an LCA */
+    const uint32_t *n_hashes;      /* [n_reads] QHASH_COUNT (_add_csr: the lists' lengths) */
+    double seconds_kernels;        /* HIP-event time of this call's kernels */
+    uint64_t probes;               /* (hash, leaf bin) lookups made by this call: three one-byte gathers each */
+    uint64_t tuple_steps;          /* (64 hashes, tuple) steps that reached the lookup ... */
+    uint64_t tuple_steps_full;     /* ... of one per tuple per round of 64 hashes; loop iterations that only read a tuple's agree byte are in neither */
+} taxor_confidence_calls;
+int taxor_gpu_confidence_create(taxor_gpu_index *idx, const taxor_hixf_view *view, const taxor_lineage *lineage, double confidence,
+                                taxor_gpu_confidence **out);
+int taxor_gpu_confidence_add_batch(taxor_gpu_confidence *cf, taxor_gpu_searcher *s, const taxor_gpu_saved *saved, uint64_t first_read,
+                                   taxor_confidence_calls *calls);
+int taxor_gpu_confidence_add_csr(taxor_gpu_confidence *cf, uint64_t n_reads, const uint64_t *read_off, const int64_t *user_bin, const uint32_t *count,
+                                 const uint64_t *query_len, const uint64_t *hash_off, const uint64_t *hashes, taxor_confidence_calls *calls);
+int taxor_gpu_confidence_results(taxor_gpu_confidence *cf, taxor_lca_results *out);
+void taxor_gpu_confidence_destroy(taxor_gpu_confidence *cf);
+
 /* ---- search straight from file bytes (taxor_amd/csrc/fastx_scan.hip): raw[0, n_bytes) holds whole records of one
  * kind, '>' (FASTA) or '@' (four-line FASTQ) -- what a reader cuts at record boundaries.  The device finds the records, packs their
  * sequences into the searcher's batch and runs the search; taxor_gpu_search_batch_end follows as after any _begin.  raw may be pageable

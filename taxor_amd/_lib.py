@@ -216,6 +216,14 @@ class LcaResults(C.Structure):
                 ("n_reads", C.c_uint64), ("seconds_kernel", C.c_double)]
 
 
+class ConfidenceCalls(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("first_read", C.c_uint64), ("node", C.POINTER(C.c_int32)), ("depth", C.POINTER(C.c_uint32)),
+                ("lca_node", C.POINTER(C.c_int32)), ("lca_depth", C.POINTER(C.c_uint32)), ("support", C.POINTER(C.c_uint32)),
+                ("lca_support", C.POINTER(C.c_uint32)), ("any_support", C.POINTER(C.c_uint32)), ("best", C.POINTER(C.c_uint32)),
+                ("n_refs", C.POINTER(C.c_uint32)), ("n_hashes", C.POINTER(C.c_uint32)), ("seconds_kernels", C.c_double), ("probes", C.c_uint64),
+                ("tuple_steps", C.c_uint64), ("tuple_steps_full", C.c_uint64)]
+
+
 class HitmapBatch(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_mapped", C.c_uint64), ("segments", C.c_uint32), ("reserved", C.c_uint32),
                 ("map_off", C.POINTER(C.c_uint64)), ("tuple", C.POINTER(C.c_uint64)), ("user_bin", C.POINTER(C.c_int64)),
@@ -279,6 +287,11 @@ SIGNATURES = {
     "taxor_gpu_lca_add_csr": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, C.POINTER(LcaCalls)]),
     "taxor_gpu_lca_results": (C.c_int, [_P, C.POINTER(LcaResults)]),
     "taxor_gpu_lca_destroy": (None, [_P]),
+    "taxor_gpu_confidence_create": (C.c_int, [_P, C.POINTER(HixfView), _P, C.c_double, C.POINTER(_P)]),
+    "taxor_gpu_confidence_add_batch": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(ConfidenceCalls)]),
+    "taxor_gpu_confidence_add_csr": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, C.POINTER(ConfidenceCalls)]),
+    "taxor_gpu_confidence_results": (C.c_int, [_P, C.POINTER(LcaResults)]),
+    "taxor_gpu_confidence_destroy": (None, [_P]),
     "taxor_gpu_hitmap_create": (C.c_int, [_P, C.POINTER(HixfView), C.c_uint32, C.POINTER(_P)]),
     "taxor_gpu_hitmap_add_batch": (C.c_int, [_P, _P, _P, C.POINTER(HitmapBatch)]),
     "taxor_gpu_hitmap_destroy": (None, [_P]),

@@ -145,6 +145,10 @@ struct Batch {
     // --lca-file / --report-file: the reads' calls copied out of the accumulator (lca.hip); n_hashes above comes with them when no TSV is written
     std::vector<int32_t> lca_node;
     std::vector<uint32_t> lca_best, lca_refs;
+    // --lca-confidence: lca_node is the confident call then (confidence.hip); beside it the support behind it, the call without a
+    // threshold and the support behind that
+    std::vector<int32_t> cf_lca_node;
+    std::vector<uint32_t> cf_support, cf_lca_support;
     // --hitmap-file: the chunk's share of the batch's hit maps (hitmap.hip): read r's mapped tuples are [hm_off[r], hm_off[r + 1]) of
     // hm_user_bin / hm_count, tuple t's counters hm_hits[t * S .. (t + 1) * S); n_hashes above comes with them when no TSV is written
     std::vector<uint64_t> hm_off;

@@ -22,6 +22,8 @@ struct Config : ReaderOptions {              // taxor_search_configuration.hpp:8
     std::string kraken_file;    // --report-file: Kraken-style clade report of the whole run
     std::string report_unit;    // --report-unit reads | bases (empty: reads): which tally fills the report's first three columns
     bool lca_mode() const { return !lca_file.empty() || !kraken_file.empty(); }
+    double lca_confidence = -1.0;      // --lca-confidence: share of a read's hashes a call must have behind it, in [0,1] (below 0: not given; confidence.hip)
+    bool confidence_mode() const { return lca_confidence >= 0.0; }
     std::string hitmap_file;    // --hitmap-file: one line per (read, reference) line of the TSV, the hits along the read's hash list (hitmap.hip)
     uint32_t hitmap_segments = 0;      // hidden --hitmap-segments: parts the ordered hash list is cut into, in [1,64] (0: 16)
     std::string gather;         // several devices: "rccl" | "host" (taxor_gpu_comm transports) | "none" (independent workers, each
@@ -67,6 +69,8 @@ void usage()
             "                           matched, its length, hash count, best match and the number of references  } ONE index file, ONE\n"
             "  --report-file <f>        Kraken-style report: per taxon the reads of its clade and its own            } device; --output-file\n"
             "  --report-unit <reads|bases> what --report-file counts (default reads)                                } is then optional\n"
+            "  --lca-confidence <0..1>  with --lca-file / --report-file: a read is called at the deepest taxon of its call's lineage that this share\n"
+            "                           of its hashes supports, or not at all; the call file gains SUPPORT, LCA_TAXID, LCA_SUPPORT\n"
             "  --hitmap-file <f>        per line of --output-file that a read with hashes produced: in which sixteenth of the read's ordered hash\n"
             "                           list the reference's hits lie (a chimeric read, an inserted element, one conserved operon); ONE index\n"
             "                           file, ONE device; --output-file is then optional\n"
@@ -125,6 +129,17 @@ void advanced_help()
                     "                           root, depth-first, children by clade count descending and taxid ascending; empty clades are left out.\n"
                     "                           Both options: a comma list of index files, several devices, a --gather transport and an index that has\n"
                     "                           to be paged are refused; without --output-file the per-read tuples never leave the device.\n"
+                    "  --lca-confidence <C>     with --lca-file / --report-file.  A read's call above comes from the references within 0.8 of its best match\n"
+                    "                           alone, however few of the read's hashes they hold.  With the option every hash of the read is looked up in\n"
+                    "                           the leaf bins of EVERY reference the search reported for it (the survivors and the others); a hash stands\n"
+                    "                           behind depth d of the call's lineage when a reference that found it shares the lineage's first d taxa, and\n"
+                    "                           it counts once, however many references or parts of a split reference hold it.  The read is called at the\n"
+                    "                           deepest taxon, from the call upwards, with at least C * QHASH_COUNT hashes behind it; U (TAXID 0) if not\n"
+                    "                           even the root has them.  0 gives the calls above.  Both files come from these calls.  The call file gains\n"
+                    "                           three columns: SUPPORT (hashes behind the taxon printed; behind the root for a read the threshold made U,\n"
+                    "                           which keeps its real QHASH_COUNT, BEST_QHASH_MATCH and REFERENCES), LCA_TAXID (the call without a\n"
+                    "                           threshold) and LCA_SUPPORT (hashes behind that); a read that was U anyway prints zeros.  The searchers keep\n"
+                    "                           every batch's hash lists in host memory until the batch is called.  Refused like --lca-file.\n"
                     "  --hitmap-file <f>        columns QUERY_NAME, ACCESSION, TAXID, QUERY_LEN, QHASH_COUNT, QHASH_MATCH, LOCATED, SEGMENT_SIZES, SEGMENT_HITS; one\n"
                     "                           line per line of --output-file (the tuples that survive the 0.8 * max filter), in its order, except the\n"
                     "                           lines of a read without a hash (QHASH_COUNT 0: nothing to locate).  The read's hashes are kept in the order\n"
@@ -409,6 +424,9 @@ struct SearchRun {
     taxor_lineage *lineage = nullptr;         // --lca-file / --report-file: the index's taxonomy as a tree (lineage.h) ...
     taxor_gpu_lca *lca = nullptr;             // ... and the accumulator beside the resident index, for the whole run (lca.hip)
     FILE *lca_out = nullptr;                  // --lca-file; written by the sequencer, which sees the chunks in input order
+    taxor_gpu_confidence *confidence = nullptr;   // --lca-confidence: stands in for `lca` (confidence.hip); fed from the saved hash lists
+    double t_confidence = 0, t_confidence_kernels = 0;   // seconds inside taxor_gpu_confidence_add_batch and in its kernels, summed over workers
+    uint64_t confidence_probes = 0, confidence_steps = 0, confidence_steps_full = 0;
     taxor_gpu_hitmap *hitmap = nullptr;       // --hitmap-file: the hit map beside the resident index, for the whole run (hitmap.hip)
     FILE *hitmap_out = nullptr;               // --hitmap-file; written by the sequencer as well
     std::vector<uint32_t> hitmap_species;     // user bin -> the species the TSV names for it
@@ -500,6 +518,10 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             cfg.lca_file = val();
             if (cfg.lca_file.empty()) die("Validation failed for option --lca-file: the file name is empty.");
         }
+        else if (k == "--lca-confidence") {
+            cfg.lca_confidence = num(val(), false);
+            if (!taxor::confidence_valid(cfg.lca_confidence)) die("Validation failed for option --lca-confidence: Value not in range [0,1].");
+        }
         else if (k == "--hitmap-file") {
             cfg.hitmap_file = val();
             if (cfg.hitmap_file.empty()) die("Validation failed for option --hitmap-file: the file name is empty.");
@@ -566,6 +588,16 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             die("Validation failed for option --gather: --coverage-file runs on ONE device, where nothing is gathered; leave --gather out.");
     }
     if (!cfg.report_unit.empty() && cfg.kraken_file.empty()) die("Option --report-unit says what --report-file counts: it needs that option.");
+    if (cfg.confidence_mode() && !cfg.lca_mode()) die("Option --lca-confidence weighs the calls of --lca-file / --report-file: it needs one of them.");
+    if (cfg.confidence_mode()) {   // before any HIP call
+        if (cfg.index_file.find(',') != std::string::npos)
+            die("Validation failed for option --index-file: --lca-confidence takes ONE index file (a read's hashes are looked up in the leaf bins of the index its references belong to); "
+                "search the indexes one by one.");
+        if (cfg.gpus.size() > 1)
+            die("Validation failed for option " + run.gpus_option + ": --lca-confidence weighs on ONE device (a batch's hash lists and its results must lie on the same one); give --gpu <id>.");
+        if (!cfg.gather.empty() && cfg.gather != "none")
+            die("Validation failed for option --gather: --lca-confidence runs on ONE device, where nothing is gathered; leave --gather out.");
+    }
     if (cfg.lca_mode()) {   // before any HIP call
         const std::string opt = !cfg.lca_file.empty() ? "--lca-file" : "--report-file";
         if (cfg.index_file.find(',') != std::string::npos)
@@ -1081,6 +1113,16 @@ struct ReportWriter {
         const size_t n = bt.ids.size();
         if (bt.lca_node.size() != n || bt.n_hashes.size() != n) die("internal: a chunk reached the writer without its reads' calls");
         lca_text.clear();
+        if (run.cfg.confidence_mode()) {                   // the confident calls and their three further columns (confidence_format.h)
+            if (bt.cf_lca_node.size() != n) die("internal: a chunk reached the writer without its reads' supports");
+            auto id_of = [&](int32_t node) -> const char * { return node == TAXOR_LCA_UNCLASSIFIED ? nullptr : node == TAXOR_LCA_ROOT ? "1" : lv.id[node]; };
+            for (size_t r = 0; r < n; ++r)
+                taxor::confidence_line(lca_text, bt.ids.ptr(r), bt.ids.len(r), id_of(bt.lca_node[r]), bt.offsets[r + 1] - bt.offsets[r], bt.n_hashes[r], bt.lca_best[r],
+                                       bt.lca_refs[r], bt.cf_support[r], id_of(bt.cf_lca_node[r]), bt.cf_lca_support[r]);
+            if (!lca_text.empty() && fwrite(lca_text.data(), 1, lca_text.size(), run.lca_out) != lca_text.size())
+                die("cannot write to " + run.cfg.lca_file + ": " + strerror(errno));
+            return;
+        }
         char num[4][24];
         for (size_t r = 0; r < n; ++r) {
             const int32_t node = bt.lca_node[r];
@@ -1279,7 +1321,7 @@ void finish_lca(SearchRun &run)
         run.lca_out = nullptr;
     }
     taxor_lca_results lr{};
-    if (taxor_gpu_lca_results(run.lca, &lr) != TAXOR_OK) die(taxor_gpu_last_error());
+    if ((run.confidence ? taxor_gpu_confidence_results(run.confidence, &lr) : taxor_gpu_lca_results(run.lca, &lr)) != TAXOR_OK) die(taxor_gpu_last_error());
     const taxor_lineage_view &lv = run.lineage_view;
     const uint64_t nn = lr.n_nodes;
     if (!cfg.kraken_file.empty()) {
@@ -1327,7 +1369,14 @@ void finish_lca(SearchRun &run)
     }
     if (tune_env("TAXOR_CLI_TRACE"))
         fprintf(stderr, "[trace] lca: %llu nodes, %llu reads called, %llu of them unclassified; %.3f s inside the accumulation (summed over workers), %.6f s in its kernel\n",
-                (unsigned long long)nn, (unsigned long long)lr.n_reads, (unsigned long long)lr.direct_reads[nn + 1], run.t_lca, lr.seconds_kernel);
+                (unsigned long long)nn, (unsigned long long)lr.n_reads, (unsigned long long)lr.direct_reads[nn + 1], run.confidence ? run.t_confidence : run.t_lca, lr.seconds_kernel);
+    if (run.confidence && tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] confidence: threshold %g; %.3f s inside the weighing (summed over workers), %.6f s in its kernels, %llu (hash, leaf bin) lookups, "
+                        "%llu of %llu (64 hashes, tuple) steps made\n",
+                cfg.lca_confidence, run.t_confidence, run.t_confidence_kernels, (unsigned long long)run.confidence_probes, (unsigned long long)run.confidence_steps,
+                (unsigned long long)run.confidence_steps_full);
+    taxor_gpu_confidence_destroy(run.confidence);
+    run.confidence = nullptr;
     taxor_gpu_lca_destroy(run.lca);
     run.lca = nullptr;
     taxor_lineage_free(run.lineage);
@@ -1409,6 +1458,7 @@ struct GpuStage {
             for (uint64_t i = meta->n_species; i-- > 0;)
                 if (meta->species[i].user_bin < view->n_user_bins) run.hitmap_species[meta->species[i].user_bin] = (uint32_t)i;
         }
+        if (cfg.confidence_mode() && taxor_gpu_confidence_create(gidx[0], view, run.lineage, cfg.lca_confidence, &run.confidence) != TAXOR_OK) die(taxor_gpu_last_error());
         for (auto *s : sr)
             if (taxor_gpu_search_capture(s, 1) != TAXOR_OK) die(taxor_gpu_last_error());
     }
@@ -1442,10 +1492,39 @@ struct GpuStage {
             }
         }
         const double c3 = now();
+        // --lca-confidence: the batch's reads are called from its results on the device and these lists; the calls go to the chunks
+        taxor_confidence_calls cc{};
+        if (rc == TAXOR_OK && run.confidence) {
+            uint64_t nr = 0;
+            for (auto &bt : group) nr += bt->ids.size();
+            rc = taxor_gpu_confidence_add_batch(run.confidence, s, sv, run.lca_next_read.fetch_add(nr), &cc);
+            if (rc == TAXOR_OK && cc.n_reads != nr) die("internal: a batch's calls do not cover its chunks");
+            uint64_t r0 = 0;
+            for (auto &bt : group) {
+                if (rc != TAXOR_OK) break;
+                const uint64_t n = bt->ids.size();
+                bt->lca_node.assign(cc.node + r0, cc.node + r0 + n);
+                bt->lca_best.assign(cc.best + r0, cc.best + r0 + n);
+                bt->lca_refs.assign(cc.n_refs + r0, cc.n_refs + r0 + n);
+                bt->cf_lca_node.assign(cc.lca_node + r0, cc.lca_node + r0 + n);
+                bt->cf_support.assign(cc.support + r0, cc.support + r0 + n);
+                bt->cf_lca_support.assign(cc.lca_support + r0, cc.lca_support + r0 + n);
+                if (!run.write_tsv) bt->n_hashes.assign(cc.n_hashes + r0, cc.n_hashes + r0 + n);
+                r0 += n;
+            }
+        }
+        const double c3b = now();
         taxor_gpu_saved_free(sv);
         if (rc != TAXOR_OK) die(taxor_gpu_last_error());
-        const double c4 = now(), shared = (c1 - c0) + (c4 - c3);        // taking and freeing the lists: the first consumer's
+        const double c4 = now(), shared = (c1 - c0) + (c4 - c3b);       // taking and freeing the lists: the first consumer's
         std::lock_guard<std::mutex> lk(run.stat_mu);
+        if (run.confidence) {
+            run.t_confidence += c3b - c3 + (run.coverage || run.hitmap ? 0.0 : shared);
+            run.t_confidence_kernels += cc.seconds_kernels;
+            run.confidence_probes += cc.probes;
+            run.confidence_steps += cc.tuple_steps;
+            run.confidence_steps_full += cc.tuple_steps_full;
+        }
         if (run.coverage) run.t_coverage += c2 - c1 + shared;
         if (run.hitmap) {
             run.t_hitmap += c3 - c2 + (run.coverage ? 0.0 : shared);
@@ -1691,7 +1770,7 @@ struct GpuStage {
             // without a TSV nothing on the host reads the tuples: they stay on the device for the profile feed
             if (classify(sr[wi], group, scanned, run.write_tsv ? &res : nullptr) != TAXOR_OK) die(taxor_gpu_last_error());
             if (run.profile_mode) feed_profile(sr[wi], group);
-            if (run.coverage || run.hitmap) use_saved(sr[wi], group);
+            if (run.coverage || run.hitmap || run.confidence) use_saved(sr[wi], group);
             if (run.lca) add_lca(sr[wi], group);
             --n_running;
             const double t3 = now();
@@ -1780,8 +1859,9 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
     const double t_search0 = now();
     if (run.profile_mode) run.fused.begin(view, taxor_hixf_get_meta(h), run.prof.device);
     gpu.create_searchers(prm);
-    if (!cfg.coverage_file.empty() || !cfg.hitmap_file.empty()) gpu.begin_saved_consumers(view, taxor_hixf_get_meta(h));
-    if (run.lineage && taxor_gpu_lca_create(gpu.gidx[0], run.lineage, &run.lca) != TAXOR_OK) die(taxor_gpu_last_error());
+    if (!cfg.coverage_file.empty() || !cfg.hitmap_file.empty() || cfg.confidence_mode()) gpu.begin_saved_consumers(view, taxor_hixf_get_meta(h));
+    // (with --lca-confidence the confident calls fill both files: the plain accumulator is not created)
+    if (run.lineage && !run.confidence && taxor_gpu_lca_create(gpu.gidx[0], run.lineage, &run.lca) != TAXOR_OK) die(taxor_gpu_last_error());
     gpu.run_workers();
     run.t_search_wall += now() - t_search0;
     if (run.coverage) {
@@ -1805,7 +1885,7 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
                 writer.t_last_write > writer.t_first_write ? writer.out_written.load() / 1e9 / (writer.t_last_write - writer.t_first_write) : 0.0, writer.t_write,
                 writer.t_write > 0 ? writer.out_written.load() / 1e9 / writer.t_write : 0.0);
     run.t_reads += *std::max_element(feed.reader_time.begin(), feed.reader_time.end());
-    if (run.lca) {
+    if (run.lca || run.confidence) {
         finish_lca(run);
         trace("calls and report written");
     }
@@ -1910,6 +1990,13 @@ void search_files(SearchRun &run, const std::string &hixf_file, const std::vecto
         if (budget)
             die("Validation failed for option --hitmap-file: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
                 std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; locating hits pass by pass is not built.");
+    }
+    if (cfg.confidence_mode()) {
+        // a read's hashes are looked up in ALL the leaf bins of its references, and its final tuples exist only after the last pass's merge
+        if (budget && cfg.index_budget_mib && whole.index_bytes <= budget) budget = 0;
+        if (budget)
+            die("Validation failed for option --lca-confidence: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
+                std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; weighing calls pass by pass is not built.");
     }
     if (cfg.lca_mode()) {
         // a read is called from its FINAL tuples, which a paged search has only after the last pass's merge

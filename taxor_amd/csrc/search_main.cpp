@@ -13,6 +13,7 @@
 #include "tuning.h"
 #include "ixf_arith.h"
 #include "ixf_layout.h"
+#include "confidence_format.h"
 #include "hitmap_format.h"
 #include "key_store.h"
 using taxor::tune_env;
@@ -109,7 +110,7 @@ int main(int argc, char **argv)
     if (!cfg.lca_file.empty()) {
         run.lca_out = fopen(cfg.lca_file.c_str(), "wb");
         if (!run.lca_out) die("cannot open call file " + cfg.lca_file);
-        fputs("#STATUS\tQUERY_NAME\tTAXID\tQUERY_LEN\tQHASH_COUNT\tBEST_QHASH_MATCH\tREFERENCES\n", run.lca_out);
+        fputs(cfg.confidence_mode() ? taxor::confidence_header() : "#STATUS\tQUERY_NAME\tTAXID\tQUERY_LEN\tQHASH_COUNT\tBEST_QHASH_MATCH\tREFERENCES\n", run.lca_out);
     }
     if (!cfg.hitmap_file.empty()) {
         run.hitmap_out = fopen(cfg.hitmap_file.c_str(), "wb");

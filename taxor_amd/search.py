@@ -832,6 +832,89 @@ class Lca:
 
 
 @dataclass
+class ConfidenceCalls:
+    """per read of one add: the confident call and its depth, the call without a threshold and its depth D, support at the confident
+    depth (support[0] for a read the threshold made unclassified), support[D], support[0], and LcaCalls' best / n_refs / n_hashes"""
+    first_read: int
+    node: np.ndarray          # int32[n_reads]
+    depth: np.ndarray         # uint32[n_reads]
+    lca_node: np.ndarray      # int32[n_reads]
+    lca_depth: np.ndarray     # uint32[n_reads]
+    support: np.ndarray       # uint32[n_reads]
+    lca_support: np.ndarray   # uint32[n_reads]
+    any_support: np.ndarray   # uint32[n_reads]
+    best: np.ndarray          # uint32[n_reads]
+    n_refs: np.ndarray        # uint32[n_reads]
+    n_hashes: np.ndarray      # uint32[n_reads]
+    seconds_kernels: float
+    probes: int
+    tuple_steps: int
+    tuple_steps_full: int
+
+
+class Confidence:
+    """Hash support behind each LCA call and the call a threshold on it leaves (taxor_amd/csrc/confidence.hip).  `ixfs` is the list
+    the GpuIndex was made from (only bins and fname_idx are read).  add_batch follows a batch that ran with Searcher.capture() on and
+    takes its SavedBatch, which stays the caller's; add_csr takes host arrays.  The arrays returned are copies."""
+
+    WORDS = ("node", "depth", "lca_node", "lca_depth", "support", "lca_support", "any_support", "best", "n_refs", "n_hashes")
+
+    def __init__(self, index: GpuIndex, ixfs, lineage: Lineage, confidence=0.0):
+        view, keep = GpuIndex._view([dict(f, data=None) for f in ixfs], index.n_user_bins, index.k, index.s, index.t, index.use_syncmer, 1,
+                                    index.window_size)
+        self._L = _lib.lib()
+        self._h = C.c_void_p()
+        self.index, self.lineage, self.confidence = index, lineage, float(confidence)
+        check(self._L.taxor_gpu_confidence_create(index._h, C.byref(view), lineage._h, float(confidence), C.byref(self._h)))
+        del keep
+
+    @classmethod
+    def _calls(cls, c):
+        n = int(c.n_reads)
+        arr = lambda ptr, dt: np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        words = [arr(getattr(c, f), np.int32 if f in ("node", "lca_node") else np.uint32) for f in cls.WORDS]
+        return ConfidenceCalls(int(c.first_read), *words, float(c.seconds_kernels), int(c.probes), int(c.tuple_steps), int(c.tuple_steps_full))
+
+    def add_batch(self, searcher: Searcher, saved: "SavedBatch", first_read=0) -> ConfidenceCalls:
+        c = _lib.ConfidenceCalls()
+        check(self._L.taxor_gpu_confidence_add_batch(self._h, searcher._h, saved._h if saved is not None else None, int(first_read), C.byref(c)))
+        return self._calls(c)
+
+    def add_csr(self, read_off, user_bin, count, query_len, hash_off, hashes) -> ConfidenceCalls:
+        ro = np.ascontiguousarray(read_off, dtype=np.uint64)
+        ub = np.ascontiguousarray(user_bin, dtype=np.int64)
+        ct = np.ascontiguousarray(count, dtype=np.uint32)
+        ql = np.ascontiguousarray(query_len, dtype=np.uint64)
+        ho = np.ascontiguousarray(hash_off, dtype=np.uint64)
+        hs = np.ascontiguousarray(hashes, dtype=np.uint64)
+        assert ro.size >= 1 and ql.size == ro.size - 1 and ho.size == ro.size and ub.size == ct.size and int(ro[-1]) <= ub.size and int(ho[-1]) <= hs.size
+        c = _lib.ConfidenceCalls()
+        check(self._L.taxor_gpu_confidence_add_csr(self._h, ro.size - 1, _p(ro), _p(ub) if ub.size else None, _p(ct) if ct.size else None,
+                                                   _p(ql) if ql.size else None, _p(ho), _p(hs) if hs.size else None, C.byref(c)))
+        return self._calls(c)
+
+    def results(self) -> LcaTallies:
+        res = _lib.LcaResults()
+        check(self._L.taxor_gpu_confidence_results(self._h, C.byref(res)))
+        n = int(res.n_nodes)
+        return LcaTallies(n, np.ctypeslib.as_array(res.direct_reads, shape=(n + 2,)).copy(), np.ctypeslib.as_array(res.direct_bases, shape=(n + 2,)).copy(),
+                          int(res.n_reads), float(res.seconds_kernel))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.taxor_gpu_confidence_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+@dataclass
 class HitmapBatch:
     """Hitmap.add_batch(): read r's mapped tuples are [map_off[r], map_off[r + 1]) of tuple / user_bin / count / hits"""
     segments: int
