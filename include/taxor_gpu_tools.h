@@ -823,6 +823,64 @@ int taxor_gpu_confidence_add_csr(taxor_gpu_confidence *cf, uint64_t n_reads, con
 int taxor_gpu_confidence_results(taxor_gpu_confidence *cf, taxor_lca_results *out);
 void taxor_gpu_confidence_destroy(taxor_gpu_confidence *cf);
 
+/* ---- where a read switches reference (`taxor search --breakpoint-file`; taxor_amd/csrc/breakpoint.hip and breakpoint_format.h,
+ * DESIGN.md section 10.6).  The hit map above gives one line per reference and sixteen counters; whether a read is a chimera, carries
+ * an inserted element or crosses a host/microbe junction needs all of a read's references at once and every position of its list.
+ * For read r: n = its saved hash count (QHASH_COUNT); h(0) .. h(n-1) its saved list, in the capture's first-occurrence order; T = ALL
+ * its tuples in the batch CSR, not only the survivors of the 0.8 * max filter (the minor partner of a chimera lies below that filter by
+ * construction).  The CANDIDATES are the tuples of T with count > 0, in CSR order, numbered c = 0 .. M-1.  The read is EXAMINED when
+ * n > 0 and M >= 2; every word below is 0 for a read that is not.
+ * x_c(i) = 1 when h(i) matches candidate c's user bin by the hit map's lookup above (at least one leaf technical bin of the user bin,
+ * under the index's arithmetic code and the IXF's seed), else 0.  total_c = sum_i x_c(i) (the hit map's LOCATED);
+ * pre_c(p) = sum_{i<p} x_c(i); suf_c(p) = total_c - pre_c(p).  For p in [0, n): P(p) = max_c pre_c(p), S(p) = max_c suf_c(p),
+ * split(p) = P(p) + S(p).  single = max_c total_c = split(0); best = the lowest c that attains it.  gain = max_p split(p) - single >= 0.
+ * The break p* = the smallest p that attains the maximum; A = the lowest c with pre_c(p*) == P(p*), B = the lowest c with
+ * suf_c(p*) == S(p*).  Where gain > 0, A != B (A == B gives split(p*) = total_A <= single).  All arithmetic is integer.
+ * A read is REPORTED when it is examined and gain >= min_gain.  A partner that did not pass the search threshold is not a tuple and
+ * cannot be a candidate: lower the threshold to look for short inserts.
+ * _create: `view` is the one the index was created from (only bins and fname_idx are read); min_gain >= 1.  TAXOR_E_ARG naming the
+ * reason: min_gain 0; a paged index, by name.
+ * _add_batch: after taxor_gpu_search_batch_end (or _batch_sync) of a batch that ran with capture on, with that batch's saved lists
+ * (which stay the caller's), before the next batch on the searcher.  Checked before any launch, TAXOR_E_ARG naming the field: the saved
+ * batch is sound, its n_reads is the searcher's, its n_hashes are the searcher's, the searcher's index is the object's.  The searcher's
+ * device-resident CSR is read where it lies; only the lists of examined reads are staged, through a bounded device buffer.  The match
+ * matrix (8 bytes per candidate and 64 hashes, and 4 bytes of prefix counts beside them) lies in device scratch held under a fixed
+ * budget per group of reads; a read that exceeds it by itself is processed alone in scratch grown to fit, and an allocation that fails
+ * is TAXOR_E_NOMEM naming the bytes: no read is skipped.  The result lies in page-locked host memory kept per searcher: valid until the
+ * next _add_batch on THAT searcher (or _destroy).
+ * _add_csr: the same over host arrays (tuples of read r at [read_off[r], read_off[r+1]) of user_bin / count; the read's hash list at
+ * [hash_off[r], hash_off[r+1]) of hashes); a `user_bin` outside the index is refused before any launch; valid until the next _add_csr.
+ * _add calls may come from several threads.  Nothing depends on the launch geometry nor on the cut into pieces, groups and batches. */
+typedef struct taxor_gpu_breakpoint taxor_gpu_breakpoint;
+typedef struct {
+    uint64_t n_reads, n_examined, n_reported;
+    uint32_t min_gain, reserved;
+    const uint8_t *examined;       /* [n_reads] 1: n > 0 and M >= 2 */
+    const uint32_t *gain;          /* [n_reads] */
+    const uint32_t *break_hash;    /* [n_reads] p* */
+    const uint64_t *tuple_a;       /* [n_reads] index of A in the batch CSR (_add_csr: in user_bin / count as given) */
+    const uint64_t *tuple_b;       /* [n_reads] of B */
+    const uint64_t *tuple_best;    /* [n_reads] of best */
+    const uint32_t *pre_a;         /* [n_reads] pre_A(p*) = P(p*) */
+    const uint32_t *suf_b;         /* [n_reads] suf_B(p*) = S(p*) */
+    const uint32_t *pre_b;         /* [n_reads] pre_B(p*) */
+    const uint32_t *suf_a;         /* [n_reads] suf_A(p*) */
+    const uint32_t *single;        /* [n_reads] */
+    const uint32_t *n_candidates;  /* [n_reads] M */
+    const uint32_t *n;             /* [n_reads] n, 0 for a read that is not examined */
+    const uint32_t *n_hashes;      /* [n_reads] QHASH_COUNT of every read (_add_csr: the lists' lengths) */
+    const int64_t *bin_a;          /* [n_reads] the user bins of A, B and best, beside the twelve words */
+    const int64_t *bin_b;
+    const int64_t *bin_best;
+    double seconds_kernels;        /* HIP-event time of this call's kernels */
+    uint64_t lookups;              /* (hash, leaf bin) lookups made by this call: three one-byte gathers each */
+} taxor_breakpoint_batch;
+int taxor_gpu_breakpoint_create(taxor_gpu_index *idx, const taxor_hixf_view *view, uint32_t min_gain, taxor_gpu_breakpoint **out);
+int taxor_gpu_breakpoint_add_batch(taxor_gpu_breakpoint *bp, taxor_gpu_searcher *s, const taxor_gpu_saved *saved, taxor_breakpoint_batch *out);
+int taxor_gpu_breakpoint_add_csr(taxor_gpu_breakpoint *bp, uint64_t n_reads, const uint64_t *read_off, const int64_t *user_bin, const uint32_t *count,
+                                 const uint64_t *hash_off, const uint64_t *hashes, taxor_breakpoint_batch *out);
+void taxor_gpu_breakpoint_destroy(taxor_gpu_breakpoint *bp);
+
 /* ---- search straight from file bytes (taxor_amd/csrc/fastx_scan.hip): raw[0, n_bytes) holds whole records of one
  * kind, '>' (FASTA) or '@' (four-line FASTQ) -- what a reader cuts at record boundaries.  The device finds the records, packs their
  * sequences into the searcher's batch and runs the search; taxor_gpu_search_batch_end follows as after any _begin.  raw may be pageable

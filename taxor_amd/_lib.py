@@ -224,6 +224,16 @@ class ConfidenceCalls(C.Structure):
                 ("tuple_steps", C.c_uint64), ("tuple_steps_full", C.c_uint64)]
 
 
+class BreakpointBatch(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_examined", C.c_uint64), ("n_reported", C.c_uint64), ("min_gain", C.c_uint32), ("reserved", C.c_uint32),
+                ("examined", C.POINTER(C.c_uint8)), ("gain", C.POINTER(C.c_uint32)), ("break_hash", C.POINTER(C.c_uint32)),
+                ("tuple_a", C.POINTER(C.c_uint64)), ("tuple_b", C.POINTER(C.c_uint64)), ("tuple_best", C.POINTER(C.c_uint64)),
+                ("pre_a", C.POINTER(C.c_uint32)), ("suf_b", C.POINTER(C.c_uint32)), ("pre_b", C.POINTER(C.c_uint32)), ("suf_a", C.POINTER(C.c_uint32)),
+                ("single", C.POINTER(C.c_uint32)), ("n_candidates", C.POINTER(C.c_uint32)), ("n", C.POINTER(C.c_uint32)), ("n_hashes", C.POINTER(C.c_uint32)),
+                ("bin_a", C.POINTER(C.c_int64)), ("bin_b", C.POINTER(C.c_int64)), ("bin_best", C.POINTER(C.c_int64)),
+                ("seconds_kernels", C.c_double), ("lookups", C.c_uint64)]
+
+
 class HitmapBatch(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_mapped", C.c_uint64), ("segments", C.c_uint32), ("reserved", C.c_uint32),
                 ("map_off", C.POINTER(C.c_uint64)), ("tuple", C.POINTER(C.c_uint64)), ("user_bin", C.POINTER(C.c_int64)),
@@ -292,6 +302,10 @@ SIGNATURES = {
     "taxor_gpu_confidence_add_csr": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, _P, C.POINTER(ConfidenceCalls)]),
     "taxor_gpu_confidence_results": (C.c_int, [_P, C.POINTER(LcaResults)]),
     "taxor_gpu_confidence_destroy": (None, [_P]),
+    "taxor_gpu_breakpoint_create": (C.c_int, [_P, C.POINTER(HixfView), C.c_uint32, C.POINTER(_P)]),
+    "taxor_gpu_breakpoint_add_batch": (C.c_int, [_P, _P, _P, C.POINTER(BreakpointBatch)]),
+    "taxor_gpu_breakpoint_add_csr": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, C.POINTER(BreakpointBatch)]),
+    "taxor_gpu_breakpoint_destroy": (None, [_P]),
     "taxor_gpu_hitmap_create": (C.c_int, [_P, C.POINTER(HixfView), C.c_uint32, C.POINTER(_P)]),
     "taxor_gpu_hitmap_add_batch": (C.c_int, [_P, _P, _P, C.POINTER(HitmapBatch)]),
     "taxor_gpu_hitmap_destroy": (None, [_P]),

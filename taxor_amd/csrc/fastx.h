@@ -154,6 +154,14 @@ struct Batch {
     std::vector<uint64_t> hm_off;
     std::vector<int64_t> hm_user_bin;
     std::vector<uint32_t> hm_count, hm_hits;
+    // --breakpoint-file: the chunk's REPORTED reads (breakpoint.hip), in read order; bp_set says that the batch's share has arrived;
+    // n_hashes above comes with them when no TSV is written
+    struct BreakRow {
+        uint32_t read, gain, break_hash, pre_a, suf_b, pre_b, suf_a, single, n_cand;
+        int64_t bin_a, bin_b, bin_best;
+    };
+    std::vector<BreakRow> bp_rows;
+    bool bp_set = false;
     // --device-parse: the chunk is a byte range of the file as read (whole records of kind raw_kind, '>' or '@'); the device finds
     // the records, ids and offsets are filled from its table and bases stays empty.  raw_kind 0: a parsed chunk, as above
     BaseBuf raw;

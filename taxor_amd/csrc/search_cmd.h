@@ -26,6 +26,8 @@ struct Config : ReaderOptions {              // taxor_search_configuration.hpp:8
     bool confidence_mode() const { return lca_confidence >= 0.0; }
     std::string hitmap_file;    // --hitmap-file: one line per (read, reference) line of the TSV, the hits along the read's hash list (hitmap.hip)
     uint32_t hitmap_segments = 0;      // hidden --hitmap-segments: parts the ordered hash list is cut into, in [1,64] (0: 16)
+    std::string breakpoint_file;       // --breakpoint-file: one line per read whose hash list splits between two of its references (breakpoint.hip)
+    uint32_t breakpoint_min_gain = 0;  // --breakpoint-min-gain: hits the split must explain beyond the best single reference, >= 1 (0: not given, 1)
     std::string gather;         // several devices: "rccl" | "host" (taxor_gpu_comm transports) | "none" (independent workers, each
                                 // fetching its own results); empty = rccl when the devices are distinct, host when one repeats
 };
@@ -74,6 +76,10 @@ void usage()
             "  --hitmap-file <f>        per line of --output-file that a read with hashes produced: in which sixteenth of the read's ordered hash\n"
             "                           list the reference's hits lie (a chimeric read, an inserted element, one conserved operon); ONE index\n"
             "                           file, ONE device; --output-file is then optional\n"
+            "  --breakpoint-file <f>    per read whose ordered hash list splits between two of the references it reported: where the split lies,\n"
+            "                           the two references and the hits the split explains beyond the best single reference (a chimeric read,\n"
+            "                           an inserted element, a host/microbe junction); ONE index file, ONE device; --output-file is then optional\n"
+            "  --breakpoint-min-gain <n> with --breakpoint-file: report a read from this many hits gained on (default 1)\n"
             "  --expect <tsv>           compare the output per read with a TSV the reference wrote for the same input (exit 3 if it differs)\n"
             "search to profile in one run (the options of `taxor profile`; results go from the device's search buffers into the profile's\n"
             "device pipeline, no TSV is written or parsed in between):\n"
@@ -153,6 +159,23 @@ void advanced_help()
                     "                           is located.  Refused: a comma list of index files, several devices, a --gather transport, and an index\n"
                     "                           that has to be paged.\n"
                     "  --hitmap-segments <S>    with --hitmap-file: the number of segments, in [1,64] (default 16).\n"
+                    "  --breakpoint-file <f>    columns QUERY_NAME, QUERY_LEN, QHASH_COUNT, CANDIDATES, BEST_ACCESSION, BEST_TAXID, BEST_LOCATED, BREAK_HASH,\n"
+                    "                           BREAK_BASE_APPROX, LEFT_ACCESSION, LEFT_TAXID, LEFT_HITS, LEFT_HITS_OF_RIGHT, RIGHT_ACCESSION, RIGHT_TAXID, RIGHT_HITS,\n"
+                    "                           RIGHT_HITS_OF_LEFT, GAIN; one line per reported read, in input order.  The CANDIDATES of a read are ALL the\n"
+                    "                           references the search reported for it with QHASH_MATCH > 0, not only the lines of --output-file (the minor\n"
+                    "                           partner of a chimera lies below the 0.8 * max filter); a read with a hash and two candidates or more is\n"
+                    "                           examined.  Every hash of the read is looked up in every candidate's own leaf bins (--hitmap-file's lookup).\n"
+                    "                           For a break in front of hash p of the ordered list, split(p) = the most hits any candidate has among the\n"
+                    "                           hashes before p + the most any has from p on; BREAK_HASH is the smallest p with the greatest split, LEFT\n"
+                    "                           and RIGHT the candidates that attain the two maxima there (the first in the search's order on a tie), and\n"
+                    "                           GAIN = that split - BEST_LOCATED, the hits of the best single candidate.  A read is written when GAIN >=\n"
+                    "                           --breakpoint-min-gain, so never for GAIN 0; LEFT and RIGHT then differ.  LEFT_HITS_OF_RIGHT and\n"
+                    "                           RIGHT_HITS_OF_LEFT are the other reference's hits on that side.  BREAK_BASE_APPROX = floor(BREAK_HASH *\n"
+                    "                           QUERY_LEN / QHASH_COUNT): the list carries no positions, so this is the base only as far as the read's\n"
+                    "                           hashes are spread evenly (--hitmap-file's caveat).  A partner that did not pass the search threshold was\n"
+                    "                           never reported and cannot be a candidate: lower --percentage to look for short inserts.  The searchers keep\n"
+                    "                           every batch's hash lists in host memory until the batch is examined.  Refused: a comma list of index\n"
+                    "                           files, several devices, a --gather transport, and an index that has to be paged.\n"
                     "  --paged-reread           the default said aloud: read the query file again in every pass; wins over --paged-replay.\n"
                     "BAM input: the BGZF blocks are inflated on --threads threads, one thread walks the records (block_size, flag, l_seq, read_name)\n"
                     "                           and copies the 4-bit SEQ fields into a page-locked buffer; CIGAR, QUAL and tags are never read.  A\n"
@@ -432,6 +455,11 @@ struct SearchRun {
     std::vector<uint32_t> hitmap_species;     // user bin -> the species the TSV names for it
     double t_hitmap = 0, t_hitmap_kernels = 0;   // seconds inside taxor_gpu_hitmap_add_batch and in its kernels, summed over workers
     uint64_t hitmap_probes = 0, hitmap_lines = 0;
+    taxor_gpu_breakpoint *breakpoint = nullptr;   // --breakpoint-file: the object beside the resident index, for the whole run (breakpoint.hip)
+    FILE *breakpoint_out = nullptr;           // --breakpoint-file; written by the sequencer as well
+    std::vector<uint32_t> breakpoint_species; // user bin -> the species the TSV names for it
+    double t_breakpoint = 0, t_breakpoint_kernels = 0;   // seconds inside taxor_gpu_breakpoint_add_batch and in its kernels, summed over workers
+    uint64_t breakpoint_lookups = 0, breakpoint_lines = 0, breakpoint_examined = 0, breakpoint_reads = 0;
     std::atomic<uint64_t> lca_next_read{0};   // the next batch's first read as the accumulator numbers it
     double t_lca = 0;               // seconds inside taxor_gpu_lca_add_batch, summed over workers
     double t_coverage = 0;          // seconds inside taxor_gpu_coverage_add_batch (taking and freeing the saved lists included), summed over workers
@@ -531,6 +559,15 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             if (n < 1 || n > 64) die("Validation failed for option --hitmap-segments: Value not in range [1,64].");
             cfg.hitmap_segments = (uint32_t)n;
         }
+        else if (k == "--breakpoint-file") {
+            cfg.breakpoint_file = val();
+            if (cfg.breakpoint_file.empty()) die("Validation failed for option --breakpoint-file: the file name is empty.");
+        }
+        else if (k == "--breakpoint-min-gain") {
+            const double n = num(val(), true);
+            if (n < 1 || n > 4294967295.0) die("Validation failed for option --breakpoint-min-gain: Value not in range [1,4294967295].");
+            cfg.breakpoint_min_gain = (uint32_t)n;
+        }
         else if (k == "--report-file") {
             cfg.kraken_file = val();
             if (cfg.kraken_file.empty()) die("Validation failed for option --report-file: the file name is empty.");
@@ -620,7 +657,18 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             die("Validation failed for option --gather: --hitmap-file runs on ONE device, where nothing is gathered; leave --gather out.");
         if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
     }
-    run.write_tsv = !(run.profile_mode || cfg.lca_mode() || !cfg.hitmap_file.empty()) || !cfg.report_file.empty();
+    if (cfg.breakpoint_min_gain && cfg.breakpoint_file.empty()) die("Option --breakpoint-min-gain says which reads --breakpoint-file reports: it needs that option.");
+    if (!cfg.breakpoint_file.empty()) {   // before any HIP call
+        if (cfg.index_file.find(',') != std::string::npos)
+            die("Validation failed for option --index-file: --breakpoint-file takes ONE index file (a read's hashes are looked up in the leaf bins of the index its references belong to); "
+                "search the indexes one by one.");
+        if (cfg.gpus.size() > 1)
+            die("Validation failed for option " + run.gpus_option + ": --breakpoint-file examines on ONE device (a batch's hash lists and its results must lie on the same one); give --gpu <id>.");
+        if (!cfg.gather.empty() && cfg.gather != "none")
+            die("Validation failed for option --gather: --breakpoint-file runs on ONE device, where nothing is gathered; leave --gather out.");
+        if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
+    }
+    run.write_tsv = !(run.profile_mode || cfg.lca_mode() || !cfg.hitmap_file.empty() || !cfg.breakpoint_file.empty()) || !cfg.report_file.empty();
     if (cfg.threads == 0) {
         // --threads not given.  The reference's default is one worker thread (taxor_search_configuration.hpp:17) -- there the
         // thread that classifies; here host threads only parse the query file and render text for the GPU, and one of them
@@ -1089,6 +1137,7 @@ struct ReportWriter {
                 if (run.profile_mode) run.fused.take_ids(bt);            // chunks pass here in input order
                 if (run.lca_out) write_lca_lines(bt);
                 if (run.hitmap_out) write_hitmap_lines(bt);
+                if (run.breakpoint_out) write_breakpoint_lines(*hd->b);
                 if (n == 0 || !run.write_tsv) { chunk_done(hd); continue; }
                 // cut where the estimated text passes piece_bytes
                 const uint64_t per_tuple = line_bytes_guess.load();
@@ -1161,6 +1210,29 @@ struct ReportWriter {
         run.hitmap_lines += bt.hm_count.size();
         if (!hitmap_text.empty() && fwrite(hitmap_text.data(), 1, hitmap_text.size(), run.hitmap_out) != hitmap_text.size())
             die("cannot write to " + run.cfg.hitmap_file + ": " + strerror(errno));
+    }
+    // --breakpoint-file: the chunk's reported reads, one line each, by the sequencer (breakpoint_format.h)
+    std::string breakpoint_text;
+    void write_breakpoint_lines(Batch &bt)
+    {
+        const size_t n = bt.ids.size();
+        if (!bt.bp_set || bt.n_hashes.size() != n) die("internal: a chunk reached the writer without its reads' breaks");
+        bt.bp_set = false;
+        const taxor_hixf_meta *meta = taxor_hixf_get_meta(h);
+        auto ref = [&](int64_t bin) {     // the species `taxor_format_read` prints for the user bin
+            const uint64_t b = (uint64_t)bin;
+            const taxor_species *sp = meta->n_species ? &meta->species[b < run.breakpoint_species.size() ? run.breakpoint_species[b] : 0] : nullptr;
+            return taxor::breakpoint_ref{sp ? sp->accession_id : nullptr, sp ? sp->taxid : nullptr};
+        };
+        breakpoint_text.clear();
+        for (const Batch::BreakRow &x : bt.bp_rows) {
+            if (x.read >= n) die("internal: a break names a read outside its chunk");
+            taxor::breakpoint_line(breakpoint_text, bt.ids.ptr(x.read), bt.ids.len(x.read), bt.offsets[x.read + 1] - bt.offsets[x.read], bt.n_hashes[x.read], x.n_cand,
+                                   ref(x.bin_best), x.single, x.break_hash, ref(x.bin_a), x.pre_a, x.pre_b, ref(x.bin_b), x.suf_b, x.suf_a, x.gain);
+        }
+        run.breakpoint_lines += bt.bp_rows.size();
+        if (!breakpoint_text.empty() && fwrite(breakpoint_text.data(), 1, breakpoint_text.size(), run.breakpoint_out) != breakpoint_text.size())
+            die("cannot write to " + run.cfg.breakpoint_file + ": " + strerror(errno));
     }
     // a piece's text goes to the file when its ticket comes up
     void write_in_turn(const Piece &pc, const char *text, uint64_t need)
@@ -1309,6 +1381,23 @@ void finish_hitmap(SearchRun &run)
     run.hitmap = nullptr;
 }
 
+// ---- `--breakpoint-file`: the lines were written chunk by chunk; the file is closed here
+void finish_breakpoint(SearchRun &run)
+{
+    if (run.breakpoint_out) {
+        if (ferror(run.breakpoint_out) || fclose(run.breakpoint_out) != 0) die("cannot write to " + run.cfg.breakpoint_file + ": " + strerror(errno));
+        run.breakpoint_out = nullptr;
+    }
+    if (tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] breakpoint: %llu lines from %llu examined reads of %llu; %.3f s inside the examining (summed over workers), %.6f s in its kernels, "
+                        "%llu lookups of a hash in a leaf bin = %.2f G gathers/s\n",
+                (unsigned long long)run.breakpoint_lines, (unsigned long long)run.breakpoint_examined, (unsigned long long)run.breakpoint_reads, run.t_breakpoint,
+                run.t_breakpoint_kernels, (unsigned long long)run.breakpoint_lookups,
+                run.t_breakpoint_kernels > 0 ? 3.0 * run.breakpoint_lookups / run.t_breakpoint_kernels / 1e9 : 0.0);
+    taxor_gpu_breakpoint_destroy(run.breakpoint);
+    run.breakpoint = nullptr;
+}
+
 // ---- `--report-file`: the run's tallies, fetched once, rolled up the tree on the host (a few hundred thousand nodes at most, once per
 // run) and written as a Kraken-style report; `--lca-file` is closed here as well.  The layout: percentage of
 // the clade, clade count, direct count, rank code, taxid, name indented by two spaces per depth; unclassified first, then the tree from
@@ -1446,7 +1535,7 @@ struct GpuStage {
             for (unsigned w = 0; w < wpg; ++w)
                 if (taxor_gpu_searcher_create(gidx[g], &prm, &sr[g * wpg + w]) != TAXOR_OK) die(taxor_gpu_last_error());
     }
-    // --coverage-file / --hitmap-file: the consumers beside the (one) index, and every searcher leaves its batches' hash lists for them
+    // --coverage-file / --hitmap-file / --lca-confidence / --breakpoint-file: the consumers beside the (one) index, and every searcher leaves its batches' hash lists for them
     void begin_saved_consumers(const taxor_hixf_view *view, const taxor_hixf_meta *meta)
     {
         const Config &cfg = run.cfg;
@@ -1459,6 +1548,13 @@ struct GpuStage {
                 if (meta->species[i].user_bin < view->n_user_bins) run.hitmap_species[meta->species[i].user_bin] = (uint32_t)i;
         }
         if (cfg.confidence_mode() && taxor_gpu_confidence_create(gidx[0], view, run.lineage, cfg.lca_confidence, &run.confidence) != TAXOR_OK) die(taxor_gpu_last_error());
+        if (!cfg.breakpoint_file.empty()) {
+            if (taxor_gpu_breakpoint_create(gidx[0], view, cfg.breakpoint_min_gain ? cfg.breakpoint_min_gain : taxor::BREAKPOINT_DEFAULT_MIN_GAIN, &run.breakpoint) != TAXOR_OK)
+                die(taxor_gpu_last_error());
+            run.breakpoint_species.assign(view->n_user_bins, 0u);     // as for the hit map
+            for (uint64_t i = meta->n_species; i-- > 0;)
+                if (meta->species[i].user_bin < view->n_user_bins) run.breakpoint_species[meta->species[i].user_bin] = (uint32_t)i;
+        }
         for (auto *s : sr)
             if (taxor_gpu_search_capture(s, 1) != TAXOR_OK) die(taxor_gpu_last_error());
     }
@@ -1514,9 +1610,32 @@ struct GpuStage {
             }
         }
         const double c3b = now();
+        // --breakpoint-file: the reported reads of the batch go to the chunks that hold them
+        taxor_breakpoint_batch bb{};
+        if (rc == TAXOR_OK && run.breakpoint) rc = taxor_gpu_breakpoint_add_batch(run.breakpoint, s, sv, &bb);
+        if (rc == TAXOR_OK && run.breakpoint) {
+            uint64_t nr = 0;
+            for (auto &bt : group) nr += bt->ids.size();
+            if (bb.n_reads != nr) die("internal: a batch's breaks do not cover its chunks");
+            uint64_t r0 = 0;
+            for (auto &bt : group) {
+                const uint64_t n = bt->ids.size();
+                bt->bp_rows.clear();
+                for (uint64_t i = 0; i < n; ++i) {
+                    const uint64_t r = r0 + i;
+                    if (bb.examined[r] && bb.gain[r] >= bb.min_gain)
+                        bt->bp_rows.push_back(Batch::BreakRow{(uint32_t)i, bb.gain[r], bb.break_hash[r], bb.pre_a[r], bb.suf_b[r], bb.pre_b[r], bb.suf_a[r], bb.single[r],
+                                                              bb.n_candidates[r], bb.bin_a[r], bb.bin_b[r], bb.bin_best[r]});
+                }
+                bt->bp_set = true;
+                if (!run.write_tsv) bt->n_hashes.assign(bb.n_hashes + r0, bb.n_hashes + r0 + n);
+                r0 += n;
+            }
+        }
+        const double c3c = now();
         taxor_gpu_saved_free(sv);
         if (rc != TAXOR_OK) die(taxor_gpu_last_error());
-        const double c4 = now(), shared = (c1 - c0) + (c4 - c3b);       // taking and freeing the lists: the first consumer's
+        const double c4 = now(), shared = (c1 - c0) + (c4 - c3c);       // taking and freeing the lists: the first consumer's
         std::lock_guard<std::mutex> lk(run.stat_mu);
         if (run.confidence) {
             run.t_confidence += c3b - c3 + (run.coverage || run.hitmap ? 0.0 : shared);
@@ -1524,6 +1643,13 @@ struct GpuStage {
             run.confidence_probes += cc.probes;
             run.confidence_steps += cc.tuple_steps;
             run.confidence_steps_full += cc.tuple_steps_full;
+        }
+        if (run.breakpoint) {
+            run.t_breakpoint += c3c - c3b + (run.coverage || run.hitmap || run.confidence ? 0.0 : shared);
+            run.t_breakpoint_kernels += bb.seconds_kernels;
+            run.breakpoint_lookups += bb.lookups;
+            run.breakpoint_examined += bb.n_examined;
+            run.breakpoint_reads += bb.n_reads;
         }
         if (run.coverage) run.t_coverage += c2 - c1 + shared;
         if (run.hitmap) {
@@ -1770,7 +1896,7 @@ struct GpuStage {
             // without a TSV nothing on the host reads the tuples: they stay on the device for the profile feed
             if (classify(sr[wi], group, scanned, run.write_tsv ? &res : nullptr) != TAXOR_OK) die(taxor_gpu_last_error());
             if (run.profile_mode) feed_profile(sr[wi], group);
-            if (run.coverage || run.hitmap || run.confidence) use_saved(sr[wi], group);
+            if (run.coverage || run.hitmap || run.confidence || run.breakpoint) use_saved(sr[wi], group);
             if (run.lca) add_lca(sr[wi], group);
             --n_running;
             const double t3 = now();
@@ -1859,7 +1985,7 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
     const double t_search0 = now();
     if (run.profile_mode) run.fused.begin(view, taxor_hixf_get_meta(h), run.prof.device);
     gpu.create_searchers(prm);
-    if (!cfg.coverage_file.empty() || !cfg.hitmap_file.empty() || cfg.confidence_mode()) gpu.begin_saved_consumers(view, taxor_hixf_get_meta(h));
+    if (!cfg.coverage_file.empty() || !cfg.hitmap_file.empty() || cfg.confidence_mode() || !cfg.breakpoint_file.empty()) gpu.begin_saved_consumers(view, taxor_hixf_get_meta(h));
     // (with --lca-confidence the confident calls fill both files: the plain accumulator is not created)
     if (run.lineage && !run.confidence && taxor_gpu_lca_create(gpu.gidx[0], run.lineage, &run.lca) != TAXOR_OK) die(taxor_gpu_last_error());
     gpu.run_workers();
@@ -1892,6 +2018,10 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
     if (run.hitmap) {
         finish_hitmap(run);
         trace("hit maps written");
+    }
+    if (run.breakpoint) {
+        finish_breakpoint(run);
+        trace("breaks written");
     }
     gpu.release();
     if (run.profile_mode) {
@@ -1990,6 +2120,13 @@ void search_files(SearchRun &run, const std::string &hixf_file, const std::vecto
         if (budget)
             die("Validation failed for option --hitmap-file: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
                 std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; locating hits pass by pass is not built.");
+    }
+    if (!cfg.breakpoint_file.empty()) {
+        // a read's hashes are looked up in ALL the leaf bins of its candidates, and its final tuples exist only after the last pass's merge
+        if (budget && cfg.index_budget_mib && whole.index_bytes <= budget) budget = 0;
+        if (budget)
+            die("Validation failed for option --breakpoint-file: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
+                std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; finding breaks pass by pass is not built.");
     }
     if (cfg.confidence_mode()) {
         // a read's hashes are looked up in ALL the leaf bins of its references, and its final tuples exist only after the last pass's merge

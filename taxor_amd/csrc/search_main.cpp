@@ -13,6 +13,7 @@
 #include "tuning.h"
 #include "ixf_arith.h"
 #include "ixf_layout.h"
+#include "breakpoint_format.h"
 #include "confidence_format.h"
 #include "hitmap_format.h"
 #include "key_store.h"
@@ -116,6 +117,11 @@ int main(int argc, char **argv)
         run.hitmap_out = fopen(cfg.hitmap_file.c_str(), "wb");
         if (!run.hitmap_out) die("cannot open hit map file " + cfg.hitmap_file);
         fputs(taxor::hitmap_header(), run.hitmap_out);
+    }
+    if (!cfg.breakpoint_file.empty()) {
+        run.breakpoint_out = fopen(cfg.breakpoint_file.c_str(), "wb");
+        if (!run.breakpoint_out) die("cannot open breakpoint file " + cfg.breakpoint_file);
+        fputs(taxor::breakpoint_header(), run.breakpoint_out);
     }
     if (index_files.size() == 1) {
         search_files(run, index_files[0], query_files, true);

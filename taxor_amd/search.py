@@ -964,6 +964,94 @@ class Hitmap:
         self.close()
 
 
+@dataclass
+class BreakpointBatch:
+    """Breakpoints.add_batch() / add_csr(): per read the twelve words of include/taxor_gpu_tools.h (all 0 for a read that is not
+    examined), the user bins of A, B and best, and every read's hash count.  reported = examined and gain >= min_gain"""
+    min_gain: int
+    examined: np.ndarray      # bool[n_reads]
+    gain: np.ndarray          # uint32[n_reads]
+    break_hash: np.ndarray    # uint32[n_reads] p*
+    tuple_a: np.ndarray       # uint64[n_reads] index in the batch CSR
+    tuple_b: np.ndarray
+    tuple_best: np.ndarray
+    pre_a: np.ndarray         # uint32[n_reads]
+    suf_b: np.ndarray
+    pre_b: np.ndarray
+    suf_a: np.ndarray
+    single: np.ndarray
+    n_candidates: np.ndarray  # M
+    n: np.ndarray             # the hash count of an examined read
+    n_hashes: np.ndarray      # of every read
+    bin_a: np.ndarray         # int64[n_reads]
+    bin_b: np.ndarray
+    bin_best: np.ndarray
+    n_examined: int
+    n_reported: int
+    seconds_kernels: float
+    lookups: int
+
+    @property
+    def reported(self):
+        return self.examined & (self.gain >= self.min_gain)
+
+
+class Breakpoints:
+    """Where a read switches reference (taxor_amd/csrc/breakpoint.hip).  `ixfs` is the list the GpuIndex was made from (only bins and
+    fname_idx are read).  add_batch follows a batch that ran with Searcher.capture() on and takes its SavedBatch, which stays the
+    caller's; add_csr takes host arrays.  The arrays returned are copies."""
+
+    WORDS = (("gain", np.uint32), ("break_hash", np.uint32), ("tuple_a", np.uint64), ("tuple_b", np.uint64), ("tuple_best", np.uint64), ("pre_a", np.uint32),
+             ("suf_b", np.uint32), ("pre_b", np.uint32), ("suf_a", np.uint32), ("single", np.uint32), ("n_candidates", np.uint32), ("n", np.uint32),
+             ("n_hashes", np.uint32), ("bin_a", np.int64), ("bin_b", np.int64), ("bin_best", np.int64))
+
+    def __init__(self, index: GpuIndex, ixfs, min_gain=1):
+        view, keep = GpuIndex._view([dict(f, data=None) for f in ixfs], index.n_user_bins, index.k, index.s, index.t, index.use_syncmer, 1,
+                                    index.window_size)
+        self._L = _lib.lib()
+        self._h = C.c_void_p()
+        self.index, self.min_gain = index, int(min_gain)
+        check(self._L.taxor_gpu_breakpoint_create(index._h, C.byref(view), int(min_gain), C.byref(self._h)))
+        del keep
+
+    @classmethod
+    def _batch(cls, b):
+        n = int(b.n_reads)
+        arr = lambda ptr, dt: np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, dt)
+        return BreakpointBatch(int(b.min_gain), arr(b.examined, np.uint8).astype(bool), *[arr(getattr(b, f), dt) for f, dt in cls.WORDS], int(b.n_examined),
+                               int(b.n_reported), float(b.seconds_kernels), int(b.lookups))
+
+    def add_batch(self, searcher: Searcher, saved: "SavedBatch") -> BreakpointBatch:
+        b = _lib.BreakpointBatch()
+        check(self._L.taxor_gpu_breakpoint_add_batch(self._h, searcher._h, saved._h if saved is not None else None, C.byref(b)))
+        return self._batch(b)
+
+    def add_csr(self, read_off, user_bin, count, hash_off, hashes) -> BreakpointBatch:
+        ro = np.ascontiguousarray(read_off, dtype=np.uint64)
+        ub = np.ascontiguousarray(user_bin, dtype=np.int64)
+        ct = np.ascontiguousarray(count, dtype=np.uint32)
+        ho = np.ascontiguousarray(hash_off, dtype=np.uint64)
+        hs = np.ascontiguousarray(hashes, dtype=np.uint64)
+        assert ro.size >= 1 and ho.size == ro.size and ub.size == ct.size and int(ro[-1]) <= ub.size and int(ho[-1]) <= hs.size
+        b = _lib.BreakpointBatch()
+        check(self._L.taxor_gpu_breakpoint_add_csr(self._h, ro.size - 1, _p(ro), _p(ub) if ub.size else None, _p(ct) if ct.size else None, _p(ho),
+                                                   _p(hs) if hs.size else None, C.byref(b)))
+        return self._batch(b)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.taxor_gpu_breakpoint_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Comm:
     """Several GPUs of one node driven by this one process (the C++ host's `taxor search --gpus N` shape): the index is
     replicated (one upload + ncclBroadcast), every device classifies its own batch, results are gathered on devices[0].
