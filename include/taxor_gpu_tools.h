@@ -881,6 +881,68 @@ int taxor_gpu_breakpoint_add_csr(taxor_gpu_breakpoint *bp, uint64_t n_reads, con
                                  const uint64_t *hash_off, const uint64_t *hashes, taxor_breakpoint_batch *out);
 void taxor_gpu_breakpoint_destroy(taxor_gpu_breakpoint *bp);
 
+/* ---- paint a read with its references (`taxor search --segments-file`; taxor_amd/csrc/segments.hip and segments_format.h, DESIGN.md
+ * section 10.7).  The breakpoint above is the best SINGLE split between two references; a chromosome read that carries a prophage
+ * (A | B | A), a three-way concatemer (A | B | C) and a read across a shared mobile element all come out of it as one break with an
+ * unexplained remainder.  This is the optimal segmentation of the read's ordered hash list among ALL its candidates, with a cost per
+ * switch: any number of segments, exact integer arithmetic; the single break, the insert and the mosaic are its special cases.
+ * For read r take n, h(0) .. h(n-1), the CANDIDATES c = 0 .. M-1 (all tuples of the read with count > 0, in CSR order), x_c(i), `single`
+ * and `best` exactly as defined above.  The read is EXAMINED when n > 0 and M >= 2; every word below is 0 for a read that is not.
+ * A path is s: [0, n) -> [0, M).  hits(s) = sum_i x_{s(i)}(i); switches(s) = the number of i >= 1 with s(i) != s(i-1);
+ * value(s) = (hits(s) - L * switches(s)) * 2^32 - switches(s) in signed 64 bits, L the switch cost, an integer in [1, 2^20].  In words:
+ * maximise hits minus L per switch; among the paths that do, take one with the fewest switches -- a switch that gains nothing is never
+ * reported.  A read with n >= 2^31 is refused by name: the value would leave 63 bits.
+ * The reported path is the one this recurrence builds; its tie rules are part of the definition.
+ *   V_c(0) = x_c(0) * 2^32.  For i >= 1: B(i-1) = max_c V_c(i-1); a(i-1) = the lowest c attaining it; J = B(i-1) - (L * 2^32 + 1);
+ *   sw_c(i) = (V_c(i-1) < J), so a tie stays; V_c(i) = x_c(i) * 2^32 + max(V_c(i-1), J).
+ *   End: e = a(n-1), value = B(n-1).  Backtrace: s(n-1) = e; for i = n-1 .. 1: s(i-1) = sw_{s(i)}(i) ? a(i-1) : s(i).
+ * Consequences: V never decreases and is never negative; sw_{a(i-1)}(i) is never set, so every switch changes the candidate;
+ * hits - L * switches >= single (the path that stays on `best` has value single * 2^32).
+ * Segments are the maximal runs of s; K = switches + 1.  Segment j carries [start_j, end_j), its candidate c_j,
+ * hits_j = sum_{i in segment} x_{c_j}(i) and best_hits_j, the same sum for `best`.  A read is REPORTED when it is examined and K >= 2.
+ * The SHAPE of a reported read (segments_format.h, on the host, from the user bins of its segments alone): `split` when K == 2,
+ * `insert` when K == 3 and segments 0 and 2 have the same user bin, `mosaic` otherwise.
+ * _create: `view` is the one the index was created from (only bins and fname_idx are read).  TAXOR_E_ARG naming the reason: a
+ * switch_cost of 0 or above 2^20; a paged index, by name.
+ * _add_batch: as taxor_gpu_breakpoint_add_batch, with its checks before any launch.  Scratch per examined read: 8 * M * ceil(n / 64)
+ * bytes of match masks, as many of switch words, 4 * 64 * ceil(n / 64) of a, 8 * M of state; groups of reads are held under a fixed
+ * budget of 2^23 mask words; a read that exceeds it by itself runs alone in scratch grown to fit, and an allocation that fails is
+ * TAXOR_E_NOMEM naming the bytes and the read: no read is skipped.  The result lies in page-locked host memory kept per searcher: valid
+ * until the next _add_batch on THAT searcher (or _destroy).
+ * _add_csr: the same over host arrays, as taxor_gpu_breakpoint_add_csr; a `user_bin` outside the index is refused before any launch;
+ * the same user bin may stand in several tuples; valid until the next _add_csr.
+ * _add calls may come from several threads.  Nothing depends on the launch geometry nor on the cut into pieces, groups and batches. */
+typedef struct taxor_gpu_segments taxor_gpu_segments;
+typedef struct {
+    uint64_t n_reads, n_examined, n_reported;
+    uint32_t switch_cost;
+    uint32_t n_groups;              /* groups of reads the scratch budget cut the examined reads into (0 when none is examined); never moves a result */
+    const uint8_t *examined;        /* [n_reads] 1: n > 0 and M >= 2 */
+    const uint32_t *n_candidates;   /* [n_reads] M */
+    const uint32_t *n;              /* [n_reads] n, 0 for a read that is not examined */
+    const uint32_t *n_hashes;       /* [n_reads] QHASH_COUNT of every read (_add_csr: the lists' lengths) */
+    const uint32_t *n_segments;     /* [n_reads] K: 0 when not examined, 1 when examined and unbroken */
+    const uint32_t *path_hits;      /* [n_reads] hits(s) of the reported path */
+    const uint32_t *path_switches;  /* [n_reads] K - 1 */
+    const uint32_t *single;         /* [n_reads] */
+    const uint64_t *tuple_best;     /* [n_reads] index of best in the batch CSR (_add_csr: in user_bin / count as given) */
+    const int64_t *bin_best;        /* [n_reads] its user bin */
+    const uint64_t *seg_off;        /* [n_reads + 1] a reported read's K segments are [seg_off[r], seg_off[r + 1]); none otherwise */
+    const uint32_t *seg_start;      /* per segment, in list order (null when no read is reported): [start, end) in the hash list */
+    const uint32_t *seg_end;
+    const uint64_t *seg_tuple;      /* index of the segment's candidate in the batch CSR */
+    const int64_t *seg_bin;         /* its user bin */
+    const uint32_t *seg_hits;       /* hits_j; their sum over a read is path_hits */
+    const uint32_t *seg_best_hits;  /* best_hits_j */
+    double seconds_kernels;         /* HIP-event time of this call's kernels */
+    uint64_t lookups;               /* (hash, leaf bin) lookups made by this call: three one-byte gathers each */
+} taxor_segments_batch;
+int taxor_gpu_segments_create(taxor_gpu_index *idx, const taxor_hixf_view *view, uint32_t switch_cost, taxor_gpu_segments **out);
+int taxor_gpu_segments_add_batch(taxor_gpu_segments *sg, taxor_gpu_searcher *s, const taxor_gpu_saved *saved, taxor_segments_batch *out);
+int taxor_gpu_segments_add_csr(taxor_gpu_segments *sg, uint64_t n_reads, const uint64_t *read_off, const int64_t *user_bin, const uint32_t *count,
+                               const uint64_t *hash_off, const uint64_t *hashes, taxor_segments_batch *out);
+void taxor_gpu_segments_destroy(taxor_gpu_segments *sg);
+
 /* ---- search straight from file bytes (taxor_amd/csrc/fastx_scan.hip): raw[0, n_bytes) holds whole records of one
  * kind, '>' (FASTA) or '@' (four-line FASTQ) -- what a reader cuts at record boundaries.  The device finds the records, packs their
  * sequences into the searcher's batch and runs the search; taxor_gpu_search_batch_end follows as after any _begin.  raw may be pageable

@@ -234,6 +234,16 @@ class BreakpointBatch(C.Structure):
                 ("seconds_kernels", C.c_double), ("lookups", C.c_uint64)]
 
 
+class SegmentsBatch(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_examined", C.c_uint64), ("n_reported", C.c_uint64), ("switch_cost", C.c_uint32), ("n_groups", C.c_uint32),
+                ("examined", C.POINTER(C.c_uint8)), ("n_candidates", C.POINTER(C.c_uint32)), ("n", C.POINTER(C.c_uint32)), ("n_hashes", C.POINTER(C.c_uint32)),
+                ("n_segments", C.POINTER(C.c_uint32)), ("path_hits", C.POINTER(C.c_uint32)), ("path_switches", C.POINTER(C.c_uint32)),
+                ("single", C.POINTER(C.c_uint32)), ("tuple_best", C.POINTER(C.c_uint64)), ("bin_best", C.POINTER(C.c_int64)),
+                ("seg_off", C.POINTER(C.c_uint64)), ("seg_start", C.POINTER(C.c_uint32)), ("seg_end", C.POINTER(C.c_uint32)),
+                ("seg_tuple", C.POINTER(C.c_uint64)), ("seg_bin", C.POINTER(C.c_int64)), ("seg_hits", C.POINTER(C.c_uint32)),
+                ("seg_best_hits", C.POINTER(C.c_uint32)), ("seconds_kernels", C.c_double), ("lookups", C.c_uint64)]
+
+
 class HitmapBatch(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_mapped", C.c_uint64), ("segments", C.c_uint32), ("reserved", C.c_uint32),
                 ("map_off", C.POINTER(C.c_uint64)), ("tuple", C.POINTER(C.c_uint64)), ("user_bin", C.POINTER(C.c_int64)),
@@ -306,6 +316,10 @@ SIGNATURES = {
     "taxor_gpu_breakpoint_add_batch": (C.c_int, [_P, _P, _P, C.POINTER(BreakpointBatch)]),
     "taxor_gpu_breakpoint_add_csr": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, C.POINTER(BreakpointBatch)]),
     "taxor_gpu_breakpoint_destroy": (None, [_P]),
+    "taxor_gpu_segments_create": (C.c_int, [_P, C.POINTER(HixfView), C.c_uint32, C.POINTER(_P)]),
+    "taxor_gpu_segments_add_batch": (C.c_int, [_P, _P, _P, C.POINTER(SegmentsBatch)]),
+    "taxor_gpu_segments_add_csr": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, C.POINTER(SegmentsBatch)]),
+    "taxor_gpu_segments_destroy": (None, [_P]),
     "taxor_gpu_hitmap_create": (C.c_int, [_P, C.POINTER(HixfView), C.c_uint32, C.POINTER(_P)]),
     "taxor_gpu_hitmap_add_batch": (C.c_int, [_P, _P, _P, C.POINTER(HitmapBatch)]),
     "taxor_gpu_hitmap_destroy": (None, [_P]),

@@ -162,6 +162,21 @@ struct Batch {
     };
     std::vector<BreakRow> bp_rows;
     bool bp_set = false;
+    // --segments-file: the chunk's REPORTED reads (segments.hip), in read order, and their segments in list order: row x's are
+    // sg_segs[x.first .. x.first + x.n_seg); sg_set says that the batch's share has arrived; n_hashes above comes with them when no TSV
+    // is written
+    struct SegRow {
+        uint32_t read, n_cand, n_seg, path_hits, single;
+        int64_t bin_best;
+        uint64_t first;
+    };
+    struct Seg {
+        uint32_t start, end, hits, best_hits;
+        int64_t bin;
+    };
+    std::vector<SegRow> sg_rows;
+    std::vector<Seg> sg_segs;
+    bool sg_set = false;
     // --device-parse: the chunk is a byte range of the file as read (whole records of kind raw_kind, '>' or '@'); the device finds
     // the records, ids and offsets are filled from its table and bases stays empty.  raw_kind 0: a parsed chunk, as above
     BaseBuf raw;

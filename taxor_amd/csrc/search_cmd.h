@@ -28,6 +28,8 @@ struct Config : ReaderOptions {              // taxor_search_configuration.hpp:8
     uint32_t hitmap_segments = 0;      // hidden --hitmap-segments: parts the ordered hash list is cut into, in [1,64] (0: 16)
     std::string breakpoint_file;       // --breakpoint-file: one line per read whose hash list splits between two of its references (breakpoint.hip)
     uint32_t breakpoint_min_gain = 0;  // --breakpoint-min-gain: hits the split must explain beyond the best single reference, >= 1 (0: not given, 1)
+    std::string segments_file;         // --segments-file: one line per segment of a read whose best path among its references switches (segments.hip)
+    uint32_t segments_switch_cost = 0; // --segments-switch-cost: hits a switch of reference costs, in [1,2^20] (0: not given, 16)
     std::string gather;         // several devices: "rccl" | "host" (taxor_gpu_comm transports) | "none" (independent workers, each
                                 // fetching its own results); empty = rccl when the devices are distinct, host when one repeats
 };
@@ -80,6 +82,11 @@ void usage()
             "                           the two references and the hits the split explains beyond the best single reference (a chimeric read,\n"
             "                           an inserted element, a host/microbe junction); ONE index file, ONE device; --output-file is then optional\n"
             "  --breakpoint-min-gain <n> with --breakpoint-file: report a read from this many hits gained on (default 1)\n"
+            "  --segments-file <f>      per read whose ordered hash list is best explained by SEVERAL of the references it reported, one after the\n"
+            "                           other: one line per segment (where it lies, its reference, its hits) and the read's shape, split, insert or\n"
+            "                           mosaic (a chimeric read, a prophage or IS element inside a chromosome read, a concatemer); ONE index file,\n"
+            "                           ONE device; --output-file is then optional\n"
+            "  --segments-switch-cost <n> with --segments-file: the hits a switch of reference must pay for, in [1,1048576] (default 16)\n"
             "  --expect <tsv>           compare the output per read with a TSV the reference wrote for the same input (exit 3 if it differs)\n"
             "search to profile in one run (the options of `taxor profile`; results go from the device's search buffers into the profile's\n"
             "device pipeline, no TSV is written or parsed in between):\n"
@@ -176,6 +183,26 @@ void advanced_help()
                     "                           never reported and cannot be a candidate: lower --percentage to look for short inserts.  The searchers keep\n"
                     "                           every batch's hash lists in host memory until the batch is examined.  Refused: a comma list of index\n"
                     "                           files, several devices, a --gather transport, and an index that has to be paged.\n"
+                    "  --segments-file <f>      columns QUERY_NAME, QUERY_LEN, QHASH_COUNT, CANDIDATES, SEGMENTS, SHAPE, PATH_HITS, SINGLE_HITS, SEGMENT, HASH_START,\n"
+                    "                           HASH_END, BASE_START_APPROX, BASE_END_APPROX, ACCESSION, TAXID, HITS, BEST_ACCESSION, BEST_TAXID, HITS_OF_BEST; one\n"
+                    "                           line per segment of a reported read, reads in input order, SEGMENT counting from 0.  Candidates, examined\n"
+                    "                           reads and the lookup are --breakpoint-file's.  A path gives every hash of the ordered list to one candidate;\n"
+                    "                           it scores the hashes that match the candidate they were given to, minus --segments-switch-cost for every\n"
+                    "                           change of candidate.  The best path is found exactly (a Viterbi pass on the device); among equally good\n"
+                    "                           paths the one with the fewest switches is taken, so a switch that gains nothing is never reported, and\n"
+                    "                           equal candidates go to the first in the search's order.  A read is written when its path has two segments\n"
+                    "                           or more.  SHAPE, from the references of the segments alone: split (two segments), insert (three, the outer\n"
+                    "                           two the same reference: a prophage, an IS element), mosaic (anything else).  PATH_HITS is the sum of HITS,\n"
+                    "                           SINGLE_HITS the hits of the best single candidate (BEST_*), HITS_OF_BEST that candidate's hits inside the\n"
+                    "                           segment; PATH_HITS - cost * (SEGMENTS - 1) >= SINGLE_HITS.  BASE_*_APPROX = floor(HASH_* * QUERY_LEN /\n"
+                    "                           QHASH_COUNT): the list carries no positions (--hitmap-file's caveat).  A partner that did not pass the\n"
+                    "                           search threshold was never reported and cannot be a candidate: lower --percentage to look for short\n"
+                    "                           inserts.  Beside --breakpoint-file every hash is looked up twice, once per option.  Refused: a comma list of\n"
+                    "                           index files, several devices, a --gather transport, and an index that has to be paged.\n"
+                    "  --segments-switch-cost <n> with --segments-file: an integer in [1,1048576], default 16.  The default is a choice, not a measurement: at\n"
+                    "                           k = 22, s = 12 about one base in 11 starts a syncmer, so 16 hits are roughly 180 bases of exact match, and\n"
+                    "                           an inner segment, which pays twice, has to beat its flank by some 350 bases' worth of hits -- less than the\n"
+                    "                           mobile elements people look for.\n"
                     "  --paged-reread           the default said aloud: read the query file again in every pass; wins over --paged-replay.\n"
                     "BAM input: the BGZF blocks are inflated on --threads threads, one thread walks the records (block_size, flag, l_seq, read_name)\n"
                     "                           and copies the 4-bit SEQ fields into a page-locked buffer; CIGAR, QUAL and tags are never read.  A\n"
@@ -460,6 +487,11 @@ struct SearchRun {
     std::vector<uint32_t> breakpoint_species; // user bin -> the species the TSV names for it
     double t_breakpoint = 0, t_breakpoint_kernels = 0;   // seconds inside taxor_gpu_breakpoint_add_batch and in its kernels, summed over workers
     uint64_t breakpoint_lookups = 0, breakpoint_lines = 0, breakpoint_examined = 0, breakpoint_reads = 0;
+    taxor_gpu_segments *segments = nullptr;   // --segments-file: the object beside the resident index, for the whole run (segments.hip)
+    FILE *segments_out = nullptr;             // --segments-file; written by the sequencer as well
+    std::vector<uint32_t> segments_species;   // user bin -> the species the TSV names for it
+    double t_segments = 0, t_segments_kernels = 0;       // seconds inside taxor_gpu_segments_add_batch and in its kernels, summed over workers
+    uint64_t segments_lookups = 0, segments_lines = 0, segments_reported = 0, segments_examined = 0, segments_reads = 0, segments_groups = 0;
     std::atomic<uint64_t> lca_next_read{0};   // the next batch's first read as the accumulator numbers it
     double t_lca = 0;               // seconds inside taxor_gpu_lca_add_batch, summed over workers
     double t_coverage = 0;          // seconds inside taxor_gpu_coverage_add_batch (taking and freeing the saved lists included), summed over workers
@@ -568,6 +600,15 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             if (n < 1 || n > 4294967295.0) die("Validation failed for option --breakpoint-min-gain: Value not in range [1,4294967295].");
             cfg.breakpoint_min_gain = (uint32_t)n;
         }
+        else if (k == "--segments-file") {
+            cfg.segments_file = val();
+            if (cfg.segments_file.empty()) die("Validation failed for option --segments-file: the file name is empty.");
+        }
+        else if (k == "--segments-switch-cost") {
+            const double n = num(val(), true);
+            if (n < 1 || n > (double)taxor::SEGMENTS_MAX_SWITCH_COST) die("Validation failed for option --segments-switch-cost: Value not in range [1,1048576].");
+            cfg.segments_switch_cost = (uint32_t)n;
+        }
         else if (k == "--report-file") {
             cfg.kraken_file = val();
             if (cfg.kraken_file.empty()) die("Validation failed for option --report-file: the file name is empty.");
@@ -668,7 +709,18 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             die("Validation failed for option --gather: --breakpoint-file runs on ONE device, where nothing is gathered; leave --gather out.");
         if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
     }
-    run.write_tsv = !(run.profile_mode || cfg.lca_mode() || !cfg.hitmap_file.empty() || !cfg.breakpoint_file.empty()) || !cfg.report_file.empty();
+    if (cfg.segments_switch_cost && cfg.segments_file.empty()) die("Option --segments-switch-cost says what a switch costs in --segments-file: it needs that option.");
+    if (!cfg.segments_file.empty()) {   // before any HIP call
+        if (cfg.index_file.find(',') != std::string::npos)
+            die("Validation failed for option --index-file: --segments-file takes ONE index file (a read's hashes are looked up in the leaf bins of the index its references belong to); "
+                "search the indexes one by one.");
+        if (cfg.gpus.size() > 1)
+            die("Validation failed for option " + run.gpus_option + ": --segments-file examines on ONE device (a batch's hash lists and its results must lie on the same one); give --gpu <id>.");
+        if (!cfg.gather.empty() && cfg.gather != "none")
+            die("Validation failed for option --gather: --segments-file runs on ONE device, where nothing is gathered; leave --gather out.");
+        if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
+    }
+    run.write_tsv = !(run.profile_mode || cfg.lca_mode() || !cfg.hitmap_file.empty() || !cfg.breakpoint_file.empty() || !cfg.segments_file.empty()) || !cfg.report_file.empty();
     if (cfg.threads == 0) {
         // --threads not given.  The reference's default is one worker thread (taxor_search_configuration.hpp:17) -- there the
         // thread that classifies; here host threads only parse the query file and render text for the GPU, and one of them
@@ -1138,6 +1190,7 @@ struct ReportWriter {
                 if (run.lca_out) write_lca_lines(bt);
                 if (run.hitmap_out) write_hitmap_lines(bt);
                 if (run.breakpoint_out) write_breakpoint_lines(*hd->b);
+                if (run.segments_out) write_segments_lines(*hd->b);
                 if (n == 0 || !run.write_tsv) { chunk_done(hd); continue; }
                 // cut where the estimated text passes piece_bytes
                 const uint64_t per_tuple = line_bytes_guess.load();
@@ -1233,6 +1286,37 @@ struct ReportWriter {
         run.breakpoint_lines += bt.bp_rows.size();
         if (!breakpoint_text.empty() && fwrite(breakpoint_text.data(), 1, breakpoint_text.size(), run.breakpoint_out) != breakpoint_text.size())
             die("cannot write to " + run.cfg.breakpoint_file + ": " + strerror(errno));
+    }
+    // --segments-file: the chunk's reported reads, one line per segment, by the sequencer (segments_format.h)
+    std::string segments_text;
+    std::vector<int64_t> segments_bins;
+    void write_segments_lines(Batch &bt)
+    {
+        const size_t n = bt.ids.size();
+        if (!bt.sg_set || bt.n_hashes.size() != n) die("internal: a chunk reached the writer without its reads' segments");
+        bt.sg_set = false;
+        const taxor_hixf_meta *meta = taxor_hixf_get_meta(h);
+        auto ref = [&](int64_t bin) {     // the species `taxor_format_read` prints for the user bin
+            const uint64_t b = (uint64_t)bin;
+            const taxor_species *sp = meta->n_species ? &meta->species[b < run.segments_species.size() ? run.segments_species[b] : 0] : nullptr;
+            return taxor::breakpoint_ref{sp ? sp->accession_id : nullptr, sp ? sp->taxid : nullptr};
+        };
+        segments_text.clear();
+        for (const Batch::SegRow &x : bt.sg_rows) {
+            if (x.read >= n || x.n_seg < 2 || x.first + x.n_seg > bt.sg_segs.size()) die("internal: a segmented read lies outside its chunk");
+            segments_bins.clear();
+            for (uint32_t j = 0; j < x.n_seg; ++j) segments_bins.push_back(bt.sg_segs[x.first + j].bin);
+            const char *shape = taxor::segments_shape(x.n_seg, segments_bins.data());
+            for (uint32_t j = 0; j < x.n_seg; ++j) {
+                const Batch::Seg &sg = bt.sg_segs[x.first + j];
+                taxor::segments_line(segments_text, bt.ids.ptr(x.read), bt.ids.len(x.read), bt.offsets[x.read + 1] - bt.offsets[x.read], bt.n_hashes[x.read], x.n_cand,
+                                     x.n_seg, shape, x.path_hits, x.single, j, sg.start, sg.end, ref(sg.bin), sg.hits, ref(x.bin_best), sg.best_hits);
+            }
+            run.segments_lines += x.n_seg;
+        }
+        run.segments_reported += bt.sg_rows.size();
+        if (!segments_text.empty() && fwrite(segments_text.data(), 1, segments_text.size(), run.segments_out) != segments_text.size())
+            die("cannot write to " + run.cfg.segments_file + ": " + strerror(errno));
     }
     // a piece's text goes to the file when its ticket comes up
     void write_in_turn(const Piece &pc, const char *text, uint64_t need)
@@ -1398,6 +1482,23 @@ void finish_breakpoint(SearchRun &run)
     run.breakpoint = nullptr;
 }
 
+// ---- `--segments-file`: the lines were written chunk by chunk; the file is closed here
+void finish_segments(SearchRun &run)
+{
+    if (run.segments_out) {
+        if (ferror(run.segments_out) || fclose(run.segments_out) != 0) die("cannot write to " + run.cfg.segments_file + ": " + strerror(errno));
+        run.segments_out = nullptr;
+    }
+    if (tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] segments: %llu lines from %llu reported reads of %llu examined reads of %llu; %.3f s inside the segmenting (summed over workers), %.6f s in its "
+                        "kernels, %llu lookups of a hash in a leaf bin, %llu groups of reads under the scratch budget\n",
+                (unsigned long long)run.segments_lines, (unsigned long long)run.segments_reported, (unsigned long long)run.segments_examined,
+                (unsigned long long)run.segments_reads, run.t_segments, run.t_segments_kernels, (unsigned long long)run.segments_lookups,
+                (unsigned long long)run.segments_groups);
+    taxor_gpu_segments_destroy(run.segments);
+    run.segments = nullptr;
+}
+
 // ---- `--report-file`: the run's tallies, fetched once, rolled up the tree on the host (a few hundred thousand nodes at most, once per
 // run) and written as a Kraken-style report; `--lca-file` is closed here as well.  The layout: percentage of
 // the clade, clade count, direct count, rank code, taxid, name indented by two spaces per depth; unclassified first, then the tree from
@@ -1535,7 +1636,7 @@ struct GpuStage {
             for (unsigned w = 0; w < wpg; ++w)
                 if (taxor_gpu_searcher_create(gidx[g], &prm, &sr[g * wpg + w]) != TAXOR_OK) die(taxor_gpu_last_error());
     }
-    // --coverage-file / --hitmap-file / --lca-confidence / --breakpoint-file: the consumers beside the (one) index, and every searcher leaves its batches' hash lists for them
+    // --coverage-file / --hitmap-file / --lca-confidence / --breakpoint-file / --segments-file: the consumers beside the (one) index, and every searcher leaves its batches' hash lists for them
     void begin_saved_consumers(const taxor_hixf_view *view, const taxor_hixf_meta *meta)
     {
         const Config &cfg = run.cfg;
@@ -1554,6 +1655,13 @@ struct GpuStage {
             run.breakpoint_species.assign(view->n_user_bins, 0u);     // as for the hit map
             for (uint64_t i = meta->n_species; i-- > 0;)
                 if (meta->species[i].user_bin < view->n_user_bins) run.breakpoint_species[meta->species[i].user_bin] = (uint32_t)i;
+        }
+        if (!cfg.segments_file.empty()) {
+            if (taxor_gpu_segments_create(gidx[0], view, cfg.segments_switch_cost ? cfg.segments_switch_cost : taxor::SEGMENTS_DEFAULT_SWITCH_COST, &run.segments) != TAXOR_OK)
+                die(taxor_gpu_last_error());
+            run.segments_species.assign(view->n_user_bins, 0u);       // as for the hit map
+            for (uint64_t i = meta->n_species; i-- > 0;)
+                if (meta->species[i].user_bin < view->n_user_bins) run.segments_species[meta->species[i].user_bin] = (uint32_t)i;
         }
         for (auto *s : sr)
             if (taxor_gpu_search_capture(s, 1) != TAXOR_OK) die(taxor_gpu_last_error());
@@ -1633,9 +1741,34 @@ struct GpuStage {
             }
         }
         const double c3c = now();
+        // --segments-file: the reported reads of the batch and their segments go to the chunks that hold them
+        taxor_segments_batch gb{};
+        if (rc == TAXOR_OK && run.segments) rc = taxor_gpu_segments_add_batch(run.segments, s, sv, &gb);
+        if (rc == TAXOR_OK && run.segments) {
+            uint64_t nr = 0;
+            for (auto &bt : group) nr += bt->ids.size();
+            if (gb.n_reads != nr) die("internal: a batch's segments do not cover its chunks");
+            uint64_t r0 = 0;
+            for (auto &bt : group) {
+                const uint64_t n = bt->ids.size();
+                bt->sg_rows.clear();
+                bt->sg_segs.clear();
+                for (uint64_t i = 0; i < n; ++i) {
+                    const uint64_t r = r0 + i, k = gb.seg_off[r + 1] - gb.seg_off[r];
+                    if (k == 0) continue;
+                    bt->sg_rows.push_back(Batch::SegRow{(uint32_t)i, gb.n_candidates[r], (uint32_t)k, gb.path_hits[r], gb.single[r], gb.bin_best[r], bt->sg_segs.size()});
+                    for (uint64_t j = gb.seg_off[r]; j < gb.seg_off[r + 1]; ++j)
+                        bt->sg_segs.push_back(Batch::Seg{gb.seg_start[j], gb.seg_end[j], gb.seg_hits[j], gb.seg_best_hits[j], gb.seg_bin[j]});
+                }
+                bt->sg_set = true;
+                if (!run.write_tsv) bt->n_hashes.assign(gb.n_hashes + r0, gb.n_hashes + r0 + n);
+                r0 += n;
+            }
+        }
+        const double c3d = now();
         taxor_gpu_saved_free(sv);
         if (rc != TAXOR_OK) die(taxor_gpu_last_error());
-        const double c4 = now(), shared = (c1 - c0) + (c4 - c3c);       // taking and freeing the lists: the first consumer's
+        const double c4 = now(), shared = (c1 - c0) + (c4 - c3d);       // taking and freeing the lists: the first consumer's
         std::lock_guard<std::mutex> lk(run.stat_mu);
         if (run.confidence) {
             run.t_confidence += c3b - c3 + (run.coverage || run.hitmap ? 0.0 : shared);
@@ -1650,6 +1783,14 @@ struct GpuStage {
             run.breakpoint_lookups += bb.lookups;
             run.breakpoint_examined += bb.n_examined;
             run.breakpoint_reads += bb.n_reads;
+        }
+        if (run.segments) {
+            run.t_segments += c3d - c3c + (run.coverage || run.hitmap || run.confidence || run.breakpoint ? 0.0 : shared);
+            run.t_segments_kernels += gb.seconds_kernels;
+            run.segments_lookups += gb.lookups;
+            run.segments_examined += gb.n_examined;
+            run.segments_reads += gb.n_reads;
+            run.segments_groups += gb.n_groups;
         }
         if (run.coverage) run.t_coverage += c2 - c1 + shared;
         if (run.hitmap) {
@@ -1896,7 +2037,7 @@ struct GpuStage {
             // without a TSV nothing on the host reads the tuples: they stay on the device for the profile feed
             if (classify(sr[wi], group, scanned, run.write_tsv ? &res : nullptr) != TAXOR_OK) die(taxor_gpu_last_error());
             if (run.profile_mode) feed_profile(sr[wi], group);
-            if (run.coverage || run.hitmap || run.confidence || run.breakpoint) use_saved(sr[wi], group);
+            if (run.coverage || run.hitmap || run.confidence || run.breakpoint || run.segments) use_saved(sr[wi], group);
             if (run.lca) add_lca(sr[wi], group);
             --n_running;
             const double t3 = now();
@@ -1985,7 +2126,8 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
     const double t_search0 = now();
     if (run.profile_mode) run.fused.begin(view, taxor_hixf_get_meta(h), run.prof.device);
     gpu.create_searchers(prm);
-    if (!cfg.coverage_file.empty() || !cfg.hitmap_file.empty() || cfg.confidence_mode() || !cfg.breakpoint_file.empty()) gpu.begin_saved_consumers(view, taxor_hixf_get_meta(h));
+    if (!cfg.coverage_file.empty() || !cfg.hitmap_file.empty() || cfg.confidence_mode() || !cfg.breakpoint_file.empty() || !cfg.segments_file.empty())
+        gpu.begin_saved_consumers(view, taxor_hixf_get_meta(h));
     // (with --lca-confidence the confident calls fill both files: the plain accumulator is not created)
     if (run.lineage && !run.confidence && taxor_gpu_lca_create(gpu.gidx[0], run.lineage, &run.lca) != TAXOR_OK) die(taxor_gpu_last_error());
     gpu.run_workers();
@@ -2022,6 +2164,10 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
     if (run.breakpoint) {
         finish_breakpoint(run);
         trace("breaks written");
+    }
+    if (run.segments) {
+        finish_segments(run);
+        trace("segments written");
     }
     gpu.release();
     if (run.profile_mode) {
@@ -2127,6 +2273,13 @@ void search_files(SearchRun &run, const std::string &hixf_file, const std::vecto
         if (budget)
             die("Validation failed for option --breakpoint-file: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
                 std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; finding breaks pass by pass is not built.");
+    }
+    if (!cfg.segments_file.empty()) {
+        // as for --breakpoint-file
+        if (budget && cfg.index_budget_mib && whole.index_bytes <= budget) budget = 0;
+        if (budget)
+            die("Validation failed for option --segments-file: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
+                std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; segmenting pass by pass is not built.");
     }
     if (cfg.confidence_mode()) {
         // a read's hashes are looked up in ALL the leaf bins of its references, and its final tuples exist only after the last pass's merge

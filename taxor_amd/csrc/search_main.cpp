@@ -17,6 +17,7 @@
 #include "confidence_format.h"
 #include "hitmap_format.h"
 #include "key_store.h"
+#include "segments_format.h"
 using taxor::tune_env;
 extern char **environ;
 
@@ -122,6 +123,11 @@ int main(int argc, char **argv)
         run.breakpoint_out = fopen(cfg.breakpoint_file.c_str(), "wb");
         if (!run.breakpoint_out) die("cannot open breakpoint file " + cfg.breakpoint_file);
         fputs(taxor::breakpoint_header(), run.breakpoint_out);
+    }
+    if (!cfg.segments_file.empty()) {
+        run.segments_out = fopen(cfg.segments_file.c_str(), "wb");
+        if (!run.segments_out) die("cannot open segments file " + cfg.segments_file);
+        fputs(taxor::segments_header(), run.segments_out);
     }
     if (index_files.size() == 1) {
         search_files(run, index_files[0], query_files, true);

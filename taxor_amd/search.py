@@ -1052,6 +1052,100 @@ class Breakpoints:
         self.close()
 
 
+@dataclass
+class SegmentsBatch:
+    """Segments.add_batch() / add_csr(): per read the words of include/taxor_gpu_tools.h (all 0 for a read that is not examined), every
+    read's hash count, and the segments of the reported reads (n_segments >= 2) in list order: read r's are [seg_off[r], seg_off[r+1])"""
+    switch_cost: int
+    examined: np.ndarray      # bool[n_reads]
+    n_candidates: np.ndarray  # uint32[n_reads] M
+    n: np.ndarray             # the hash count of an examined read
+    n_hashes: np.ndarray      # of every read
+    n_segments: np.ndarray    # K: 0 not examined, 1 examined and unbroken
+    path_hits: np.ndarray
+    path_switches: np.ndarray
+    single: np.ndarray
+    tuple_best: np.ndarray    # uint64[n_reads] index in the batch CSR
+    bin_best: np.ndarray      # int64[n_reads]
+    seg_off: np.ndarray       # uint64[n_reads + 1]
+    seg_start: np.ndarray     # uint32 per segment
+    seg_end: np.ndarray
+    seg_tuple: np.ndarray     # uint64
+    seg_bin: np.ndarray       # int64
+    seg_hits: np.ndarray      # uint32
+    seg_best_hits: np.ndarray
+    n_examined: int
+    n_reported: int
+    seconds_kernels: float
+    lookups: int
+    n_groups: int = 0         # groups of reads the scratch budget cut the examined reads into
+
+    @property
+    def reported(self):
+        return self.examined & (self.n_segments >= 2)
+
+
+class Segments:
+    """Paint a read with its references (taxor_amd/csrc/segments.hip): the optimal segmentation of its ordered hash list among all its
+    candidates, `switch_cost` hits per switch.  `ixfs` is the list the GpuIndex was made from (only bins and fname_idx are read).
+    add_batch follows a batch that ran with Searcher.capture() on and takes its SavedBatch, which stays the caller's; add_csr takes host
+    arrays.  The arrays returned are copies."""
+
+    WORDS = (("n_candidates", np.uint32), ("n", np.uint32), ("n_hashes", np.uint32), ("n_segments", np.uint32), ("path_hits", np.uint32),
+             ("path_switches", np.uint32), ("single", np.uint32), ("tuple_best", np.uint64), ("bin_best", np.int64))
+    SEG_WORDS = (("seg_start", np.uint32), ("seg_end", np.uint32), ("seg_tuple", np.uint64), ("seg_bin", np.int64), ("seg_hits", np.uint32),
+                 ("seg_best_hits", np.uint32))
+
+    def __init__(self, index: GpuIndex, ixfs, switch_cost=16):
+        view, keep = GpuIndex._view([dict(f, data=None) for f in ixfs], index.n_user_bins, index.k, index.s, index.t, index.use_syncmer, 1,
+                                    index.window_size)
+        self._L = _lib.lib()
+        self._h = C.c_void_p()
+        self.index, self.switch_cost = index, int(switch_cost)
+        check(self._L.taxor_gpu_segments_create(index._h, C.byref(view), int(switch_cost), C.byref(self._h)))
+        del keep
+
+    @classmethod
+    def _batch(cls, b):
+        n = int(b.n_reads)
+        arr = lambda ptr, dt, m: np.ctypeslib.as_array(ptr, shape=(m,)).copy() if m else np.zeros(0, dt)
+        seg_off = np.ctypeslib.as_array(b.seg_off, shape=(n + 1,)).copy()
+        ns = int(seg_off[n])
+        return SegmentsBatch(int(b.switch_cost), arr(b.examined, np.uint8, n).astype(bool), *[arr(getattr(b, f), dt, n) for f, dt in cls.WORDS], seg_off,
+                             *[arr(getattr(b, f), dt, ns) for f, dt in cls.SEG_WORDS], int(b.n_examined), int(b.n_reported), float(b.seconds_kernels),
+                             int(b.lookups), int(b.n_groups))
+
+    def add_batch(self, searcher: Searcher, saved: "SavedBatch") -> SegmentsBatch:
+        b = _lib.SegmentsBatch()
+        check(self._L.taxor_gpu_segments_add_batch(self._h, searcher._h, saved._h if saved is not None else None, C.byref(b)))
+        return self._batch(b)
+
+    def add_csr(self, read_off, user_bin, count, hash_off, hashes) -> SegmentsBatch:
+        ro = np.ascontiguousarray(read_off, dtype=np.uint64)
+        ub = np.ascontiguousarray(user_bin, dtype=np.int64)
+        ct = np.ascontiguousarray(count, dtype=np.uint32)
+        ho = np.ascontiguousarray(hash_off, dtype=np.uint64)
+        hs = np.ascontiguousarray(hashes, dtype=np.uint64)
+        assert ro.size >= 1 and ho.size == ro.size and ub.size == ct.size and int(ro[-1]) <= ub.size and int(ho[-1]) <= hs.size
+        b = _lib.SegmentsBatch()
+        check(self._L.taxor_gpu_segments_add_csr(self._h, ro.size - 1, _p(ro), _p(ub) if ub.size else None, _p(ct) if ct.size else None, _p(ho),
+                                                 _p(hs) if hs.size else None, C.byref(b)))
+        return self._batch(b)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.taxor_gpu_segments_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Comm:
     """Several GPUs of one node driven by this one process (the C++ host's `taxor search --gpus N` shape): the index is
     replicated (one upload + ncclBroadcast), every device classifies its own batch, results are gathered on devices[0].
