@@ -943,6 +943,76 @@ int taxor_gpu_segments_add_csr(taxor_gpu_segments *sg, uint64_t n_reads, const u
                                const uint64_t *hash_off, const uint64_t *hashes, taxor_segments_batch *out);
 void taxor_gpu_segments_destroy(taxor_gpu_segments *sg);
 
+/* ---- hashes only one reference explains (`taxor search --exclusive-file` / `--exclusive-reads-file`; taxor_amd/csrc/exclusive.hip and
+ * exclusive_format.h).  Near-identical references all pass the 0.8 * max filter with almost the same count; the
+ * coverage table counts a shared hash for each of them and the LCA confidence counts it once for none.  This says which of the
+ * references a read reported holds hashes that none of the others on that read's list holds, and how many.
+ * For read r take n, h(0) .. h(n-1), T (ALL its tuples in the batch CSR), the CANDIDATES c = 0 .. M-1 (the tuples of T with count > 0, in
+ * CSR order) and x_c(i) exactly as defined for the breakpoint above.  The read is EXAMINED when n > 0 and M >= 1 -- one candidate is
+ * enough here; every word below is 0 for a read that is not.  All arithmetic is integer.
+ *   k(i) = sum_c x_c(i).  Hash i is EXCLUSIVE TO c when x_c(i) == 1 and k(i) == 1, SHARED when k(i) >= 2, UNMATCHED when k(i) == 0.
+ *   Per candidate: hits_c = sum_i x_c(i) -- the hit map's located hashes, which for a split user bin may differ from the tuple's count,
+ *   as said there; excl_c = #{i : i exclusive to c}.  Per read: shared = #{i : k(i) >= 2}, matched = #{i : k(i) >= 1}.
+ *   Hence sum_c excl_c + shared == matched <= n; excl_c <= hits_c; sum_c hits_c >= matched; M == 1 gives excl_0 == hits_0.
+ * A user bin that stands in two tuples of one read is possible only in hand-made input (_add_csr): both candidates then match the same
+ * hashes, so neither has an exclusive one.  That follows from the definition and is not treated specially.
+ * Per user bin b, summed over every examined read and every candidate c of it whose user bin is b, in 64 bits on the device:
+ *   cand_reads[b] += 1, hits[b] += hits_c, exclusive_hits[b] += excl_c, exclusive_reads[b] += (excl_c > 0);
+ * and every hash exclusive to c goes into b's HyperLogLog sketch: (i, rho) = taxor_hll_slot(h, P), registers[b][i] = max(registers[b][i], rho)
+ * -- the coverage accumulator's slot, byte registers and estimator (taxor_hll_estimate).
+ * Exclusivity is relative to the references the read REPORTED: a reference below the search threshold is not a tuple and takes no hash
+ * away.  And fingerprints have 8 bits: a foreign leaf bin answers yes at about 1/256, so a truly exclusive hash is lost at about (leaf
+ * bins of the other candidates) / 256 and a candidate that shares nothing still shows about n * leaves / 256 hits, most of them exclusive.
+ * _create: precision P in [4, 16], 0 = 12; `view` is the one the index was created from (only bins and fname_idx are read).  The
+ * registers (n_user_bins << P bytes) and the counters are held against the device's free memory first: TAXOR_E_NOMEM with both
+ * figures.  A paged index is refused by name (TAXOR_E_ARG).
+ * _add_batch: as taxor_gpu_breakpoint_add_batch, with its checks before any launch, TAXOR_E_ARG naming the field.  Scratch per examined
+ * read is 8 * M bytes (hits and excl, which are the result) beside two words per read of the batch; there is no per-hash array, so
+ * reads are not grouped under a budget and none is skipped.  Only the lists of examined reads are staged, through a bounded device
+ * buffer.  The batch lies in page-locked host memory kept per searcher: valid until the next _add_batch on THAT searcher (or _destroy).
+ * _add_csr: the same over host arrays, as taxor_gpu_breakpoint_add_csr; a `user_bin` outside the index is refused before any launch;
+ * valid until the next _add_csr.
+ * _results: the run's sums and registers; host pointers, valid until _destroy or the next _results.
+ * _add calls may come from several threads.  Sums are integer additions and registers a maximum: nothing depends on the launch geometry,
+ * the order of the calls nor on the cut into pieces and batches. */
+typedef struct taxor_gpu_exclusive taxor_gpu_exclusive;
+typedef struct {
+    uint64_t n_reads, n_examined, n_cand;   /* n_cand = cand_off[n_reads]: the candidates of the examined reads */
+    uint32_t precision, reserved;
+    const uint8_t *examined;        /* [n_reads] 1: n > 0 and M >= 1 */
+    const uint32_t *n_candidates;   /* [n_reads] M */
+    const uint32_t *n;              /* [n_reads] n, 0 for a read that is not examined */
+    const uint32_t *matched;        /* [n_reads] */
+    const uint32_t *shared;         /* [n_reads] */
+    const uint32_t *n_hashes;       /* [n_reads] QHASH_COUNT of every read (_add_csr: the lists' lengths) */
+    const uint64_t *cand_off;       /* [n_reads + 1] an examined read's M candidates are [cand_off[r], cand_off[r + 1]); none otherwise */
+    const uint64_t *cand_tuple;     /* per candidate, in CSR order (null when no read is examined): index in the batch CSR (_add_csr: in
+                                       user_bin / count as given) */
+    const int64_t *cand_bin;        /* its user bin */
+    const uint32_t *cand_count;     /* the tuple's count (QHASH_MATCH) */
+    const uint32_t *cand_hits;      /* hits_c */
+    const uint32_t *cand_excl;      /* excl_c */
+    double seconds_kernels;         /* HIP-event time of this call's kernels */
+    uint64_t probes;                /* (hash, leaf bin) lookups made by this call: three one-byte gathers each */
+} taxor_exclusive_batch;
+typedef struct {
+    uint64_t n_user_bins;
+    uint32_t precision, reserved;
+    const uint64_t *cand_reads;       /* [n_user_bins] */
+    const uint64_t *hits;             /* [n_user_bins] */
+    const uint64_t *exclusive_hits;   /* [n_user_bins] */
+    const uint64_t *exclusive_reads;  /* [n_user_bins] */
+    const uint8_t *registers;         /* [n_user_bins << precision] user bin b's sketch at registers + (b << precision) */
+    double seconds_kernels;           /* summed over the calls */
+    uint64_t probes;
+} taxor_exclusive_results;
+int taxor_gpu_exclusive_create(taxor_gpu_index *idx, const taxor_hixf_view *view, uint32_t precision, taxor_gpu_exclusive **out);
+int taxor_gpu_exclusive_add_batch(taxor_gpu_exclusive *ex, taxor_gpu_searcher *s, const taxor_gpu_saved *saved, taxor_exclusive_batch *out);
+int taxor_gpu_exclusive_add_csr(taxor_gpu_exclusive *ex, uint64_t n_reads, const uint64_t *read_off, const int64_t *user_bin, const uint32_t *count,
+                                const uint64_t *hash_off, const uint64_t *hashes, taxor_exclusive_batch *out);
+int taxor_gpu_exclusive_results(taxor_gpu_exclusive *ex, taxor_exclusive_results *out);
+void taxor_gpu_exclusive_destroy(taxor_gpu_exclusive *ex);
+
 /* ---- search straight from file bytes (taxor_amd/csrc/fastx_scan.hip): raw[0, n_bytes) holds whole records of one
  * kind, '>' (FASTA) or '@' (four-line FASTQ) -- what a reader cuts at record boundaries.  The device finds the records, packs their
  * sequences into the searcher's batch and runs the search; taxor_gpu_search_batch_end follows as after any _begin.  raw may be pageable

@@ -244,6 +244,20 @@ class SegmentsBatch(C.Structure):
                 ("seg_best_hits", C.POINTER(C.c_uint32)), ("seconds_kernels", C.c_double), ("lookups", C.c_uint64)]
 
 
+class ExclusiveBatch(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_examined", C.c_uint64), ("n_cand", C.c_uint64), ("precision", C.c_uint32), ("reserved", C.c_uint32),
+                ("examined", C.POINTER(C.c_uint8)), ("n_candidates", C.POINTER(C.c_uint32)), ("n", C.POINTER(C.c_uint32)), ("matched", C.POINTER(C.c_uint32)),
+                ("shared", C.POINTER(C.c_uint32)), ("n_hashes", C.POINTER(C.c_uint32)), ("cand_off", C.POINTER(C.c_uint64)),
+                ("cand_tuple", C.POINTER(C.c_uint64)), ("cand_bin", C.POINTER(C.c_int64)), ("cand_count", C.POINTER(C.c_uint32)),
+                ("cand_hits", C.POINTER(C.c_uint32)), ("cand_excl", C.POINTER(C.c_uint32)), ("seconds_kernels", C.c_double), ("probes", C.c_uint64)]
+
+
+class ExclusiveResults(C.Structure):
+    _fields_ = [("n_user_bins", C.c_uint64), ("precision", C.c_uint32), ("reserved", C.c_uint32), ("cand_reads", C.POINTER(C.c_uint64)),
+                ("hits", C.POINTER(C.c_uint64)), ("exclusive_hits", C.POINTER(C.c_uint64)), ("exclusive_reads", C.POINTER(C.c_uint64)),
+                ("registers", C.POINTER(C.c_uint8)), ("seconds_kernels", C.c_double), ("probes", C.c_uint64)]
+
+
 class HitmapBatch(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_mapped", C.c_uint64), ("segments", C.c_uint32), ("reserved", C.c_uint32),
                 ("map_off", C.POINTER(C.c_uint64)), ("tuple", C.POINTER(C.c_uint64)), ("user_bin", C.POINTER(C.c_int64)),
@@ -320,6 +334,11 @@ SIGNATURES = {
     "taxor_gpu_segments_add_batch": (C.c_int, [_P, _P, _P, C.POINTER(SegmentsBatch)]),
     "taxor_gpu_segments_add_csr": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, C.POINTER(SegmentsBatch)]),
     "taxor_gpu_segments_destroy": (None, [_P]),
+    "taxor_gpu_exclusive_create": (C.c_int, [_P, C.POINTER(HixfView), C.c_uint32, C.POINTER(_P)]),
+    "taxor_gpu_exclusive_add_batch": (C.c_int, [_P, _P, _P, C.POINTER(ExclusiveBatch)]),
+    "taxor_gpu_exclusive_add_csr": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, C.POINTER(ExclusiveBatch)]),
+    "taxor_gpu_exclusive_results": (C.c_int, [_P, C.POINTER(ExclusiveResults)]),
+    "taxor_gpu_exclusive_destroy": (None, [_P]),
     "taxor_gpu_hitmap_create": (C.c_int, [_P, C.POINTER(HixfView), C.c_uint32, C.POINTER(_P)]),
     "taxor_gpu_hitmap_add_batch": (C.c_int, [_P, _P, _P, C.POINTER(HitmapBatch)]),
     "taxor_gpu_hitmap_destroy": (None, [_P]),

@@ -177,6 +177,14 @@ struct Batch {
     std::vector<SegRow> sg_rows;
     std::vector<Seg> sg_segs;
     bool sg_set = false;
+    // --exclusive-reads-file: the surviving tuples of the chunk's examined reads with two candidates or more (exclusive.hip), in read and
+    // tuple order; ex_set says that the batch's share has arrived; n_hashes above comes with them when no TSV is written
+    struct ExRow {
+        uint32_t read, count, hits, excl, n_cand, matched, shared;
+        int64_t bin;
+    };
+    std::vector<ExRow> ex_rows;
+    bool ex_set = false;
     // --device-parse: the chunk is a byte range of the file as read (whole records of kind raw_kind, '>' or '@'); the device finds
     // the records, ids and offsets are filled from its table and bases stays empty.  raw_kind 0: a parsed chunk, as above
     BaseBuf raw;

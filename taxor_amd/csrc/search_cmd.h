@@ -30,6 +30,10 @@ struct Config : ReaderOptions {              // taxor_search_configuration.hpp:8
     uint32_t breakpoint_min_gain = 0;  // --breakpoint-min-gain: hits the split must explain beyond the best single reference, >= 1 (0: not given, 1)
     std::string segments_file;         // --segments-file: one line per segment of a read whose best path among its references switches (segments.hip)
     uint32_t segments_switch_cost = 0; // --segments-switch-cost: hits a switch of reference costs, in [1,2^20] (0: not given, 16)
+    std::string exclusive_file;        // --exclusive-file: per user bin the hashes that no other reference on a read's list holds, over the whole run (exclusive.hip)
+    std::string exclusive_reads_file;  // --exclusive-reads-file: the same per line of the TSV, for reads with two candidates or more
+    uint32_t exclusive_precision = 0;  // hidden --exclusive-precision: registers per sketch = 2^this, in [4,16] (0: the library's 12)
+    bool exclusive_mode() const { return !exclusive_file.empty() || !exclusive_reads_file.empty(); }
     std::string gather;         // several devices: "rccl" | "host" (taxor_gpu_comm transports) | "none" (independent workers, each
                                 // fetching its own results); empty = rccl when the devices are distinct, host when one repeats
 };
@@ -87,6 +91,10 @@ void usage()
             "                           mosaic (a chimeric read, a prophage or IS element inside a chromosome read, a concatemer); ONE index file,\n"
             "                           ONE device; --output-file is then optional\n"
             "  --segments-switch-cost <n> with --segments-file: the hits a switch of reference must pay for, in [1,1048576] (default 16)\n"
+            "  --exclusive-file <f>     per reference that was a candidate of any read: its hits, and how many of them are hashes that NO other\n"
+            "                           reference the same read reported holds (which of several near-identical strains a read supports); ONE\n"
+            "                           index file, ONE device; --output-file is then optional\n"
+            "  --exclusive-reads-file <f> the same per line of --output-file, for reads with two candidates or more; alone or beside --exclusive-file\n"
             "  --expect <tsv>           compare the output per read with a TSV the reference wrote for the same input (exit 3 if it differs)\n"
             "search to profile in one run (the options of `taxor profile`; results go from the device's search buffers into the profile's\n"
             "device pipeline, no TSV is written or parsed in between):\n"
@@ -203,7 +211,27 @@ void advanced_help()
                     "                           k = 22, s = 12 about one base in 11 starts a syncmer, so 16 hits are roughly 180 bases of exact match, and\n"
                     "                           an inner segment, which pays twice, has to beat its flank by some 350 bases' worth of hits -- less than the\n"
                     "                           mobile elements people look for.\n"
-                    "  --paged-reread           the default said aloud: read the query file again in every pass; wins over --paged-replay.\n"
+                    "  --exclusive-file <f>     columns ACCESSION, TAXID, CANDIDATE_READS, HITS, EXCLUSIVE_HITS, EXCLUSIVE_READS, DISTINCT_EXCLUSIVE,\n"
+                    "                           EXCLUSIVE_FRACTION; one line per reference that was a candidate of an examined read, in the coverage file's\n"
+                    "                           order.  Candidates and the lookup are --breakpoint-file's (every tuple of the read with a match, not only the\n"
+                    "                           TSV's lines); a read is examined when it has a hash and at least ONE candidate.  A hash of the read is\n"
+                    "                           exclusive to a candidate when that candidate matches it and no other candidate of the same read does, shared\n"
+                    "                           when two or more do.  HITS sums the candidate's matches over its reads, EXCLUSIVE_HITS the exclusive ones,\n"
+                    "                           EXCLUSIVE_READS counts the reads that gave it at least one, DISTINCT_EXCLUSIVE is a sketch's estimate of the\n"
+                    "                           distinct exclusive hashes (the coverage file's sketch, at least 1 where EXCLUSIVE_HITS is above 0), and\n"
+                    "                           EXCLUSIVE_FRACTION = EXCLUSIVE_HITS / HITS with four decimals, 0.0000 without hits -- reported, not\n"
+                    "                           thresholded: 0.5 is no verdict.  Two limits.  Exclusivity is relative to the references the read REPORTED: a\n"
+                    "                           reference below the search threshold is not a tuple and takes no hash away.  And fingerprints have 8 bits: a\n"
+                    "                           foreign leaf bin answers yes at about 1/256, so a truly exclusive hash is lost at about (leaf bins of the other\n"
+                    "                           candidates)/256, and a candidate that shares nothing still shows about QHASH_COUNT * leaves/256 hits, most of\n"
+                    "                           them exclusive.  Refused: a comma list of index files, several devices, a --gather transport, and an index\n"
+                    "                           that has to be paged.  Beside --breakpoint-file or --segments-file every hash is looked up once per option.\n"
+                    "  --exclusive-reads-file <f> columns QUERY_NAME, ACCESSION, TAXID, QUERY_LEN, QHASH_COUNT, QHASH_MATCH, HITS, EXCLUSIVE_HITS, CANDIDATES, MATCHED,\n"
+                    "                           SHARED; for every examined read with two candidates or more one line per line of --output-file, reads in\n"
+                    "                           input order.  MATCHED counts the read's hashes that any candidate matches, SHARED those that two or more do:\n"
+                    "                           the candidates' EXCLUSIVE_HITS (lines below the 0.8 * max filter included) and SHARED add up to MATCHED.\n"
+                    "  --exclusive-precision <p> with --exclusive-file: registers per sketch = 2^p, in [4,16] (default 12).\n"
+                    "  --paged-reread          the default said aloud: read the query file again in every pass; wins over --paged-replay.\n"
                     "BAM input: the BGZF blocks are inflated on --threads threads, one thread walks the records (block_size, flag, l_seq, read_name)\n"
                     "                           and copies the 4-bit SEQ fields into a page-locked buffer; CIGAR, QUAL and tags are never read.  A\n"
                     "                           missing BGZF end-of-file block is a warning; CRAM and SAM text are refused.  With TAXOR_CLI_TRACE the\n"
@@ -492,6 +520,11 @@ struct SearchRun {
     std::vector<uint32_t> segments_species;   // user bin -> the species the TSV names for it
     double t_segments = 0, t_segments_kernels = 0;       // seconds inside taxor_gpu_segments_add_batch and in its kernels, summed over workers
     uint64_t segments_lookups = 0, segments_lines = 0, segments_reported = 0, segments_examined = 0, segments_reads = 0, segments_groups = 0;
+    taxor_gpu_exclusive *exclusive = nullptr; // --exclusive-file / --exclusive-reads-file: the object beside the resident index, for the whole run (exclusive.hip)
+    FILE *exclusive_reads_out = nullptr;      // --exclusive-reads-file; written by the sequencer as well
+    std::vector<uint32_t> exclusive_species;  // user bin -> the species the TSV names for it
+    double t_exclusive = 0, t_exclusive_kernels = 0;     // seconds inside taxor_gpu_exclusive_add_batch and in its kernels, summed over workers
+    uint64_t exclusive_probes = 0, exclusive_lines = 0, exclusive_examined = 0, exclusive_reads = 0;
     std::atomic<uint64_t> lca_next_read{0};   // the next batch's first read as the accumulator numbers it
     double t_lca = 0;               // seconds inside taxor_gpu_lca_add_batch, summed over workers
     double t_coverage = 0;          // seconds inside taxor_gpu_coverage_add_batch (taking and freeing the saved lists included), summed over workers
@@ -609,6 +642,19 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             if (n < 1 || n > (double)taxor::SEGMENTS_MAX_SWITCH_COST) die("Validation failed for option --segments-switch-cost: Value not in range [1,1048576].");
             cfg.segments_switch_cost = (uint32_t)n;
         }
+        else if (k == "--exclusive-file") {
+            cfg.exclusive_file = val();
+            if (cfg.exclusive_file.empty()) die("Validation failed for option --exclusive-file: the file name is empty.");
+        }
+        else if (k == "--exclusive-reads-file") {
+            cfg.exclusive_reads_file = val();
+            if (cfg.exclusive_reads_file.empty()) die("Validation failed for option --exclusive-reads-file: the file name is empty.");
+        }
+        else if (k == "--exclusive-precision") {
+            const double n = num(val(), true);
+            if (n < 4 || n > 16) die("Validation failed for option --exclusive-precision: Value not in range [4,16].");
+            cfg.exclusive_precision = (uint32_t)n;
+        }
         else if (k == "--report-file") {
             cfg.kraken_file = val();
             if (cfg.kraken_file.empty()) die("Validation failed for option --report-file: the file name is empty.");
@@ -720,7 +766,20 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             die("Validation failed for option --gather: --segments-file runs on ONE device, where nothing is gathered; leave --gather out.");
         if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
     }
-    run.write_tsv = !(run.profile_mode || cfg.lca_mode() || !cfg.hitmap_file.empty() || !cfg.breakpoint_file.empty() || !cfg.segments_file.empty()) || !cfg.report_file.empty();
+    if (cfg.exclusive_precision && cfg.exclusive_file.empty()) die("Option --exclusive-precision sizes the sketches of --exclusive-file: it needs that option.");
+    if (cfg.exclusive_mode()) {   // before any HIP call
+        const std::string opt = !cfg.exclusive_file.empty() ? "--exclusive-file" : "--exclusive-reads-file";
+        if (cfg.index_file.find(',') != std::string::npos)
+            die("Validation failed for option --index-file: " + opt + " takes ONE index file (a read's hashes are looked up in the leaf bins of the index its references belong to); "
+                "search the indexes one by one.");
+        if (cfg.gpus.size() > 1)
+            die("Validation failed for option " + run.gpus_option + ": " + opt + " examines on ONE device (a batch's hash lists and its results must lie on the same one); give --gpu <id>.");
+        if (!cfg.gather.empty() && cfg.gather != "none")
+            die("Validation failed for option --gather: " + opt + " runs on ONE device, where nothing is gathered; leave --gather out.");
+        if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
+    }
+    run.write_tsv = !(run.profile_mode || cfg.lca_mode() || !cfg.hitmap_file.empty() || !cfg.breakpoint_file.empty() || !cfg.segments_file.empty() || cfg.exclusive_mode()) ||
+                    !cfg.report_file.empty();
     if (cfg.threads == 0) {
         // --threads not given.  The reference's default is one worker thread (taxor_search_configuration.hpp:17) -- there the
         // thread that classifies; here host threads only parse the query file and render text for the GPU, and one of them
@@ -1191,6 +1250,7 @@ struct ReportWriter {
                 if (run.hitmap_out) write_hitmap_lines(bt);
                 if (run.breakpoint_out) write_breakpoint_lines(*hd->b);
                 if (run.segments_out) write_segments_lines(*hd->b);
+                if (run.exclusive_reads_out) write_exclusive_lines(*hd->b);
                 if (n == 0 || !run.write_tsv) { chunk_done(hd); continue; }
                 // cut where the estimated text passes piece_bytes
                 const uint64_t per_tuple = line_bytes_guess.load();
@@ -1317,6 +1377,26 @@ struct ReportWriter {
         run.segments_reported += bt.sg_rows.size();
         if (!segments_text.empty() && fwrite(segments_text.data(), 1, segments_text.size(), run.segments_out) != segments_text.size())
             die("cannot write to " + run.cfg.segments_file + ": " + strerror(errno));
+    }
+    // --exclusive-reads-file: the chunk's rows, one line each, by the sequencer (exclusive_format.h)
+    std::string exclusive_text;
+    void write_exclusive_lines(Batch &bt)
+    {
+        const size_t n = bt.ids.size();
+        if (!bt.ex_set || bt.n_hashes.size() != n) die("internal: a chunk reached the writer without its reads' exclusive hashes");
+        bt.ex_set = false;
+        const taxor_hixf_meta *meta = taxor_hixf_get_meta(h);
+        exclusive_text.clear();
+        for (const Batch::ExRow &x : bt.ex_rows) {
+            if (x.read >= n) die("internal: an exclusive row names a read outside its chunk");
+            const uint64_t b = (uint64_t)x.bin;     // the species `taxor_format_read` prints for the user bin
+            const taxor_species *sp = meta->n_species ? &meta->species[b < run.exclusive_species.size() ? run.exclusive_species[b] : 0] : nullptr;
+            taxor::exclusive_read_line(exclusive_text, bt.ids.ptr(x.read), bt.ids.len(x.read), taxor::exclusive_ref{sp ? sp->accession_id : nullptr, sp ? sp->taxid : nullptr},
+                                       bt.offsets[x.read + 1] - bt.offsets[x.read], bt.n_hashes[x.read], x.count, x.hits, x.excl, x.n_cand, x.matched, x.shared);
+        }
+        run.exclusive_lines += bt.ex_rows.size();
+        if (!exclusive_text.empty() && fwrite(exclusive_text.data(), 1, exclusive_text.size(), run.exclusive_reads_out) != exclusive_text.size())
+            die("cannot write to " + run.cfg.exclusive_reads_file + ": " + strerror(errno));
     }
     // a piece's text goes to the file when its ticket comes up
     void write_in_turn(const Piece &pc, const char *text, uint64_t need)
@@ -1499,6 +1579,42 @@ void finish_segments(SearchRun &run)
     run.segments = nullptr;
 }
 
+// ---- `--exclusive-file`: the run's table, fetched once and written here, one line per user bin that was a candidate of an examined read, in
+// user-bin order (the coverage file's; the species of a user bin as the TSV names it).  `--exclusive-reads-file` was written chunk by chunk
+// and is closed here
+void finish_exclusive(SearchRun &run, const taxor_hixf_meta *meta)
+{
+    if (run.exclusive_reads_out) {
+        if (ferror(run.exclusive_reads_out) || fclose(run.exclusive_reads_out) != 0) die("cannot write to " + run.cfg.exclusive_reads_file + ": " + strerror(errno));
+        run.exclusive_reads_out = nullptr;
+    }
+    uint64_t lines = 0;
+    if (!run.cfg.exclusive_file.empty()) {
+        taxor_exclusive_results er{};
+        if (taxor_gpu_exclusive_results(run.exclusive, &er) != TAXOR_OK) die(taxor_gpu_last_error());
+        const std::string &path = run.cfg.exclusive_file;
+        FILE *f = fopen(path.c_str(), "wb");
+        if (!f) die("cannot open exclusive file " + path);
+        std::string text = taxor::exclusive_header();
+        for (uint64_t b = 0; b < er.n_user_bins; ++b) {
+            if (er.cand_reads[b] == 0) continue;
+            const taxor_species *sp = meta->n_species ? &meta->species[b < run.exclusive_species.size() ? run.exclusive_species[b] : 0] : nullptr;
+            taxor::exclusive_bin_line(text, taxor::exclusive_ref{sp ? sp->accession_id : nullptr, sp ? sp->taxid : nullptr}, er.cand_reads[b], er.hits[b], er.exclusive_hits[b],
+                                      er.exclusive_reads[b], taxor::exclusive_distinct(taxor_hll_estimate(er.registers + (b << er.precision), er.precision), er.exclusive_hits[b]));
+            ++lines;
+        }
+        if (fwrite(text.data(), 1, text.size(), f) != text.size() || ferror(f) || fclose(f) != 0) die("cannot write to " + path + ": " + strerror(errno));
+    }
+    if (tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] exclusive: %llu user bins and %llu read lines from %llu examined reads of %llu; %.3f s inside the examining (summed over workers), %.6f s in its "
+                        "kernels, %llu lookups of a hash in a leaf bin = %.2f G gathers/s\n",
+                (unsigned long long)lines, (unsigned long long)run.exclusive_lines, (unsigned long long)run.exclusive_examined, (unsigned long long)run.exclusive_reads,
+                run.t_exclusive, run.t_exclusive_kernels, (unsigned long long)run.exclusive_probes,
+                run.t_exclusive_kernels > 0 ? 3.0 * run.exclusive_probes / run.t_exclusive_kernels / 1e9 : 0.0);
+    taxor_gpu_exclusive_destroy(run.exclusive);
+    run.exclusive = nullptr;
+}
+
 // ---- `--report-file`: the run's tallies, fetched once, rolled up the tree on the host (a few hundred thousand nodes at most, once per
 // run) and written as a Kraken-style report; `--lca-file` is closed here as well.  The layout: percentage of
 // the clade, clade count, direct count, rank code, taxid, name indented by two spaces per depth; unclassified first, then the tree from
@@ -1636,7 +1752,7 @@ struct GpuStage {
             for (unsigned w = 0; w < wpg; ++w)
                 if (taxor_gpu_searcher_create(gidx[g], &prm, &sr[g * wpg + w]) != TAXOR_OK) die(taxor_gpu_last_error());
     }
-    // --coverage-file / --hitmap-file / --lca-confidence / --breakpoint-file / --segments-file: the consumers beside the (one) index, and every searcher leaves its batches' hash lists for them
+    // --coverage-file / --hitmap-file / --lca-confidence / --breakpoint-file / --segments-file / --exclusive-file: the consumers beside the (one) index, and every searcher leaves its batches' hash lists for them
     void begin_saved_consumers(const taxor_hixf_view *view, const taxor_hixf_meta *meta)
     {
         const Config &cfg = run.cfg;
@@ -1662,6 +1778,12 @@ struct GpuStage {
             run.segments_species.assign(view->n_user_bins, 0u);       // as for the hit map
             for (uint64_t i = meta->n_species; i-- > 0;)
                 if (meta->species[i].user_bin < view->n_user_bins) run.segments_species[meta->species[i].user_bin] = (uint32_t)i;
+        }
+        if (cfg.exclusive_mode()) {
+            if (taxor_gpu_exclusive_create(gidx[0], view, cfg.exclusive_precision, &run.exclusive) != TAXOR_OK) die(taxor_gpu_last_error());
+            run.exclusive_species.assign(view->n_user_bins, 0u);      // as for the hit map
+            for (uint64_t i = meta->n_species; i-- > 0;)
+                if (meta->species[i].user_bin < view->n_user_bins) run.exclusive_species[meta->species[i].user_bin] = (uint32_t)i;
         }
         for (auto *s : sr)
             if (taxor_gpu_search_capture(s, 1) != TAXOR_OK) die(taxor_gpu_last_error());
@@ -1766,10 +1888,46 @@ struct GpuStage {
             }
         }
         const double c3d = now();
+        // --exclusive-file / --exclusive-reads-file: the per-user-bin sums stay on the device; the surviving tuples (the TSV's lines: the
+        // 0.8 * max filter in fp64 as written, the maximum over the candidates being the maximum over the read's tuples) of the examined
+        // reads with two candidates or more go to the chunks that hold them
+        taxor_exclusive_batch eb{};
+        if (rc == TAXOR_OK && run.exclusive) rc = taxor_gpu_exclusive_add_batch(run.exclusive, s, sv, &eb);
+        if (rc == TAXOR_OK && run.exclusive && run.exclusive_reads_out) {
+            uint64_t nr = 0;
+            for (auto &bt : group) nr += bt->ids.size();
+            if (eb.n_reads != nr) die("internal: a batch's exclusive hashes do not cover its chunks");
+            uint64_t r0 = 0;
+            for (auto &bt : group) {
+                const uint64_t n = bt->ids.size();
+                bt->ex_rows.clear();
+                for (uint64_t i = 0; i < n; ++i) {
+                    const uint64_t r = r0 + i;
+                    if (!eb.examined[r] || eb.n_candidates[r] < 2) continue;
+                    uint32_t mx = 0;
+                    for (uint64_t g = eb.cand_off[r]; g < eb.cand_off[r + 1]; ++g) mx = std::max(mx, eb.cand_count[g]);
+                    for (uint64_t g = eb.cand_off[r]; g < eb.cand_off[r + 1]; ++g)
+                        if (!((double)eb.cand_count[g] < (double)mx * 0.8))
+                            bt->ex_rows.push_back(Batch::ExRow{(uint32_t)i, eb.cand_count[g], eb.cand_hits[g], eb.cand_excl[g], eb.n_candidates[r], eb.matched[r], eb.shared[r],
+                                                               eb.cand_bin[g]});
+                }
+                bt->ex_set = true;
+                if (!run.write_tsv) bt->n_hashes.assign(eb.n_hashes + r0, eb.n_hashes + r0 + n);
+                r0 += n;
+            }
+        }
+        const double c3e = now();
         taxor_gpu_saved_free(sv);
         if (rc != TAXOR_OK) die(taxor_gpu_last_error());
-        const double c4 = now(), shared = (c1 - c0) + (c4 - c3d);       // taking and freeing the lists: the first consumer's
+        const double c4 = now(), shared = (c1 - c0) + (c4 - c3e);       // taking and freeing the lists: the first consumer's
         std::lock_guard<std::mutex> lk(run.stat_mu);
+        if (run.exclusive) {
+            run.t_exclusive += c3e - c3d + (run.coverage || run.hitmap || run.confidence || run.breakpoint || run.segments ? 0.0 : shared);
+            run.t_exclusive_kernels += eb.seconds_kernels;
+            run.exclusive_probes += eb.probes;
+            run.exclusive_examined += eb.n_examined;
+            run.exclusive_reads += eb.n_reads;
+        }
         if (run.confidence) {
             run.t_confidence += c3b - c3 + (run.coverage || run.hitmap ? 0.0 : shared);
             run.t_confidence_kernels += cc.seconds_kernels;
@@ -2037,7 +2195,7 @@ struct GpuStage {
             // without a TSV nothing on the host reads the tuples: they stay on the device for the profile feed
             if (classify(sr[wi], group, scanned, run.write_tsv ? &res : nullptr) != TAXOR_OK) die(taxor_gpu_last_error());
             if (run.profile_mode) feed_profile(sr[wi], group);
-            if (run.coverage || run.hitmap || run.confidence || run.breakpoint || run.segments) use_saved(sr[wi], group);
+            if (run.coverage || run.hitmap || run.confidence || run.breakpoint || run.segments || run.exclusive) use_saved(sr[wi], group);
             if (run.lca) add_lca(sr[wi], group);
             --n_running;
             const double t3 = now();
@@ -2126,7 +2284,7 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
     const double t_search0 = now();
     if (run.profile_mode) run.fused.begin(view, taxor_hixf_get_meta(h), run.prof.device);
     gpu.create_searchers(prm);
-    if (!cfg.coverage_file.empty() || !cfg.hitmap_file.empty() || cfg.confidence_mode() || !cfg.breakpoint_file.empty() || !cfg.segments_file.empty())
+    if (!cfg.coverage_file.empty() || !cfg.hitmap_file.empty() || cfg.confidence_mode() || !cfg.breakpoint_file.empty() || !cfg.segments_file.empty() || cfg.exclusive_mode())
         gpu.begin_saved_consumers(view, taxor_hixf_get_meta(h));
     // (with --lca-confidence the confident calls fill both files: the plain accumulator is not created)
     if (run.lineage && !run.confidence && taxor_gpu_lca_create(gpu.gidx[0], run.lineage, &run.lca) != TAXOR_OK) die(taxor_gpu_last_error());
@@ -2168,6 +2326,10 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
     if (run.segments) {
         finish_segments(run);
         trace("segments written");
+    }
+    if (run.exclusive) {
+        finish_exclusive(run, taxor_hixf_get_meta(h));
+        trace("exclusive hashes written");
     }
     gpu.release();
     if (run.profile_mode) {
@@ -2280,6 +2442,14 @@ void search_files(SearchRun &run, const std::string &hixf_file, const std::vecto
         if (budget)
             die("Validation failed for option --segments-file: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
                 std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; segmenting pass by pass is not built.");
+    }
+    if (cfg.exclusive_mode()) {
+        // as for --breakpoint-file
+        if (budget && cfg.index_budget_mib && whole.index_bytes <= budget) budget = 0;
+        if (budget)
+            die("Validation failed for option " + std::string(!cfg.exclusive_file.empty() ? "--exclusive-file" : "--exclusive-reads-file") +
+                ": the index would be searched in resident passes (" + std::string(why) + "; it holds " + std::to_string(whole.index_bytes >> 20) +
+                " MiB), and its leaf bins are then never resident together; counting exclusive hashes pass by pass is not built.");
     }
     if (cfg.confidence_mode()) {
         // a read's hashes are looked up in ALL the leaf bins of its references, and its final tuples exist only after the last pass's merge

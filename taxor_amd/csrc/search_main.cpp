@@ -15,6 +15,7 @@
 #include "ixf_layout.h"
 #include "breakpoint_format.h"
 #include "confidence_format.h"
+#include "exclusive_format.h"
 #include "hitmap_format.h"
 #include "key_store.h"
 #include "segments_format.h"
@@ -128,6 +129,11 @@ int main(int argc, char **argv)
         run.segments_out = fopen(cfg.segments_file.c_str(), "wb");
         if (!run.segments_out) die("cannot open segments file " + cfg.segments_file);
         fputs(taxor::segments_header(), run.segments_out);
+    }
+    if (!cfg.exclusive_reads_file.empty()) {     // --exclusive-file is written once, at the run's end
+        run.exclusive_reads_out = fopen(cfg.exclusive_reads_file.c_str(), "wb");
+        if (!run.exclusive_reads_out) die("cannot open exclusive reads file " + cfg.exclusive_reads_file);
+        fputs(taxor::exclusive_reads_header(), run.exclusive_reads_out);
     }
     if (index_files.size() == 1) {
         search_files(run, index_files[0], query_files, true);

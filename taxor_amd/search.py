@@ -1146,6 +1146,112 @@ class Segments:
         self.close()
 
 
+@dataclass
+class ExclusiveBatch:
+    """Exclusive.add_batch() / add_csr(): per read the words of include/taxor_gpu_tools.h (all 0 for a read that is not examined), every
+    read's hash count, and per candidate of an examined read -- cand_off[r] .. cand_off[r + 1], in CSR order -- its tuple, user bin,
+    count, hits and exclusive hits"""
+    precision: int
+    examined: np.ndarray      # bool[n_reads]
+    n_candidates: np.ndarray  # uint32[n_reads] M
+    n: np.ndarray             # the hash count of an examined read
+    matched: np.ndarray
+    shared: np.ndarray
+    n_hashes: np.ndarray      # of every read
+    cand_off: np.ndarray      # uint64[n_reads + 1]
+    cand_tuple: np.ndarray    # uint64[n_cand] index in the batch CSR
+    cand_bin: np.ndarray      # int64[n_cand]
+    cand_count: np.ndarray    # uint32[n_cand]
+    cand_hits: np.ndarray
+    cand_excl: np.ndarray
+    n_examined: int
+    seconds_kernels: float
+    probes: int
+
+
+@dataclass
+class ExclusiveTable:
+    """Exclusive.results(): per user bin the four sums of the whole run and the sketch of the hashes that were exclusive to it"""
+    precision: int
+    cand_reads: np.ndarray       # uint64[n_user_bins]
+    hits: np.ndarray
+    exclusive_hits: np.ndarray
+    exclusive_reads: np.ndarray
+    registers: np.ndarray        # uint8[n_user_bins, 2^precision]
+    seconds_kernels: float
+    probes: int
+
+    def distinct(self, b):
+        """DISTINCT_EXCLUSIVE of `taxor search --exclusive-file`: the rounded estimate, at least 1 where a hash was exclusive"""
+        d = int(np.floor(hll_estimate(self.registers[b], self.precision) + 0.5))      # llround: halves away from zero
+        return max(d, 1) if self.exclusive_hits[b] else d
+
+
+class Exclusive:
+    """Hashes only one reference explains (taxor_amd/csrc/exclusive.hip).  `ixfs` is the list the GpuIndex was made from (only bins and
+    fname_idx are read).  add_batch follows a batch that ran with Searcher.capture() on and takes its SavedBatch, which stays the
+    caller's; add_csr takes host arrays; results gives the run's sums.  The arrays returned are copies."""
+
+    READ_WORDS = (("n_candidates", np.uint32), ("n", np.uint32), ("matched", np.uint32), ("shared", np.uint32), ("n_hashes", np.uint32))
+    CAND_WORDS = (("cand_tuple", np.uint64), ("cand_bin", np.int64), ("cand_count", np.uint32), ("cand_hits", np.uint32), ("cand_excl", np.uint32))
+
+    def __init__(self, index: GpuIndex, ixfs, precision=0):
+        view, keep = GpuIndex._view([dict(f, data=None) for f in ixfs], index.n_user_bins, index.k, index.s, index.t, index.use_syncmer, 1,
+                                    index.window_size)
+        self._L = _lib.lib()
+        self._h = C.c_void_p()
+        self.index = index
+        check(self._L.taxor_gpu_exclusive_create(index._h, C.byref(view), int(precision), C.byref(self._h)))
+        del keep
+
+    @classmethod
+    def _batch(cls, b):
+        n, m = int(b.n_reads), int(b.n_cand)
+        arr = lambda ptr, k, dt: np.ctypeslib.as_array(ptr, shape=(k,)).copy() if k else np.zeros(0, dt)
+        return ExclusiveBatch(int(b.precision), arr(b.examined, n, np.uint8).astype(bool), *[arr(getattr(b, f), n, dt) for f, dt in cls.READ_WORDS],
+                              np.ctypeslib.as_array(b.cand_off, shape=(n + 1,)).copy(), *[arr(getattr(b, f), m, dt) for f, dt in cls.CAND_WORDS],
+                              int(b.n_examined), float(b.seconds_kernels), int(b.probes))
+
+    def add_batch(self, searcher: Searcher, saved: "SavedBatch") -> ExclusiveBatch:
+        b = _lib.ExclusiveBatch()
+        check(self._L.taxor_gpu_exclusive_add_batch(self._h, searcher._h, saved._h if saved is not None else None, C.byref(b)))
+        return self._batch(b)
+
+    def add_csr(self, read_off, user_bin, count, hash_off, hashes) -> ExclusiveBatch:
+        ro = np.ascontiguousarray(read_off, dtype=np.uint64)
+        ub = np.ascontiguousarray(user_bin, dtype=np.int64)
+        ct = np.ascontiguousarray(count, dtype=np.uint32)
+        ho = np.ascontiguousarray(hash_off, dtype=np.uint64)
+        hs = np.ascontiguousarray(hashes, dtype=np.uint64)
+        assert ro.size >= 1 and ho.size == ro.size and ub.size == ct.size and int(ro[-1]) <= ub.size and int(ho[-1]) <= hs.size
+        b = _lib.ExclusiveBatch()
+        check(self._L.taxor_gpu_exclusive_add_csr(self._h, ro.size - 1, _p(ro), _p(ub) if ub.size else None, _p(ct) if ct.size else None, _p(ho),
+                                                  _p(hs) if hs.size else None, C.byref(b)))
+        return self._batch(b)
+
+    def results(self) -> ExclusiveTable:
+        res = _lib.ExclusiveResults()
+        check(self._L.taxor_gpu_exclusive_results(self._h, C.byref(res)))
+        n, p = int(res.n_user_bins), int(res.precision)
+        arr = lambda ptr, m, dt: np.ctypeslib.as_array(ptr, shape=(m,)).copy() if m else np.zeros(0, dt)
+        return ExclusiveTable(p, arr(res.cand_reads, n, np.uint64), arr(res.hits, n, np.uint64), arr(res.exclusive_hits, n, np.uint64),
+                              arr(res.exclusive_reads, n, np.uint64), arr(res.registers, n << p, np.uint8).reshape(n, 1 << p), float(res.seconds_kernels),
+                              int(res.probes))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.taxor_gpu_exclusive_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Comm:
     """Several GPUs of one node driven by this one process (the C++ host's `taxor search --gpus N` shape): the index is
     replicated (one upload + ncclBroadcast), every device classifies its own batch, results are gathered on devices[0].
