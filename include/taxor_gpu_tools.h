@@ -1013,6 +1013,44 @@ int taxor_gpu_exclusive_add_csr(taxor_gpu_exclusive *ex, uint64_t n_reads, const
 int taxor_gpu_exclusive_results(taxor_gpu_exclusive *ex, taxor_exclusive_results *out);
 void taxor_gpu_exclusive_destroy(taxor_gpu_exclusive *ex);
 
+/* ---- index hashes per reference, read off the resident filter (`taxor census`, `taxor search --coverage-breadth`;
+ * taxor_amd/csrc/census.hip and census_format.h).  For every IXF x of the index and every bin j < bins,
+ * nonzero[bin_first[x] + j] = #{rows r < 3 * seg_len : data[r * stride + j] != 0}, an exact integer; padding columns bins <= j < stride
+ * are not reported and reach no reported bin.  A bin of an interleaved XOR filter gives each of its n keys one slot of its column and
+ * leaves the others at the 0 the builder cleared them to, and an assigned slot is uniform over 256 values: nonzero ~ Binomial(n, 255/256),
+ * nonzero <= n, and taxor_census_keys_est(nonzero) = llround(nonzero * 256 / 255) estimates n with standard deviation sqrt(n / 255).  A
+ * column with more nonzero bytes than taxor_census_capacity(seg_len) is no peeled filter (taxor_gpu_index_fill_random, a writer that
+ * does not clear free slots): its estimate says nothing.
+ * _create: the work list is cut from the index's descriptors in the search layout (an index loaded under another ixf_layout was
+ * transposed into it).  A paged index is refused by name (TAXOR_E_ARG): its IXFs are not all resident.
+ * _run: one streaming pass over the fingerprints -- every byte is read once; the counters are zeroed per call, so two calls give the same
+ * words.  tile_iters (rows per thread and tile) and max_blocks (the grid) are for tests and A/B runs, 0 = the defaults: the words do not
+ * depend on either.  Host pointers, valid until the next _run or _destroy; one _run at a time per object. */
+typedef struct taxor_gpu_census taxor_gpu_census;
+typedef struct {
+    uint64_t n_ixf, n_bins, n_user_bins;   /* n_bins = bin_first[n_ixf]: the technical bins of all IXFs */
+    const uint64_t *bin_first;             /* [n_ixf + 1] */
+    const uint64_t *nonzero;               /* [n_bins] in index bin order: all bins of IXF 0, then IXF 1, ... */
+    double seconds_kernel;                 /* HIP-event time of the launches */
+    uint64_t bytes_read;                   /* fingerprint bytes of the index, padding columns included: each read once */
+    uint64_t n_tiles;                      /* work items */
+    uint32_t launches, reserved;
+} taxor_census_results;
+int taxor_gpu_census_create(taxor_gpu_index *idx, taxor_gpu_census **out);
+int taxor_gpu_census_run(taxor_gpu_census *c, uint32_t tile_iters, uint32_t max_blocks, taxor_census_results *out);
+void taxor_gpu_census_destroy(taxor_gpu_census *c);
+/* Host only: census_format.h for a binding.  _peeled: nonzero <= capacity(seg_len).  The _line functions write the text of one line of
+ * `taxor census`'s two files (flagged != 0: the count is NA), _breadth_columns the four columns `--coverage-breadth` appends, into buf
+ * (NUL-terminated, truncated to cap) and return the full length */
+uint64_t taxor_census_keys_est(uint64_t nonzero);
+uint64_t taxor_census_capacity(uint64_t seg_len);
+int taxor_census_peeled(uint64_t nonzero, uint64_t seg_len);
+uint64_t taxor_census_ref_line(const char *accession, const char *name, const char *taxid, uint64_t ref_len, uint64_t leaf_bins, uint64_t index_hashes, int flagged,
+                               char *buf, uint64_t cap);
+uint64_t taxor_census_ixf_line(uint64_t ixf, uint64_t bins, uint64_t leaf_bins, uint64_t seg_len, uint64_t stride, uint64_t max_bin_keys, int flagged, char *buf,
+                               uint64_t cap);
+uint64_t taxor_census_breadth_columns(uint64_t distinct, uint64_t hash_matches, uint64_t index_hashes, int flagged, char *buf, uint64_t cap);
+
 /* ---- search straight from file bytes (taxor_amd/csrc/fastx_scan.hip): raw[0, n_bytes) holds whole records of one
  * kind, '>' (FASTA) or '@' (four-line FASTQ) -- what a reader cuts at record boundaries.  The device finds the records, packs their
  * sequences into the searcher's batch and runs the search; taxor_gpu_search_batch_end follows as after any _begin.  raw may be pageable

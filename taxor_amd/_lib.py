@@ -258,6 +258,12 @@ class ExclusiveResults(C.Structure):
                 ("registers", C.POINTER(C.c_uint8)), ("seconds_kernels", C.c_double), ("probes", C.c_uint64)]
 
 
+class CensusResults(C.Structure):
+    _fields_ = [("n_ixf", C.c_uint64), ("n_bins", C.c_uint64), ("n_user_bins", C.c_uint64), ("bin_first", C.POINTER(C.c_uint64)),
+                ("nonzero", C.POINTER(C.c_uint64)), ("seconds_kernel", C.c_double), ("bytes_read", C.c_uint64), ("n_tiles", C.c_uint64),
+                ("launches", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class HitmapBatch(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_mapped", C.c_uint64), ("segments", C.c_uint32), ("reserved", C.c_uint32),
                 ("map_off", C.POINTER(C.c_uint64)), ("tuple", C.POINTER(C.c_uint64)), ("user_bin", C.POINTER(C.c_int64)),
@@ -339,6 +345,15 @@ SIGNATURES = {
     "taxor_gpu_exclusive_add_csr": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, C.POINTER(ExclusiveBatch)]),
     "taxor_gpu_exclusive_results": (C.c_int, [_P, C.POINTER(ExclusiveResults)]),
     "taxor_gpu_exclusive_destroy": (None, [_P]),
+    "taxor_gpu_census_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "taxor_gpu_census_run": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(CensusResults)]),
+    "taxor_gpu_census_destroy": (None, [_P]),
+    "taxor_census_keys_est": (C.c_uint64, [C.c_uint64]),
+    "taxor_census_capacity": (C.c_uint64, [C.c_uint64]),
+    "taxor_census_peeled": (C.c_int, [C.c_uint64, C.c_uint64]),
+    "taxor_census_ref_line": (C.c_uint64, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_char_p, C.c_uint64]),
+    "taxor_census_ixf_line": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_char_p, C.c_uint64]),
+    "taxor_census_breadth_columns": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_char_p, C.c_uint64]),
     "taxor_gpu_hitmap_create": (C.c_int, [_P, C.POINTER(HixfView), C.c_uint32, C.POINTER(_P)]),
     "taxor_gpu_hitmap_add_batch": (C.c_int, [_P, _P, _P, C.POINTER(HitmapBatch)]),
     "taxor_gpu_hitmap_destroy": (None, [_P]),

@@ -17,6 +17,7 @@ struct Config : ReaderOptions {              // taxor_search_configuration.hpp:8
     bool paged_replay = false;       // hidden --paged-replay: the query file is read in the first resident pass only, the later ones replay the reads' saved hash lists
     bool paged_reread = false;       // hidden --paged-reread: every resident pass reads the query file again (the default, said aloud; wins over --paged-replay)
     std::string coverage_file;  // --coverage-file: per user bin the reads, the hash matches and the DISTINCT matched hashes of the whole run (coverage.hip)
+    bool coverage_breadth = false;     // --coverage-breadth: the coverage file gains INDEX_HASHES, BREADTH, EXPECTED_BREADTH, BREADTH_RATIO (census.hip)
     uint32_t coverage_precision = 0;   // hidden --coverage-precision: registers per sketch = 2^this, in [4,16] (0: the library's 12)
     std::string lca_file;       // --lca-file: one line per read, its lowest common ancestor (lca.hip)
     std::string kraken_file;    // --report-file: Kraken-style clade report of the whole run
@@ -73,6 +74,7 @@ void usage()
             "                           they are transposed on the device while the index is uploaded\n"
             "  --coverage-file <f>      per reference that any read reported: the reads, their QHASH_MATCH summed, the number of DISTINCT\n"
             "                           index hashes they matched (a sketch's estimate) and the ratio of the two; ONE index file, ONE device\n"
+            "  --coverage-breadth       with --coverage-file: per reference also its hashes in the index and the share of them the sample hit\n"
             "  --lca-file <f>           one line per read: C or U, the read, the taxid of the lowest common ancestor of the references it\n"
             "                           matched, its length, hash count, best match and the number of references  } ONE index file, ONE\n"
             "  --report-file <f>        Kraken-style report: per taxon the reads of its clade and its own            } device; --output-file\n"
@@ -136,6 +138,15 @@ void advanced_help()
                     "                           batch's hash lists in host memory until the batch is accumulated.  Refused: a comma list of index files,\n"
                     "                           several devices, a --gather transport, and an index that has to be paged (--device-index-budget below\n"
                     "                           the index's size, or an index larger than the device's free memory).\n"
+                    "  --coverage-breadth       with --coverage-file: every line gains INDEX_HASHES, BREADTH, EXPECTED_BREADTH, BREADTH_RATIO.  INDEX_HASHES: the\n"
+                    "                           keys of the reference's leaf bins, estimated once, when the index is resident, from the nonzero bytes of\n"
+                    "                           their columns (nonzero * 256 / 255 per bin, standard deviation sqrt(n / 255): a key owns one slot, a free\n"
+                    "                           slot stays 0; `taxor census` writes the same numbers for every reference).  BREADTH = min(1,\n"
+                    "                           DISTINCT_HASHES / INDEX_HASHES); EXPECTED_BREADTH = 1 - exp(-HASH_MATCHES / INDEX_HASHES), what uniform\n"
+                    "                           sampling at this depth would cover; BREADTH_RATIO their quotient: near 1 for a genome that is there, far\n"
+                    "                           below for hits piled on a few shared hashes.  Reported, not thresholded.  NA where a leaf bin is no peeled\n"
+                    "                           filter (more nonzero bytes than its IXF has room for keys) or INDEX_HASHES is 0; the ratio also where the\n"
+                    "                           expectation prints as 0.0000.  Limits: 8-bit fingerprints, free slots assumed zero.\n"
                     "  --lca-file <f>           columns STATUS, QUERY_NAME, TAXID, QUERY_LEN, QHASH_COUNT, BEST_QHASH_MATCH, REFERENCES; one line per read in the\n"
                     "                           order --output-file lists the reads in.  The references of a read are the lines --output-file prints for\n"
                     "                           it (the tuples that survive the 0.8 * max filter); each reference's path is the non-empty ids of its\n"
@@ -527,6 +538,7 @@ struct SearchRun {
     uint64_t exclusive_probes = 0, exclusive_lines = 0, exclusive_examined = 0, exclusive_reads = 0;
     std::atomic<uint64_t> lca_next_read{0};   // the next batch's first read as the accumulator numbers it
     double t_lca = 0;               // seconds inside taxor_gpu_lca_add_batch, summed over workers
+    std::vector<taxor::census_count> index_hashes;   // --coverage-breadth: per user bin, from the census taken when the index became resident
     double t_coverage = 0;          // seconds inside taxor_gpu_coverage_add_batch (taking and freeing the saved lists included), summed over workers
     double t_index = 0, t_reads = 0, t_compute = 0, t_pin = 0, t_search = 0, t_gather = 0, t_search_wall = 0;
     uint64_t n_batches = 0, n_gpu_batches = 0;
@@ -602,6 +614,7 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             cfg.coverage_file = val();
             if (cfg.coverage_file.empty()) die("Validation failed for option --coverage-file: the file name is empty.");
         }
+        else if (k == "--coverage-breadth") cfg.coverage_breadth = true;
         else if (k == "--coverage-precision") {
             const long n = (long)num(val(), true);
             if (n < 4 || n > 16) die("Validation failed for option --coverage-precision: Value not in range [4,16].");
@@ -702,6 +715,7 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
         prof.device = cfg.gpus[0];
     }
     if (cfg.coverage_precision && cfg.coverage_file.empty()) die("Option --coverage-precision sizes the sketches of --coverage-file: it needs that option.");
+    if (cfg.coverage_breadth && cfg.coverage_file.empty()) die("Option --coverage-breadth adds columns to --coverage-file: it needs that option.");
     if (!cfg.coverage_file.empty()) {   // before any HIP call
         if (cfg.index_file.find(',') != std::string::npos)
             die("Validation failed for option --index-file: --coverage-file takes ONE index file (a user bin's leaf bins are looked up in the index it belongs to); "
@@ -1506,7 +1520,9 @@ void write_coverage_file(SearchRun &run, const taxor_hixf_meta *meta)
     std::vector<uint32_t> bin_species(cr.n_user_bins, 0u);
     for (uint64_t i = meta->n_species; i-- > 0;)
         if (meta->species[i].user_bin < cr.n_user_bins) bin_species[meta->species[i].user_bin] = (uint32_t)i;
-    fputs("#ACCESSION\tREFERENCE_NAME\tTAXID\tREF_LEN\tREADS\tHASH_MATCHES\tDISTINCT_HASHES\tDUPLICITY\n", f);
+    const bool breadth = run.cfg.coverage_breadth;
+    fprintf(f, "#ACCESSION\tREFERENCE_NAME\tTAXID\tREF_LEN\tREADS\tHASH_MATCHES\tDISTINCT_HASHES\tDUPLICITY%s\n", breadth ? taxor::census_breadth_header() : "");
+    std::string more;
     uint64_t lines = 0;
     for (uint64_t b = 0; b < cr.n_user_bins; ++b) {
         if (cr.reads[b] == 0) continue;
@@ -1514,8 +1530,10 @@ void write_coverage_file(SearchRun &run, const taxor_hixf_meta *meta)
         if (cr.hash_matches[b] > 0 && distinct < 1) distinct = 1;
         static const taxor_species none{"-", "-", "-", "-", "-", 0, 0};
         const taxor_species &sp = meta->n_species ? meta->species[bin_species[b]] : none;
-        fprintf(f, "%s\t%s\t%s\t%llu\t%llu\t%llu\t%lld\t%.2f\n", sp.accession_id, sp.organism_name, sp.taxid, (unsigned long long)sp.seq_len,
-                (unsigned long long)cr.reads[b], (unsigned long long)cr.hash_matches[b], distinct, distinct ? (double)cr.hash_matches[b] / (double)distinct : 0.0);
+        more.clear();
+        if (breadth) taxor::census_breadth_columns(more, (uint64_t)distinct, cr.hash_matches[b], b < run.index_hashes.size() ? run.index_hashes[b] : taxor::census_count{0, true});
+        fprintf(f, "%s\t%s\t%s\t%llu\t%llu\t%llu\t%lld\t%.2f%s\n", sp.accession_id, sp.organism_name, sp.taxid, (unsigned long long)sp.seq_len,
+                (unsigned long long)cr.reads[b], (unsigned long long)cr.hash_matches[b], distinct, distinct ? (double)cr.hash_matches[b] / (double)distinct : 0.0, more.c_str());
         ++lines;
     }
     if (ferror(f) || fclose(f) != 0) die("cannot write to " + path + ": " + strerror(errno));
@@ -1757,6 +1775,13 @@ struct GpuStage {
     {
         const Config &cfg = run.cfg;
         if (!cfg.coverage_file.empty() && taxor_gpu_coverage_create(gidx[0], view, cfg.coverage_precision, &run.coverage) != TAXOR_OK) die(taxor_gpu_last_error());
+        if (cfg.coverage_breadth) {      // the census runs once, now that the index is resident
+            CensusRun cr = census_of(gidx[0], view);
+            run.index_hashes = std::move(cr.tables.index_hashes);
+            if (tune_env("TAXOR_CLI_TRACE"))
+                fprintf(stderr, "[trace] census: %.2f GB of fingerprints in %.3f s wall, %.3f ms in its kernel = %.1f GB/s, %llu tiles in %u launch(es)\n", cr.bytes_read / 1e9,
+                        cr.seconds_wall, cr.seconds_kernel * 1e3, cr.seconds_kernel > 0 ? cr.bytes_read / 1e9 / cr.seconds_kernel : 0.0, (unsigned long long)cr.n_tiles, cr.launches);
+        }
         if (!cfg.hitmap_file.empty()) {
             if (taxor_gpu_hitmap_create(gidx[0], view, cfg.hitmap_segments ? cfg.hitmap_segments : taxor::HITMAP_DEFAULT_SEGMENTS, &run.hitmap) != TAXOR_OK) die(taxor_gpu_last_error());
             // the species of a user bin as the TSV names it (the first that carries it, species[0] if none: taxor_search.cpp:172-178,289)

@@ -4,6 +4,7 @@
 //   cli_util.h      queue, die / now / trace, CPU marks, string and file helpers
 //   query_reader.h  query file -> numbered chunks of records (byte ranges, BAM, parallel gzip, sequential)
 //   tools_cmd.h     probe, verify, inflate, reads; the IXF variant helpers
+//   census_cmd.h    census: index hashes per reference and fill per IXF, counted from the resident fingerprints
 //   search_cmd.h    search: options, input checks, the resident pipeline and the paged route, search to profile, --expect
 //   pin_cmd.h, build_cmd.h, profile_cmd.h   one subcommand each
 // Here: the environment that must be set while the process has one thread, subcommand dispatch, and the outer loop of `search`.
@@ -14,6 +15,7 @@
 #include "ixf_arith.h"
 #include "ixf_layout.h"
 #include "breakpoint_format.h"
+#include "census_format.h"
 #include "confidence_format.h"
 #include "exclusive_format.h"
 #include "hitmap_format.h"
@@ -59,6 +61,7 @@ namespace {
 #include "cli_util.h"
 #include "query_reader.h"
 #include "tools_cmd.h"
+#include "census_cmd.h"
 #include "profile_cmd.h"
 #include "search_cmd.h"
 #include "pin_cmd.h"
@@ -86,6 +89,7 @@ int main(int argc, char **argv)
     if (cmd == "inflate") return inflate_command(argc, argv);
     if (cmd == "pin") return pin_command(argc, argv);           // published .hixf + reference TSV -> committed parity fixture (pin_cmd.h)
     if (cmd == "reads") return reads_command(argc, argv);
+    if (cmd == "census") return census_command(argc, argv);     // index hashes per reference, fill per IXF (census_cmd.h)
     if (cmd == "build") return build_command(argc, argv);       // genomes + taxonomy TSV -> .hixf (build_cmd.h)
     if (cmd == "profile") return profile_command(argc, argv);   // search TSV -> CAMI profile + binning (profile_cmd.h)
     // seqan3::argument_parser takes a long option's value either as the next argument or attached with '='

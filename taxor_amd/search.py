@@ -356,6 +356,26 @@ class GpuIndex:
         check(_lib.lib().taxor_gpu_index_download_ixf(self._h, ixf, _p(out), out.size))
         return out
 
+    def census(self, tile_iters=0, max_blocks=0, runs=1) -> "CensusTable":
+        """nonzero fingerprint bytes per bin of the resident index (taxor_gpu_census_*, csrc/census.hip): one streaming pass.
+        tile_iters / max_blocks: the work list's cut and the grid, 0 = the defaults (neither changes a word); runs > 1 repeats the
+        pass on the same object and keeps every run's words (CensusTable.all_runs) and the last one's time"""
+        L = _lib.lib()
+        h = C.c_void_p()
+        check(L.taxor_gpu_census_create(self._h, C.byref(h)))
+        try:
+            words = []
+            for _ in range(max(1, int(runs))):
+                r = _lib.CensusResults()
+                check(L.taxor_gpu_census_run(h, int(tile_iters), int(max_blocks), C.byref(r)))
+                words.append(np.ctypeslib.as_array(r.nonzero, (int(r.n_bins),)).copy() if r.n_bins else np.zeros(0, np.uint64))
+            first = np.ctypeslib.as_array(r.bin_first, (int(r.n_ixf) + 1,)).copy()
+            t = CensusTable(words[-1], first, float(r.seconds_kernel), int(r.bytes_read), int(r.n_tiles), int(r.launches))
+            t.all_runs = words
+            return t
+        finally:
+            L.taxor_gpu_census_destroy(h)
+
 
 class Searcher:
     """One GPU-side agent: syncmers -> dedup -> threshold -> HIXF query -> per-read tuples."""
@@ -660,6 +680,65 @@ def hll_estimate(registers, precision=12):
     r = np.ascontiguousarray(registers, dtype=np.uint8)
     assert r.size == 1 << int(precision)
     return float(_lib.lib().taxor_hll_estimate(_p(r), int(precision)))
+
+
+def census_keys_est(nonzero):
+    """taxor_census_keys_est (host only): the keys a bin's column of `nonzero` nonzero bytes stands for, llround(nonzero * 256 / 255)"""
+    return int(_lib.lib().taxor_census_keys_est(int(nonzero)))
+
+
+def census_capacity(seg_len):
+    """taxor_census_capacity (host only): the largest n with taxor_ixf_seg_len(n) <= seg_len"""
+    return int(_lib.lib().taxor_census_capacity(int(seg_len)))
+
+
+def census_peeled(nonzero, seg_len):
+    """taxor_census_peeled (host only): False when the column holds more nonzero bytes than its IXF has room for keys"""
+    return bool(_lib.lib().taxor_census_peeled(int(nonzero), int(seg_len)))
+
+
+def _census_text(fn, *args):
+    buf = C.create_string_buffer(4096)
+    n = int(fn(*args, buf, len(buf)))
+    assert n < len(buf)
+    return buf.value.decode()
+
+
+def census_ref_line(accession, name, taxid, ref_len, leaf_bins, index_hashes):
+    """one line of `taxor census --output-file`; index_hashes None = NA"""
+    enc = lambda s: None if s is None else s.encode()
+    return _census_text(_lib.lib().taxor_census_ref_line, enc(accession), enc(name), enc(taxid), int(ref_len), int(leaf_bins),
+                        int(index_hashes or 0), 1 if index_hashes is None else 0)
+
+
+def census_ixf_line(ixf, bins, leaf_bins, seg_len, stride, max_bin_keys):
+    """one line of `taxor census --ixf-file`; max_bin_keys None = NA"""
+    return _census_text(_lib.lib().taxor_census_ixf_line, int(ixf), int(bins), int(leaf_bins), int(seg_len), int(stride), int(max_bin_keys or 0),
+                        1 if max_bin_keys is None else 0)
+
+
+def census_breadth_columns(distinct, hash_matches, index_hashes):
+    """the four columns `taxor search --coverage-breadth` appends, each led by its tab; index_hashes None = NA"""
+    return _census_text(_lib.lib().taxor_census_breadth_columns, int(distinct), int(hash_matches), int(index_hashes or 0), 1 if index_hashes is None else 0)
+
+
+@dataclass
+class CensusTable:
+    """GpuIndex.census(): the nonzero fingerprint bytes of every bin, in index bin order"""
+    nonzero: np.ndarray        # uint64[n_bins]: all bins of IXF 0, then IXF 1, ...
+    bin_first: np.ndarray      # uint64[n_ixf + 1]
+    seconds_kernel: float      # HIP-event time of the pass
+    bytes_read: int            # fingerprint bytes of the index, each read once
+    n_tiles: int
+    launches: int
+    all_runs: list = None
+
+    def of_ixf(self, x):
+        return self.nonzero[int(self.bin_first[x]):int(self.bin_first[x + 1])]
+
+    def keys_est(self):
+        """llround(nonzero * 256 / 255) per bin (census_format.h), whether the bin is a peeled filter or not"""
+        return np.array([census_keys_est(v) for v in self.nonzero], dtype=np.uint64)
 
 
 @dataclass
