@@ -2,8 +2,7 @@
 // (`taxor search --lca-confidence`).
 //
 // The object lives beside a resident index for a whole run.  It holds the lineage's compacted paths as a CSR (lca.hip's table), the
-// leaf technical bins of every user bin as a CSR (coverage.hip's and hitmap.hip's table, restated: those files stay as they are), two
-// 64-bit tallies per node plus ROOT and UNCLASSIFIED, and two bounded staging buffers for hash lists.  A batch brings the searcher's
+// leaf-bin table and the piece stager of analysis_host.h, and two 64-bit tallies per node plus ROOT and UNCLASSIFIED.  A batch brings the searcher's
 // device-resident CSR -- EVERY tuple that passed the search threshold, not only the survivors of the 0.8 * max filter -- and the
 // batch's saved hash lists.
 //
@@ -23,69 +22,22 @@
 // pieces of classified reads only), so no scan kernel is needed.  Integer sums do not depend on the launch geometry nor on the cut into
 // pieces, staged groups and batches.  Every loop is bounded by a count the kernel is given (reads, a read's tuples, a piece's hashes,
 // a user bin's leaf bins, a path's length <= LINEAGE_MAX_DEPTH).  No block waits on another.
-#include "../../include/taxor_gpu_tools.h"
+#include "analysis_host.h"
 #include "confidence_format.h"
-#include "device_prims.h"
-#include "hip_host.h"
-#include "ixf_arith.h"
-#include "kernels.h"
 #include "lineage.h"
-#include "saved_batch.h"
-
-#include <hip/hip_runtime.h>
 
 #include <map>
 #include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
-
-// api.hip: the device-resident CSR of a searcher's last run (synchronises it), the reads' lengths in input order, the searcher's
-// index, an index's IXF descriptors
-extern "C" __attribute__((visibility("hidden"))) int taxor_searcher_device_results(taxor_gpu_searcher *s, const uint64_t **d_read_off,
-                                                                                   const int64_t **d_user_bin, const uint32_t **d_count,
-                                                                                   const uint32_t **d_n_hashes, uint64_t *n_reads,
-                                                                                   uint64_t *n_tuples, int *device);
-extern "C" __attribute__((visibility("hidden"))) int taxor_searcher_device_read_lengths(taxor_gpu_searcher *s, const uint32_t **d_rlen);
-extern "C" __attribute__((visibility("hidden"))) taxor_gpu_index *taxor_searcher_index(taxor_gpu_searcher *s);
-extern "C" __attribute__((visibility("hidden"))) int taxor_index_descs(const taxor_gpu_index *idx, const taxor::IxfDesc **d_ixf, const taxor::IxfDesc **h_ixf,
-                                                                       uint64_t *n_ixf, uint64_t *n_user_bins, uint32_t *n_passes, int *device);
 
 namespace {
 
 using namespace taxor;
 
-constexpr int CB = 256;                           // threads per block
-constexpr int CW = CB / 64;                       // reads / pieces per block pass (one wave each)
-constexpr int C_GRID_CAP = 4096;
-constexpr uint32_t CF_SPLIT = 2048;               // hashes of one read per piece
-constexpr uint64_t STAGE_HASHES = 1ull << 22;     // hashes per staging buffer (32 MiB); there are two
-constexpr uint64_t STAGE_PIECES = 1ull << 18;     // pieces per staging buffer (3 MiB); there are two
-constexpr uint64_t MAX_READS = 1ull << 31;
+constexpr int CB = READ_BLOCK, CW = READ_WAVES, C_GRID_CAP = READ_GRID_CAP;
 constexpr uint32_t CF_BAD = 0xFFu;                // the agree byte of a tuple whose user bin lies outside the index
 constexpr int CF_WORDS = 9;                       // words per read the kernels write (n_hashes is copied beside them)
 
 enum : uint32_t { CF_BAD_BIN = 1u };
-
-struct Piece {
-    uint32_t read;       // index in the batch
-    uint32_t first;      // offset of the piece's first hash in the staging buffer
-    uint32_t n;          // hashes, at most CF_SPLIT
-};
-
-// taxor_search.cpp:285, evaluated as written: the expression of taxor_classify_filter and lca_keeps.  Restated for lca.hip's reason:
-// device_prims.h is part of every kernel file of the search path, and this change leaves those files' objects exactly as they were
-__device__ __forceinline__ bool cf_keeps(uint32_t c, uint32_t mx) { return !((double)c < (double)mx * 0.8); }
-
-__device__ __forceinline__ uint32_t cf_wave_min(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const uint32_t t = __shfl_xor(v, d);
-        v = t < v ? t : v;
-    }
-    return v;
-}
 
 // the per-read words, n_reads apart
 struct Words {
@@ -132,7 +84,7 @@ __global__ __launch_bounds__(CB) void k_cf_agree(AgreeArgs a)
             uint32_t plo = 0, plen = 0;
             if (i < hi) {
                 const int64_t b = a.ub[i - a.t0];
-                if (b >= 0 && (uint64_t)b < a.n_bins && cf_keeps(a.count[i - a.t0], mx)) {
+                if (b >= 0 && (uint64_t)b < a.n_bins && keeps(a.count[i - a.t0], mx)) {
                     k = true;
                     plo = a.path_off[b];
                     plen = a.path_off[b + 1] - plo;
@@ -163,13 +115,13 @@ __global__ __launch_bounds__(CB) void k_cf_agree(AgreeArgs a)
                     const uint32_t lim = plen < ref_len ? plen : ref_len;
                     byte = 0;
                     while (byte < lim && a.path[plo + byte] == a.path[ref_lo + byte]) ++byte;
-                    k = cf_keeps(a.count[i - a.t0], mx);
+                    k = keeps(a.count[i - a.t0], mx);
                     if (k) ag = byte;
                 } else byte = 0;
                 a.agree[i - a.t0] = (uint8_t)byte;
             }
             n_refs += (uint32_t)__popcll(__ballot(k));
-            common = cf_wave_min(ag);      // ag is ref_len on a lane without a survivor, and common never exceeds it
+            common = wave_min(ag);      // ag is ref_len on a lane without a survivor, and common never exceeds it
             ref_len = common;              // (later tuples are still compared over the first D nodes at least: min(byte, D) is what counts)
         }
         if (lane == 0) {
@@ -202,31 +154,6 @@ struct ProbeArgs {
     unsigned long long *counters; // lookups | tuple steps made | tuple steps a full walk would make
 };
 
-// one tuple against the wave's 64 hashes: the lanes in `need` look their hash up in the leaf bins of user bin b
-__device__ __forceinline__ bool cf_lookup(const ProbeArgs &a, uint64_t b, uint64_t h, bool need, unsigned long long &lookups)
-{
-    const uint64_t l0 = a.leaf_off[b], l1 = a.leaf_off[b + 1];
-    bool matched = false;
-    uint32_t cur_ixf = 0xFFFFFFFFu;
-    IxfDesc d{};
-    ixf_probe p{};
-    for (uint64_t l = l0; l < l1; ++l) {
-        const uint2 lf = a.leaf[l];
-        if (lf.x != cur_ixf) {                                // a split user bin's parts stand side by side in one IXF: one probe
-            cur_ixf = lf.x;
-            d = a.ixf[lf.x];
-            p = ixf_probe_key_arith(h, d.seed, d.seg_len, d.arith);
-        }
-        if (need && !matched) {
-            const uint8_t f = d.data[(uint64_t)p.row[0] * d.stride + lf.y] ^ d.data[(uint64_t)p.row[1] * d.stride + lf.y] ^
-                              d.data[(uint64_t)p.row[2] * d.stride + lf.y];
-            matched = f == (uint8_t)(p.fp4 & 0xFFu);
-            ++lookups;
-        }
-    }
-    return matched;
-}
-
 __global__ __launch_bounds__(CB) void k_cf_probe(ProbeArgs a)
 {
     unsigned long long lookups = 0, steps = 0, steps_full = 0;
@@ -253,7 +180,8 @@ __global__ __launch_bounds__(CB) void k_cf_probe(ProbeArgs a)
                     const bool need = active && av < ag;
                     if (__ballot(need) == 0) continue;            // no lane this tuple could raise
                     ++steps;
-                    if (cf_lookup(a, (uint64_t)a.ub[t], h, need, lookups)) av = ag;
+                    const uint64_t b = (uint64_t)a.ub[t];
+                    if (leaf_lookup<true>(a.ixf, a.leaf, a.leaf_off[b], a.leaf_off[b + 1], h, need, lookups)) av = ag;
                     if (pass == 0 && __ballot(active && av < D) == 0) {
                         all_at_d = true;
                         break;
@@ -270,8 +198,7 @@ __global__ __launch_bounds__(CB) void k_cf_probe(ProbeArgs a)
             }
         }
     }
-    const unsigned long long wave_lookups = wave_incl_add(lookups);     // one atomic per wave and counter
-    if (lane == 63 && wave_lookups) atomicAdd(a.counters, wave_lookups);
+    wave_add_to(a.counters, lookups);
     if (lane == 0 && steps_full) {                                      // the step counters are the same in every lane
         atomicAdd(a.counters + 1, steps);
         atomicAdd(a.counters + 2, steps_full);
@@ -347,42 +274,15 @@ struct Slot {
 
 }   // namespace
 
-struct taxor_gpu_confidence {
-    taxor_gpu_index *idx = nullptr;
-    int device = 0;
+struct taxor_gpu_confidence : ReadAnalysis {
     double confidence = 0;
-    uint64_t n_bins = 0, n_nodes = 0, n_reads = 0;
-    const IxfDesc *d_ixf = nullptr;
-    hipStream_t st = nullptr;
-    std::mutex mu;                                    // batches may come from several threads
-    DeviceBuf<uint32_t> d_path_off, d_err;
+    uint64_t n_nodes = 0, n_reads = 0;
+    DeviceBuf<uint32_t> d_path_off;
     DeviceBuf<int32_t> d_path;
     DeviceBuf<unsigned long long> d_tally, d_counters;   // direct_reads | direct_bases, n_nodes + 2 each
-    DeviceBuf<uint64_t> d_leaf_off, d_hashes[2];
-    DeviceBuf<uint2> d_leaf;
-    DeviceBuf<Piece> d_pieces[2];
-    Piece *h_pieces[2] = {nullptr, nullptr};          // page-locked; ev_free[i] says that buffer i's copy has left it
-    hipEvent_t ev_free[2] = {nullptr, nullptr};
-    bool ev_used[2] = {false, false};
-    std::vector<hipEvent_t> ev_time;                  // pairs around the kernel launches of one call
-    std::vector<uint32_t> h_nh;
     std::map<const void *, std::unique_ptr<Slot>> slots;
-    // host arrays of add_csr on the device
-    DeviceBuf<uint64_t> c_off, c_qlen;
-    DeviceBuf<int64_t> c_ub;
-    DeviceBuf<uint32_t> c_cnt, c_nh;
     double seconds_kernels = 0;
     std::vector<uint64_t> r_tally;
-    ~taxor_gpu_confidence()
-    {
-        slots.clear();
-        for (int i = 0; i < 2; ++i) {
-            if (h_pieces[i]) (void)hipHostFree(h_pieces[i]);
-            if (ev_free[i]) (void)hipEventDestroy(ev_free[i]);
-        }
-        for (hipEvent_t e : ev_time) (void)hipEventDestroy(e);
-        if (st) (void)hipStreamDestroy(st);
-    }
 };
 
 namespace {
@@ -425,24 +325,14 @@ int add_device(taxor_gpu_confidence *c, const void *who, uint64_t first_read, ui
     calls->n_hashes = hw + 9 * n;
     calls->seconds_kernels = 0;
     calls->probes = calls->tuple_steps = calls->tuple_steps_full = 0;
-    if (c->ev_used[0] || c->ev_used[1]) {              // a call that failed half-way: its copies out of the page-locked pieces end first
-        CF_TRY(hipStreamSynchronize(c->st));
-        c->ev_used[0] = c->ev_used[1] = false;
-    }
+    if (int rc = c->stage.recover()) return rc;
     if (n == 0) return TAXOR_OK;
+    const uint64_t n_bins = c->leaf.n_bins;
     uint32_t *dw = sl.d_words.p;
     Words w{(int32_t *)dw, dw + n, (int32_t *)(dw + 2 * n), dw + 3 * n, dw + 4 * n, dw + 5 * n, dw + 6 * n, dw + 7 * n, dw + 8 * n};
 
-    size_t n_ev = 0;
-    auto stamp = [&]() -> int {                        // an event on the stream: launches are timed between pairs of them
-        if (c->ev_time.size() <= n_ev) {
-            hipEvent_t e = nullptr;
-            CF_TRY(hipEventCreate(&e));
-            c->ev_time.push_back(e);
-        }
-        CF_TRY(hipEventRecord(c->ev_time[n_ev++], c->st));
-        return TAXOR_OK;
-    };
+    c->timer.begin();
+    auto stamp = [&]() { return c->timer.stamp(c->st); };
 
     CF_TRY(sl.d_agree.reserve(nt + 1, nt + 1 + nt / 2));
     CF_TRY(hipMemsetAsync(c->d_counters.p, 0, 3 * 8, c->st));
@@ -452,7 +342,7 @@ int add_device(taxor_gpu_confidence *c, const void *who, uint64_t first_read, ui
     ag.count = d_cnt;
     ag.t0 = t0;
     ag.n_reads = n;
-    ag.n_bins = c->n_bins;
+    ag.n_bins = n_bins;
     ag.path_off = c->d_path_off.p;
     ag.path = c->d_path.p;
     ag.agree = sl.d_agree.p;
@@ -469,8 +359,8 @@ int add_device(taxor_gpu_confidence *c, const void *who, uint64_t first_read, ui
     CF_TRY(hipMemcpyAsync(&err, c->d_err.p, 4, hipMemcpyDeviceToHost, c->st));
     CF_TRY(hipStreamSynchronize(c->st));
     if (err & CF_BAD_BIN) {
-        CF_TRY(hipMemset(c->d_err.p, 0, 4));
-        return fail(TAXOR_E_INTERNAL, "confidence_add: user_bin: a tuple names a user bin outside the lineage's %llu", (unsigned long long)c->n_bins);
+        if (int rc = c->clear_err()) return rc;
+        return fail(TAXOR_E_INTERNAL, "confidence_add: user_bin: a tuple names a user bin outside the lineage's %llu", (unsigned long long)n_bins);
     }
     const int32_t *h_lca = (const int32_t *)(hw + 2 * n);
     const uint32_t *h_D = hw + 3 * n;
@@ -485,9 +375,9 @@ int add_device(taxor_gpu_confidence *c, const void *who, uint64_t first_read, ui
     CF_TRY(hipMemsetAsync(sl.d_hist.p, 0, (words + 1) * 4, c->st));
 
     ProbeArgs a{};
-    a.ixf = c->d_ixf;
-    a.leaf_off = c->d_leaf_off.p;
-    a.leaf = c->d_leaf.p;
+    a.ixf = c->leaf.d_ixf;
+    a.leaf_off = c->leaf.d_off.p;
+    a.leaf = c->leaf.d_leaf.p;
     a.off = d_off;
     a.ub = d_ub;
     a.t0 = t0;
@@ -496,43 +386,16 @@ int add_device(taxor_gpu_confidence *c, const void *who, uint64_t first_read, ui
     a.hist_off = sl.d_hist_off.p;
     a.hist = sl.d_hist.p;
     a.counters = c->d_counters.p;
-    // Groups of pieces, each staged and launched by itself (hitmap.hip's scheme): at most STAGE_PIECES pieces whose hashes lie within
-    // STAGE_HASHES consecutive entries of the dense host array, copied as one range
-    int buf = 0;
-    uint32_t n_p = 0;
-    uint64_t g0 = 0, g1 = 0;            // the group's hashes: [g0, g1) of hashes
-    auto flush = [&]() -> int {
-        if (n_p == 0) return TAXOR_OK;
-        CF_TRY(hipMemcpyAsync(c->d_hashes[buf].p, hashes + g0, (g1 - g0) * 8, hipMemcpyHostToDevice, c->st));
-        CF_TRY(hipMemcpyAsync(c->d_pieces[buf].p, c->h_pieces[buf], (uint64_t)n_p * sizeof(Piece), hipMemcpyHostToDevice, c->st));
-        CF_TRY(hipEventRecord(c->ev_free[buf], c->st));
-        c->ev_used[buf] = true;
-        a.pieces = c->d_pieces[buf].p;
-        a.hashes = c->d_hashes[buf].p;
+    c->stage.begin(hashes, [&](const Piece *pieces, const uint64_t *staged, uint32_t n_p) {
+        a.pieces = pieces;
+        a.hashes = staged;
         a.n_pieces = n_p;
-        if (int rc = stamp()) return rc;
         k_cf_probe<<<grid_for(n_p, CW, C_GRID_CAP), CB, 0, c->st>>>(a);
-        CF_TRY(hipGetLastError());
-        if (int rc = stamp()) return rc;
-        buf ^= 1;
-        n_p = 0;
-        if (c->ev_used[buf]) CF_TRY(hipEventSynchronize(c->ev_free[buf]));     // the page-locked pieces of two groups ago have been copied
-        return TAXOR_OK;
-    };
-    for (uint64_t r = 0; r < n; ++r) {
-        const uint64_t h0 = hash_off[r], nh = h_nh[r];
-        if (nh == 0 || h_lca[r] == TAXOR_LCA_UNCLASSIFIED) continue;
-        for (uint64_t done = 0; done < nh;) {
-            const uint32_t take = (uint32_t)std::min<uint64_t>(CF_SPLIT, nh - done);
-            if (n_p && (n_p == STAGE_PIECES || h0 + done + take - g0 > STAGE_HASHES))
-                if (int rc = flush()) return rc;
-            if (n_p == 0) g0 = h0 + done;
-            c->h_pieces[buf][n_p++] = Piece{(uint32_t)r, (uint32_t)(h0 + done - g0), take};
-            done += take;
-            g1 = h0 + done;
-        }
-    }
-    if (int rc = flush()) return rc;
+    });
+    for (uint64_t r = 0; r < n; ++r)
+        if (h_nh[r] != 0 && h_lca[r] != TAXOR_LCA_UNCLASSIFIED)
+            if (int rc = c->stage.add(r, hash_off[r], h_nh[r])) return rc;
+    if (int rc = c->stage.flush()) return rc;
 
     DecideArgs d{};
     d.n_reads = n;
@@ -557,12 +420,8 @@ int add_device(taxor_gpu_confidence *c, const void *who, uint64_t first_read, ui
     CF_TRY(hipMemcpyAsync(counters, c->d_counters.p, 3 * 8, hipMemcpyDeviceToHost, c->st));
     CF_TRY(hipStreamSynchronize(c->st));               // the searcher's buffers and the hash lists are the caller's again
     memcpy(hw + 9 * n, h_nh, n * sizeof(uint32_t));
-    c->ev_used[0] = c->ev_used[1] = false;
-    for (size_t i = 0; i + 1 < n_ev; i += 2) {
-        float ms = 0;
-        CF_TRY(hipEventElapsedTime(&ms, c->ev_time[i], c->ev_time[i + 1]));
-        calls->seconds_kernels += (double)ms * 1e-3;
-    }
+    c->stage.end();
+    if (int rc = c->timer.add_to(&calls->seconds_kernels)) return rc;
     calls->probes = counters[0];
     calls->tuple_steps = counters[1];
     calls->tuple_steps_full = counters[2];
@@ -580,18 +439,11 @@ extern "C" int taxor_gpu_confidence_create(taxor_gpu_index *idx, const taxor_hix
     *out = nullptr;
     if (!idx || !view || !lineage) return fail(TAXOR_E_ARG, "confidence_create: null argument");
     if (!confidence_valid(confidence)) return fail(TAXOR_E_ARG, "confidence_create: confidence: %g is not in [0, 1]", confidence);
-    const IxfDesc *d_ixf = nullptr, *h_ixf = nullptr;
-    uint64_t n_ixf = 0, n_bins = 0;
-    uint32_t n_passes = 0;
-    int device = 0;
-    if (taxor_index_descs(idx, &d_ixf, &h_ixf, &n_ixf, &n_bins, &n_passes, &device)) return fail(TAXOR_E_ARG, "confidence_create: null index");
-    if (n_passes)
-        return fail(TAXOR_E_ARG, "confidence_create: a paged index (%u resident pass%s) is refused: its leaf bins are not all resident at once and a read's final tuples exist only after the last pass's merge; weighing calls pass by pass is not built",
-                    n_passes, n_passes == 1 ? "" : "es");
-    if (view->n_ixf != n_ixf || view->n_user_bins != n_bins || (n_ixf && !view->ixf))
-        return fail(TAXOR_E_ARG, "confidence_create: the view (%llu IXFs, %llu user bins) is not the index's (%llu IXFs, %llu user bins)", (unsigned long long)view->n_ixf,
-                    (unsigned long long)view->n_user_bins, (unsigned long long)n_ixf, (unsigned long long)n_bins);
-    if (n_bins >= (1ull << 32) || n_ixf >= (1ull << 32)) return fail(TAXOR_E_ARG, "confidence_create: user bins and IXFs are numbered in 32 bits");
+    auto c = std::make_unique<taxor_gpu_confidence>();
+    if (int rc = c->leaf.build("confidence_create", "its leaf bins are not all resident at once and a read's final tuples exist only after the last pass's merge; weighing calls pass by pass is not built", idx, view))
+        return rc;
+    if (int rc = c->stage.configure("confidence_create")) return rc;
+    const uint64_t n_bins = c->leaf.n_bins;
     // the lineage's paths (lca.hip's table and checks)
     taxor_lineage_view v{};
     if (int rc = taxor_lineage_get_view(lineage, &v)) return rc;
@@ -605,58 +457,17 @@ extern "C" int taxor_gpu_confidence_create(taxor_gpu_index *idx, const taxor_hix
         if (off32[b + 1] < off32[b] || off32[b + 1] - off32[b] > LINEAGE_MAX_DEPTH) return fail(TAXOR_E_ARG, "confidence_create: path_off: the path of user bin %llu is malformed", (unsigned long long)b);
     for (uint64_t i = 0; i < n_path; ++i)
         if (v.path[i] < 0 || (uint64_t)v.path[i] >= v.n_nodes) return fail(TAXOR_E_ARG, "confidence_create: path: entry %llu is not a node", (unsigned long long)i);
-    // the inverse of fname_idx: every leaf technical bin of a user bin, root included, as one CSR in index order (the set and the order
-    // of coverage.hip's and hitmap.hip's tables, restated a third time: those files, and their objects, stay as they are)
-    std::vector<uint64_t> leaf_off(n_bins + 1, 0);
-    for (uint64_t x = 0; x < n_ixf; ++x) {
-        const taxor_ixf_view &f = view->ixf[x];
-        if (f.bins != h_ixf[x].bins) return fail(TAXOR_E_ARG, "confidence_create: IXF %llu has %llu bins in the view, %u in the index", (unsigned long long)x, (unsigned long long)f.bins, h_ixf[x].bins);
-        if (!f.fname_idx) return fail(TAXOR_E_ARG, "confidence_create: IXF %llu of the view has no fname_idx", (unsigned long long)x);
-        for (uint64_t j = 0; j < f.bins; ++j) {
-            const int64_t b = f.fname_idx[j];
-            if (b < 0) continue;
-            if ((uint64_t)b >= n_bins) return fail(TAXOR_E_ARG, "confidence_create: bin %llu of IXF %llu names user bin %lld of %llu", (unsigned long long)j, (unsigned long long)x, (long long)b, (unsigned long long)n_bins);
-            ++leaf_off[(uint64_t)b + 1];
-        }
-    }
-    for (uint64_t b = 0; b < n_bins; ++b) leaf_off[b + 1] += leaf_off[b];
-    std::vector<uint2> leaf(leaf_off[n_bins]);
-    {
-        std::vector<uint64_t> at(leaf_off.begin(), leaf_off.end() - 1);
-        for (uint64_t x = 0; x < n_ixf; ++x)
-            for (uint64_t j = 0; j < view->ixf[x].bins; ++j) {
-                const int64_t b = view->ixf[x].fname_idx[j];
-                if (b >= 0) leaf[at[(uint64_t)b]++] = make_uint2((uint32_t)x, (uint32_t)j);
-            }
-    }
-    CF_TRY(hipSetDevice(device));
-    auto c = std::make_unique<taxor_gpu_confidence>();
-    c->idx = idx;
-    c->device = device;
+    CF_TRY(hipSetDevice(c->leaf.device));
     c->confidence = confidence;
-    c->n_bins = n_bins;
     c->n_nodes = v.n_nodes;
-    c->d_ixf = d_ixf;
-    CF_TRY(hipStreamCreate(&c->st));
+    if (int rc = c->open("confidence")) return rc;
     CF_TRY(c->d_path_off.alloc(n_bins + 1));
     CF_TRY(c->d_path.alloc(n_path + 1));
     CF_TRY(c->d_tally.alloc(2 * (v.n_nodes + 2)));
     CF_TRY(c->d_counters.alloc(3));
-    CF_TRY(c->d_err.alloc(1));
-    CF_TRY(c->d_leaf_off.alloc(n_bins + 1));
-    CF_TRY(c->d_leaf.alloc(leaf.size() + 1));
-    for (int i = 0; i < 2; ++i) {
-        CF_TRY(c->d_hashes[i].alloc(STAGE_HASHES));
-        CF_TRY(c->d_pieces[i].alloc(STAGE_PIECES));
-        CF_TRY(hipHostMalloc((void **)&c->h_pieces[i], STAGE_PIECES * sizeof(Piece), hipHostMallocDefault));
-        CF_TRY(hipEventCreateWithFlags(&c->ev_free[i], hipEventDisableTiming));
-    }
     CF_TRY(hipMemcpy(c->d_path_off.p, off32.data(), (n_bins + 1) * 4, hipMemcpyHostToDevice));
     if (n_path) CF_TRY(hipMemcpy(c->d_path.p, v.path, n_path * 4, hipMemcpyHostToDevice));
-    CF_TRY(hipMemcpy(c->d_leaf_off.p, leaf_off.data(), (n_bins + 1) * 8, hipMemcpyHostToDevice));
-    if (!leaf.empty()) CF_TRY(hipMemcpy(c->d_leaf.p, leaf.data(), leaf.size() * 8, hipMemcpyHostToDevice));
     CF_TRY(hipMemset(c->d_tally.p, 0, 2 * (v.n_nodes + 2) * 8));
-    CF_TRY(hipMemset(c->d_err.p, 0, 4));
     *out = c.release();
     return TAXOR_OK;
 }
@@ -664,7 +475,7 @@ extern "C" int taxor_gpu_confidence_create(taxor_gpu_index *idx, const taxor_hix
 extern "C" void taxor_gpu_confidence_destroy(taxor_gpu_confidence *c)
 {
     if (!c) return;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->leaf.device);
     delete c;
 }
 
@@ -672,28 +483,12 @@ extern "C" int taxor_gpu_confidence_add_batch(taxor_gpu_confidence *c, taxor_gpu
                                               taxor_confidence_calls *calls)
 {
     if (!c || !s || !calls) return fail(TAXOR_E_ARG, "confidence_add_batch: null argument");
-    if (!saved) return fail(TAXOR_E_ARG, "confidence_add_batch: saved: no saved batch (the batch ran with capture off, or its lists were not taken)");
-    if (taxor_searcher_index(s) != c->idx) return fail(TAXOR_E_ARG, "confidence_add_batch: index: the searcher works on another index than the confidence object");
-    const std::string unsound = saved_validate(*saved);
-    if (!unsound.empty()) return fail(TAXOR_E_ARG, "confidence_add_batch: " + unsound);
-    const uint64_t *d_off = nullptr;
-    const int64_t *d_ub = nullptr;
-    const uint32_t *d_cnt = nullptr, *d_nh = nullptr, *d_rlen = nullptr;
-    uint64_t n = 0, nt = 0;
-    int dev = 0;
-    if (int rc = taxor_searcher_device_results(s, &d_off, &d_ub, &d_cnt, &d_nh, &n, &nt, &dev)) return rc;
+    std::unique_lock<std::mutex> lk;
+    SearcherBatch b;
+    if (int rc = begin_batch("confidence_add_batch", "confidence", "the confidence object", *c, s, saved, lk, &b)) return rc;
+    const uint32_t *d_rlen = nullptr;
     if (int rc = taxor_searcher_device_read_lengths(s, &d_rlen)) return rc;
-    if (saved->n_reads != n)
-        return fail(TAXOR_E_ARG, "confidence_add_batch: n_reads: the saved batch holds %llu reads, the searcher's last batch %llu", (unsigned long long)saved->n_reads, (unsigned long long)n);
-    if (n >= MAX_READS) return fail(TAXOR_E_ARG, "confidence_add_batch: n_reads: a batch of 2^31 reads or more");
-    std::lock_guard<std::mutex> lk(c->mu);
-    CF_TRY(hipSetDevice(c->device));
-    c->h_nh.resize(n);
-    if (n) CF_TRY(hipMemcpy(c->h_nh.data(), d_nh, n * 4, hipMemcpyDeviceToHost));
-    for (uint64_t r = 0; r < n; ++r)
-        if (c->h_nh[r] != saved->n_hashes[r])
-            return fail(TAXOR_E_ARG, "confidence_add_batch: n_hashes: read %llu has %u hashes in the saved batch, %u in the searcher's last batch", (unsigned long long)r, saved->n_hashes[r], c->h_nh[r]);
-    return add_device(c, s, first_read, n, nt, d_off, d_ub, d_cnt, d_nh, d_rlen, nullptr, 0, saved->hash_off.data(), saved->hashes, c->h_nh.data(), calls);
+    return add_device(c, s, first_read, b.n, b.nt, b.d_off, b.d_ub, b.d_cnt, b.d_nh, d_rlen, nullptr, 0, saved->hash_off.data(), saved->hashes, c->h_nh.data(), calls);
 }
 
 extern "C" int taxor_gpu_confidence_add_csr(taxor_gpu_confidence *c, uint64_t n_reads, const uint64_t *read_off, const int64_t *user_bin, const uint32_t *count,
@@ -701,44 +496,19 @@ extern "C" int taxor_gpu_confidence_add_csr(taxor_gpu_confidence *c, uint64_t n_
 {
     if (!c || !read_off || !hash_off || !calls) return fail(TAXOR_E_ARG, "confidence_add_csr: null argument");
     if (n_reads && !query_len) return fail(TAXOR_E_ARG, "confidence_add_csr: query_len: null array");
-    if (n_reads >= MAX_READS) return fail(TAXOR_E_ARG, "confidence_add_csr: n_reads: 2^31 reads or more");
-    for (uint64_t r = 0; r < n_reads; ++r) {
-        if (read_off[r + 1] < read_off[r]) return fail(TAXOR_E_ARG, "confidence_add_csr: read_off decreases at read %llu", (unsigned long long)r);
-        if (hash_off[r + 1] < hash_off[r] || hash_off[r + 1] - hash_off[r] >= (1ull << 32))
-            return fail(TAXOR_E_ARG, "confidence_add_csr: hash_off: the list of read %llu is malformed", (unsigned long long)r);
-    }
-    const uint64_t t0 = read_off[0], nt = read_off[n_reads] - t0;
-    if (nt && (!user_bin || !count)) return fail(TAXOR_E_ARG, "confidence_add_csr: user_bin / count: null array");
-    if (hash_off[n_reads] > hash_off[0] && !hashes) return fail(TAXOR_E_ARG, "confidence_add_csr: hashes: null array");
-    for (uint64_t i = t0; i < t0 + nt; ++i)
-        if (user_bin[i] < 0 || (uint64_t)user_bin[i] >= c->n_bins)
-            return fail(TAXOR_E_ARG, "confidence_add_csr: user_bin: tuple %llu names user bin %lld, the lineage has %llu", (unsigned long long)i, (long long)user_bin[i], (unsigned long long)c->n_bins);
+    CsrUpload &u = c->csr;
     std::lock_guard<std::mutex> lk(c->mu);
-    CF_TRY(hipSetDevice(c->device));
-    c->h_nh.resize(n_reads);
-    for (uint64_t r = 0; r < n_reads; ++r) c->h_nh[r] = (uint32_t)(hash_off[r + 1] - hash_off[r]);
-    CF_TRY(c->c_off.reserve(n_reads + 1, n_reads + 1 + n_reads / 2));
-    CF_TRY(c->c_qlen.reserve(n_reads + 1, n_reads + 1 + n_reads / 2));
-    CF_TRY(c->c_nh.reserve(n_reads + 1, n_reads + 1 + n_reads / 2));
-    CF_TRY(c->c_ub.reserve(nt + 1, nt + 1 + nt / 2));
-    CF_TRY(c->c_cnt.reserve(nt + 1, nt + 1 + nt / 2));
-    CF_TRY(hipMemcpy(c->c_off.p, read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice));
-    if (nt) {
-        CF_TRY(hipMemcpy(c->c_ub.p, user_bin + t0, nt * 8, hipMemcpyHostToDevice));
-        CF_TRY(hipMemcpy(c->c_cnt.p, count + t0, nt * 4, hipMemcpyHostToDevice));
-    }
-    if (n_reads) {
-        CF_TRY(hipMemcpy(c->c_qlen.p, query_len, n_reads * 8, hipMemcpyHostToDevice));
-        CF_TRY(hipMemcpy(c->c_nh.p, c->h_nh.data(), n_reads * 4, hipMemcpyHostToDevice));
-    }
-    return add_device(c, nullptr, 0, n_reads, nt, c->c_off.p, c->c_ub.p, c->c_cnt.p, c->c_nh.p, nullptr, c->c_qlen.p, t0, hash_off, hashes, c->h_nh.data(), calls);
+    if (int rc = u.check("confidence_add_csr", "lineage", c->leaf.n_bins, n_reads, read_off, user_bin, count, hash_off, hashes)) return rc;
+    CF_TRY(hipSetDevice(c->leaf.device));
+    if (int rc = u.upload("confidence", n_reads, read_off, user_bin, count, hash_off, query_len, &c->h_nh)) return rc;
+    return add_device(c, nullptr, 0, n_reads, u.nt, u.off.p, u.ub.p, u.cnt.p, u.nh.p, nullptr, u.qlen.p, u.t0, hash_off, hashes, c->h_nh.data(), calls);
 }
 
 extern "C" int taxor_gpu_confidence_results(taxor_gpu_confidence *c, taxor_lca_results *out)
 {
     if (!c || !out) return fail(TAXOR_E_ARG, "confidence_results: null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    CF_TRY(hipSetDevice(c->device));
+    CF_TRY(hipSetDevice(c->leaf.device));
     const uint64_t n = c->n_nodes + 2;
     c->r_tally.resize(2 * n);
     CF_TRY(hipMemcpy(c->r_tally.data(), c->d_tally.p, 2 * n * 8, hipMemcpyDeviceToHost));

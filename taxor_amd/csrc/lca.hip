@@ -16,39 +16,18 @@
 // (docs/EXPERIMENTS.md, "Per-read LCA and report"), which is why the simple shape shipped and not groups of 16 lanes per read.
 // Every loop is bounded by a count the kernel is given (the reads, a read's tuples, a path's length <= LINEAGE_MAX_DEPTH).  No block
 // waits on another.  Integer sums are order-free: the result does not depend on the launch geometry or on the order of the batches.
-#include "../../include/taxor_gpu_tools.h"
-#include "device_prims.h"
-#include "hip_host.h"
+#include "analysis_host.h"
 #include "lineage.h"
-
-#include <hip/hip_runtime.h>
 
 #include <map>
 #include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
-
-// api.hip: the device-resident CSR of a searcher's last run (synchronises it), the reads' lengths in input order, the searcher's
-// index, an index's shape
-extern "C" __attribute__((visibility("hidden"))) int taxor_searcher_device_results(taxor_gpu_searcher *s, const uint64_t **d_read_off,
-                                                                                   const int64_t **d_user_bin, const uint32_t **d_count,
-                                                                                   const uint32_t **d_n_hashes, uint64_t *n_reads,
-                                                                                   uint64_t *n_tuples, int *device);
-extern "C" __attribute__((visibility("hidden"))) int taxor_searcher_device_read_lengths(taxor_gpu_searcher *s, const uint32_t **d_rlen);
-extern "C" __attribute__((visibility("hidden"))) taxor_gpu_index *taxor_searcher_index(taxor_gpu_searcher *s);
-namespace taxor { struct IxfDesc; }
-extern "C" __attribute__((visibility("hidden"))) int taxor_index_descs(const taxor_gpu_index *idx, const taxor::IxfDesc **d_ixf, const taxor::IxfDesc **h_ixf,
-                                                                       uint64_t *n_ixf, uint64_t *n_user_bins, uint32_t *n_passes, int *device);
 
 namespace {
 
 using namespace taxor;
 
-constexpr int LB = 256;                  // threads per block
-constexpr int LW = LB / 64;              // reads per block pass (one wave each)
+constexpr int LB = READ_BLOCK, LW = READ_WAVES;
 constexpr int L_GRID_CAP = 2048;
-constexpr uint64_t MAX_READS = 1ull << 31;
 
 enum : uint32_t { LCA_BAD_BIN = 1u };
 
@@ -68,22 +47,6 @@ struct LcaArgs {
     unsigned long long *direct_reads, *direct_bases;     // [n_nodes + 2]
     uint32_t *err;
 };
-
-// taxor_search.cpp:285, evaluated as written: the expression of taxor_classify_filter, k_ff_count and k_cov_accumulate.  It stands here
-// a fourth time, and not once in device_prims.h, because that header is part of every kernel file of the search path: this change
-// leaves those files' sources, and with them their objects, exactly as they were
-__device__ __forceinline__ bool lca_keeps(uint32_t c, uint32_t mx) { return !((double)c < (double)mx * 0.8); }
-
-// minimum over the wave, the same in every lane (xor butterfly, like device_prims.h's wave_max)
-__device__ __forceinline__ uint32_t lca_wave_min(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const uint32_t t = __shfl_xor(v, d);
-        v = t < v ? t : v;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(LB) void k_lca(LcaArgs a)
 {
@@ -108,7 +71,7 @@ __global__ __launch_bounds__(LB) void k_lca(LcaArgs a)
                 if (i < hi) {
                     const int64_t b = a.ub[i - a.t0];
                     if (b < 0 || (uint64_t)b >= a.n_bins) bad = true;
-                    else if (lca_keeps(a.count[i - a.t0], mx)) {
+                    else if (keeps(a.count[i - a.t0], mx)) {
                         k = true;
                         plo = a.path_off[b];
                         plen = a.path_off[b + 1] - plo;
@@ -130,7 +93,7 @@ __global__ __launch_bounds__(LB) void k_lca(LcaArgs a)
                     agree = 0;
                     while (agree < lim && a.path[plo + agree] == a.path[ref_lo + agree]) ++agree;
                 }
-                common = lca_wave_min(agree);
+                common = wave_min(agree);
             }
             if (have_ref) node = common ? a.path[ref_lo + common - 1] : TAXOR_LCA_ROOT;
             else mx = 0;                                           // (only tuples with a user bin outside the table: reported through err)
@@ -168,23 +131,18 @@ struct taxor_gpu_lca {
     int device = 0;
     uint64_t n_bins = 0, n_nodes = 0, n_reads = 0;
     hipStream_t st = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    LaunchTimer timer;
     std::mutex mu;                                    // batches may come from several threads
     DeviceBuf<uint32_t> d_path_off, d_err;
     DeviceBuf<int32_t> d_path;
     DeviceBuf<unsigned long long> d_tally;            // direct_reads | direct_bases, n_nodes + 2 each
     std::map<const void *, std::unique_ptr<Slot>> slots;
-    // host arrays of add_csr on the device
-    DeviceBuf<uint64_t> c_off, c_qlen;
-    DeviceBuf<int64_t> c_ub;
-    DeviceBuf<uint32_t> c_cnt;
+    CsrUpload csr;                                    // the host arrays of add_csr on the device
     double seconds_kernel = 0;
     std::vector<uint64_t> r_tally;
     ~taxor_gpu_lca()
     {
         slots.clear();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
         if (st) (void)hipStreamDestroy(st);
     }
 };
@@ -232,18 +190,17 @@ int add_device(taxor_gpu_lca *c, const void *who, uint64_t first_read, uint64_t 
     a.direct_reads = c->d_tally.p;
     a.direct_bases = c->d_tally.p + c->n_nodes + 2;
     a.err = c->d_err.p;
-    LCA_TRY(hipEventRecord(c->ev[0], c->st));
+    c->timer.begin();
+    if (int rc = c->timer.stamp(c->st)) return rc;
     k_lca<<<grid_for(n, LW, L_GRID_CAP), LB, 0, c->st>>>(a);
     LCA_TRY(hipGetLastError());
-    LCA_TRY(hipEventRecord(c->ev[1], c->st));
+    if (int rc = c->timer.stamp(c->st)) return rc;
     uint32_t err = 0;
     LCA_TRY(hipMemcpyAsync(sl.h, sl.d.p, 3 * n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
     if (d_nh) LCA_TRY(hipMemcpyAsync(sl.h + 3 * n, d_nh, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
     LCA_TRY(hipMemcpyAsync(&err, c->d_err.p, 4, hipMemcpyDeviceToHost, c->st));
     LCA_TRY(hipStreamSynchronize(c->st));             // the caller's buffers (a searcher's results) may be reused from here on
-    float ms = 0;
-    LCA_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    c->seconds_kernel += (double)ms * 1e-3;
+    if (int rc = c->timer.add_to(&c->seconds_kernel)) return rc;
     c->n_reads += n;
     if (err & LCA_BAD_BIN) return fail(TAXOR_E_INTERNAL, "lca_add: user_bin: a tuple names a user bin outside the lineage's %llu", (unsigned long long)c->n_bins);
     return TAXOR_OK;
@@ -282,9 +239,8 @@ extern "C" int taxor_gpu_lca_create(taxor_gpu_index *idx, const taxor_lineage *l
     c->device = device;
     c->n_bins = n_bins;
     c->n_nodes = v.n_nodes;
+    c->timer.name = "lca";
     LCA_TRY(hipStreamCreate(&c->st));
-    LCA_TRY(hipEventCreate(&c->ev[0]));
-    LCA_TRY(hipEventCreate(&c->ev[1]));
     LCA_TRY(c->d_path_off.alloc(n_bins + 1));
     LCA_TRY(c->d_path.alloc(n_path + 1));
     LCA_TRY(c->d_tally.alloc(2 * (v.n_nodes + 2)));
@@ -326,27 +282,12 @@ extern "C" int taxor_gpu_lca_add_csr(taxor_gpu_lca *c, uint64_t n_reads, const u
 {
     if (!c || !read_off || !calls) return fail(TAXOR_E_ARG, "lca_add_csr: null argument");
     if (n_reads && !query_len) return fail(TAXOR_E_ARG, "lca_add_csr: query_len: null array");
-    if (n_reads >= MAX_READS) return fail(TAXOR_E_ARG, "lca_add_csr: n_reads: 2^31 reads or more");
-    for (uint64_t r = 0; r < n_reads; ++r)
-        if (read_off[r + 1] < read_off[r]) return fail(TAXOR_E_ARG, "lca_add_csr: read_off decreases at read %llu", (unsigned long long)r);
-    const uint64_t t0 = read_off[0], nt = read_off[n_reads] - t0;
-    if (nt && (!user_bin || !count)) return fail(TAXOR_E_ARG, "lca_add_csr: user_bin / count: null array");
-    for (uint64_t i = t0; i < t0 + nt; ++i)
-        if (user_bin[i] < 0 || (uint64_t)user_bin[i] >= c->n_bins)
-            return fail(TAXOR_E_ARG, "lca_add_csr: user_bin: tuple %llu names user bin %lld, the lineage has %llu", (unsigned long long)i, (long long)user_bin[i], (unsigned long long)c->n_bins);
+    CsrUpload &u = c->csr;
     std::lock_guard<std::mutex> lk(c->mu);
+    if (int rc = u.check("lca_add_csr", "lineage", c->n_bins, n_reads, read_off, user_bin, count, nullptr, nullptr)) return rc;
     LCA_TRY(hipSetDevice(c->device));
-    LCA_TRY(c->c_off.reserve(n_reads + 1, n_reads + 1 + n_reads / 2));
-    LCA_TRY(c->c_qlen.reserve(n_reads + 1, n_reads + 1 + n_reads / 2));
-    LCA_TRY(c->c_ub.reserve(nt + 1, nt + 1 + nt / 2));
-    LCA_TRY(c->c_cnt.reserve(nt + 1, nt + 1 + nt / 2));
-    LCA_TRY(hipMemcpy(c->c_off.p, read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice));
-    if (nt) {
-        LCA_TRY(hipMemcpy(c->c_ub.p, user_bin + t0, nt * 8, hipMemcpyHostToDevice));
-        LCA_TRY(hipMemcpy(c->c_cnt.p, count + t0, nt * 4, hipMemcpyHostToDevice));
-    }
-    if (n_reads) LCA_TRY(hipMemcpy(c->c_qlen.p, query_len, n_reads * 8, hipMemcpyHostToDevice));
-    return add_device(c, nullptr, 0, n_reads, c->c_off.p, c->c_ub.p, c->c_cnt.p, nullptr, nullptr, c->c_qlen.p, t0, calls);
+    if (int rc = u.upload("lca", n_reads, read_off, user_bin, count, nullptr, query_len, nullptr)) return rc;
+    return add_device(c, nullptr, 0, n_reads, u.off.p, u.ub.p, u.cnt.p, nullptr, nullptr, u.qlen.p, u.t0, calls);
 }
 
 extern "C" int taxor_gpu_lca_results(taxor_gpu_lca *c, taxor_lca_results *out)

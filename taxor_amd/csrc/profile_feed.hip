@@ -19,6 +19,7 @@
 #include "device_prims.h"
 #include "hip_host.h"
 #include "profile_host.h"
+#include "read_probe.h"
 
 #include <hip/hip_runtime.h>
 
@@ -66,8 +67,8 @@ __device__ __forceinline__ uint32_t ff_read_max(const uint32_t *__restrict__ cou
     return wave_max(mx);
 }
 
-// taxor_search.cpp:285, evaluated as written
-__device__ __forceinline__ bool ff_keeps(uint32_t c, uint32_t mx, bool keep_all) { return keep_all || !((double)c < (double)mx * 0.8); }
+// read_probe.h's output filter, with the keep-all switch in front
+__device__ __forceinline__ bool ff_keeps(uint32_t c, uint32_t mx, bool keep_all) { return keep_all || keeps(c, mx); }
 
 __global__ __launch_bounds__(FB) void k_ff_count(const uint64_t *__restrict__ off, const int64_t *__restrict__ ub, const uint32_t *__restrict__ count,
                                                  uint64_t t0, uint64_t n_reads, uint64_t n_bins, int keep_all, uint64_t *__restrict__ kept,

@@ -1,14 +1,14 @@
 // segments.hip -- paint a read with its references: the optimal segmentation of its ordered hash list among ALL the references it
 // reported, with a cost per switch (`taxor search --segments-file`).
 //
-// The object lives beside a resident index for a whole run and keeps nothing between batches but its buffers.  It holds the leaf
-// technical bins of every user bin as a CSR (breakpoint.hip's table, restated: that file stays as it is) and two bounded staging buffers
-// for hash lists.  A batch brings the searcher's device-resident CSR and the batch's saved hash lists.  The CANDIDATES of a read are its
-// tuples with count > 0, in CSR order; a read is EXAMINED when it has a hash and at least two candidates (section 10.6's words).
+// The object lives beside a resident index for a whole run and keeps nothing between batches but its buffers: the leaf-bin table and
+// the piece stager of analysis_host.h.  A batch brings the searcher's device-resident CSR and the batch's saved hash lists.  The
+// CANDIDATES of a read are its tuples with count > 0, in CSR order; a read is EXAMINED when it has a hash and at least two candidates
+// (section 10.6's words).
 //
-//   k_sg_count / k_sg_fill / k_sg_probe   section 10.6's three, restated: M per read to the host; the candidates compacted in CSR order;
-//                one wave per PIECE (at most SG_SPLIT consecutive hashes from a multiple of SG_SPLIT), one 64-bit match word
-//                mask[c][round] per candidate and 64 hashes, written exactly once by one lane.
+//   read_probe.h's k_cand_count, k_cand_fill and k_probe_mask, as in breakpoint.hip: M per read to the host; the candidates compacted
+//                in CSR order; one 64-bit match word mask[c][round] per candidate and 64 hashes.  `lookups` counts the leaf-bin lookups
+//                of the last, which stop at a candidate's first matching leaf bin.
 //   k_sg_single  one wave per examined read, a lane per candidate (c % 64 == lane): total_c by popcounts, then a wave maximum of
 //                (total_c, lowest c): `single` and `best`.
 //   k_sg_viterbi one wave per examined read, positions in order.  A lane owns the candidates c with c % 64 == lane.  With
@@ -31,184 +31,34 @@
 //
 // Every word is an integer maximum, an arg-max with a fixed tie rule or a sum of integers: nothing depends on the launch geometry nor on
 // the cut into pieces, groups and batches.  Every loop is bounded by a count the kernel is given.  No block waits on another.
-#include "../../include/taxor_gpu_tools.h"
-#include "device_prims.h"
-#include "hip_host.h"
-#include "ixf_arith.h"
-#include "kernels.h"
-#include "saved_batch.h"
+#include "analysis_host.h"
 #include "segments_format.h"
-#include "tuning.h"
-
-#include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cstring>
 #include <map>
 #include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
-
-// api.hip: the device-resident CSR of a searcher's last run (synchronises it); the searcher's index; an index's IXF descriptors
-extern "C" __attribute__((visibility("hidden"))) int taxor_searcher_device_results(taxor_gpu_searcher *s, const uint64_t **d_read_off,
-                                                                                   const int64_t **d_user_bin, const uint32_t **d_count,
-                                                                                   const uint32_t **d_n_hashes, uint64_t *n_reads,
-                                                                                   uint64_t *n_tuples, int *device);
-extern "C" __attribute__((visibility("hidden"))) taxor_gpu_index *taxor_searcher_index(taxor_gpu_searcher *s);
-extern "C" __attribute__((visibility("hidden"))) int taxor_index_descs(const taxor_gpu_index *idx, const taxor::IxfDesc **d_ixf, const taxor::IxfDesc **h_ixf,
-                                                                       uint64_t *n_ixf, uint64_t *n_user_bins, uint32_t *n_passes, int *device);
 
 namespace {
 
 using namespace taxor;
 
-constexpr int SB = 256;                           // threads per block
-constexpr int SWV = SB / 64;                      // reads / pieces per block pass (one wave each)
-constexpr int S_GRID_CAP = 4096;
-constexpr uint32_t SG_SPLIT = 2048;               // hashes of one read per piece: a multiple of 64, so a piece's rounds are the read's
-constexpr uint64_t STAGE_HASHES = 1ull << 22;     // hashes per staging buffer (32 MiB); there are two
-constexpr uint64_t STAGE_PIECES = 1ull << 18;     // pieces per staging buffer (4 MiB); there are two
-constexpr uint64_t MAX_READS = 1ull << 31;
+constexpr int SB = READ_BLOCK, SWV = READ_WAVES, S_GRID_CAP = READ_GRID_CAP;
 constexpr uint64_t MAX_HASHES = 1ull << 31;       // of one read: value = hits * 2^32 - ... stays within 63 bits below it
 constexpr uint64_t SG_BUDGET_WORDS = 1ull << 23;  // mask words of one group of reads (64 MiB), and as many switch words
 constexpr long long SG_NONE = LLONG_MIN;          // a lane without a candidate, in a wave maximum of V >= 0
 
-enum : uint32_t { SG_BAD_BIN = 1u, SG_MISCOUNT = 2u, SG_BAD_TRACE = 4u };
+enum : uint32_t { SG_BAD_TRACE = 4u };            // beside CAND_BAD_BIN and CAND_MISCOUNT
 
-struct Piece {
-    uint32_t read;       // index in the batch
-    uint32_t first;      // offset of the piece's first hash in the staging buffer
-    uint32_t n;          // hashes, at most SG_SPLIT
-    uint32_t rank0;      // rank of the piece's first hash in the read's list: a multiple of SG_SPLIT
-};
-
-// a tuple is a candidate when its count is above 0; one that names a user bin outside the index is reported through err
-__device__ __forceinline__ bool sg_candidate(const int64_t *__restrict__ ub, const uint32_t *__restrict__ count, uint64_t i, uint64_t hi, uint64_t t0,
-                                             uint64_t n_bins, bool *bad)
-{
-    if (i >= hi || count[i - t0] == 0) return false;
-    const int64_t b = ub[i - t0];
-    if (b < 0 || (uint64_t)b >= n_bins) {
-        *bad = true;
-        return false;
-    }
-    return true;
-}
-
-// the CSR's tuples are indexed from t0 (off[0] == t0)
-__global__ __launch_bounds__(SB) void k_sg_count(const uint64_t *__restrict__ off, const int64_t *__restrict__ ub, const uint32_t *__restrict__ count, uint64_t t0,
-                                                 const uint32_t *__restrict__ nh, uint64_t n_reads, uint64_t n_bins, uint32_t *__restrict__ n_cand,
-                                                 uint32_t *__restrict__ err)
-{
-    bool bad = false;
-    for (uint64_t r = (uint64_t)blockIdx.x * SWV + (threadIdx.x >> 6); r < n_reads; r += (uint64_t)gridDim.x * SWV) {
-        uint32_t m = 0;
-        if (nh[r] != 0) {
-            const uint64_t lo = off[r], hi = off[r + 1];
-            for (uint64_t base = lo; base < hi; base += 64) m += (uint32_t)__popcll(__ballot(sg_candidate(ub, count, base + lane_id(), hi, t0, n_bins, &bad)));
-        }
-        if (lane_id() == 0) n_cand[r] = m;
-    }
-    if (bad) atomicOr(err, SG_BAD_BIN);
-}
-
-// cand_off is the host's sum of the EXAMINED reads' counts: read r's candidates go to [cand_off[r], cand_off[r + 1]) in CSR order
-__global__ __launch_bounds__(SB) void k_sg_fill(const uint64_t *__restrict__ off, const int64_t *__restrict__ ub, const uint32_t *__restrict__ count, uint64_t t0,
-                                                uint64_t n_reads, uint64_t n_bins, const uint64_t *__restrict__ cand_off, uint64_t *__restrict__ o_tuple,
-                                                int64_t *__restrict__ o_ub, uint32_t *__restrict__ err)
-{
-    bool bad = false, miscount = false;
-    for (uint64_t r = (uint64_t)blockIdx.x * SWV + (threadIdx.x >> 6); r < n_reads; r += (uint64_t)gridDim.x * SWV) {
-        const uint64_t dst0 = cand_off[r], room = cand_off[r + 1] - dst0;
-        if (room == 0) continue;
-        const uint64_t lo = off[r], hi = off[r + 1];
-        uint64_t written = 0;
-        for (uint64_t base = lo; base < hi; base += 64) {
-            const uint64_t i = base + lane_id();
-            const bool k = sg_candidate(ub, count, i, hi, t0, n_bins, &bad);
-            const uint64_t m = __ballot(k);
-            const uint64_t at = written + (uint64_t)__popcll(m & ((1ull << lane_id()) - 1ull));
-            if (k && at < room) {                         // never past the read's room: a walk that disagrees with the count is reported below
-                o_tuple[dst0 + at] = i;
-                o_ub[dst0 + at] = ub[i - t0];
-            }
-            written += (uint64_t)__popcll(m);
-        }
-        miscount = miscount || written != room;
-    }
-    if (bad) atomicOr(err, SG_BAD_BIN);
-    if (miscount) atomicOr(err, SG_MISCOUNT);
-}
-
-// what the kernels after the fill share: the examined reads' candidates and where a read's scratch lies within its group's
-struct Layout {
-    const uint64_t *cand_off;     // [n_reads + 1]; an empty range: the read is not examined
+// what the kernels after the fill share: the match words (read_probe.h) and where a read's other scratch lies within its group's.
+// The read's switch words lie at the place of its mask words, mask_off[r], in sw
+struct Layout : MaskLayout {
     const uint64_t *cand_tuple;   // [n_cand] index in the batch CSR
-    const int64_t *cand_ub;       // [n_cand] checked against n_bins by the count's walk
-    const uint64_t *mask_off;     // [n_reads] first mask word of the read, mask[mask_off[r] + c * rounds + k]; its switch words lie at the same place in sw
     const uint64_t *a_off;        // [n_reads] first word of the read's a: a[a_off[r] + i], 64 * rounds of them
-    const uint32_t *nh;           // [n_reads] rounds = ceil(nh / 64)
-    uint64_t *mask;
     uint64_t *sw;
     uint32_t *a;
     long long *state;             // V[cand_off[r] + c], for reads with more than 64 candidates
 };
-
-struct ProbeArgs {
-    const IxfDesc *ixf;
-    const uint64_t *leaf_off;     // [n_bins + 1] user bin b's leaf technical bins are leaf[leaf_off[b] .. leaf_off[b + 1])
-    const uint2 *leaf;            // (IXF, bin)
-    Layout l;
-    const Piece *pieces;
-    const uint64_t *hashes;       // the staged part of the saved lists
-    uint32_t n_pieces;
-    unsigned long long *lookups;
-};
-
-__global__ __launch_bounds__(SB) void k_sg_probe(ProbeArgs a)
-{
-    unsigned long long lookups = 0;
-    const uint32_t lane = lane_id();
-    for (uint64_t pi = (uint64_t)blockIdx.x * SWV + (threadIdx.x >> 6); pi < a.n_pieces; pi += (uint64_t)gridDim.x * SWV) {
-        const Piece pc = a.pieces[pi];
-        const uint64_t c0 = a.l.cand_off[pc.read], c1 = a.l.cand_off[pc.read + 1];
-        const uint64_t rounds = ((uint64_t)a.l.nh[pc.read] + 63) >> 6;
-        uint64_t *mask = a.l.mask + a.l.mask_off[pc.read];
-        for (uint32_t h0 = 0; h0 < pc.n; h0 += 64) {
-            const uint32_t j = h0 + lane;
-            const bool active = j < pc.n;
-            const uint64_t h = active ? a.hashes[(uint64_t)pc.first + j] : 0;
-            const uint64_t round = ((uint64_t)pc.rank0 + h0) >> 6;    // < rounds: rank0 + h0 < the read's hashes
-            for (uint64_t c = c0; c < c1; ++c) {
-                const uint64_t b = (uint64_t)a.l.cand_ub[c];          // the same in every lane
-                const uint64_t l0 = a.leaf_off[b], l1 = a.leaf_off[b + 1];
-                bool matched = false;
-                uint32_t cur_ixf = 0xFFFFFFFFu;
-                IxfDesc d{};
-                ixf_probe p{};
-                for (uint64_t l = l0; l < l1; ++l) {
-                    const uint2 lf = a.leaf[l];
-                    if (lf.x != cur_ixf) {                            // a split user bin's parts stand side by side in one IXF: one probe
-                        cur_ixf = lf.x;
-                        d = a.ixf[lf.x];
-                        p = ixf_probe_key_arith(h, d.seed, d.seg_len, d.arith);
-                    }
-                    if (active && !matched) {
-                        const uint8_t f = d.data[(uint64_t)p.row[0] * d.stride + lf.y] ^ d.data[(uint64_t)p.row[1] * d.stride + lf.y] ^
-                                          d.data[(uint64_t)p.row[2] * d.stride + lf.y];
-                        matched = f == (uint8_t)(p.fp4 & 0xFFu);
-                        ++lookups;
-                    }
-                }
-                const uint64_t m = __ballot(matched);
-                if (lane == 0) mask[(c - c0) * rounds + round] = m;
-            }
-        }
-    }
-    const unsigned long long wave_lookups = wave_incl_add(lookups);     // one atomic per wave
-    if (lane == 63 && wave_lookups) atomicAdd(a.lookups, wave_lookups);
-}
 
 // reads [r0, r1) of the batch: one group.  single = max_c total_c; best = the lowest c that attains it
 __global__ __launch_bounds__(SB) void k_sg_single(Layout l, uint64_t r0, uint64_t r1, uint32_t *__restrict__ single, uint32_t *__restrict__ best,
@@ -494,40 +344,14 @@ struct Group {
 
 }   // namespace
 
-struct taxor_gpu_segments {
-    taxor_gpu_index *idx = nullptr;
-    int device = 0;
+struct taxor_gpu_segments : ReadAnalysis {
     uint32_t switch_cost = SEGMENTS_DEFAULT_SWITCH_COST;
-    uint64_t n_bins = 0, budget_words = SG_BUDGET_WORDS;
-    const IxfDesc *d_ixf = nullptr;
-    hipStream_t st = nullptr;
-    std::mutex mu;                                    // batches may come from several threads
-    DeviceBuf<uint64_t> d_leaf_off, d_hashes[2], d_mask, d_sw;
-    DeviceBuf<uint32_t> d_a, d_err;
-    DeviceBuf<uint2> d_leaf;
-    DeviceBuf<Piece> d_pieces[2];
+    uint64_t budget_words = SG_BUDGET_WORDS;
+    DeviceBuf<uint64_t> d_mask, d_sw;
+    DeviceBuf<uint32_t> d_a;
     DeviceBuf<unsigned long long> d_lookups;
-    Piece *h_pieces[2] = {nullptr, nullptr};          // page-locked; ev_free[i] says that buffer i's copy has left it
-    hipEvent_t ev_free[2] = {nullptr, nullptr};
-    bool ev_used[2] = {false, false};
-    std::vector<hipEvent_t> ev_time;                  // pairs around the kernel launches of one call
-    std::vector<uint32_t> h_nh;
     std::vector<Group> groups;
     std::map<const void *, std::unique_ptr<Slot>> slots;
-    // host arrays of add_csr on the device
-    DeviceBuf<uint64_t> c_off;
-    DeviceBuf<int64_t> c_ub;
-    DeviceBuf<uint32_t> c_cnt, c_nh;
-    ~taxor_gpu_segments()
-    {
-        slots.clear();
-        for (int i = 0; i < 2; ++i) {
-            if (h_pieces[i]) (void)hipHostFree(h_pieces[i]);
-            if (ev_free[i]) (void)hipEventDestroy(ev_free[i]);
-        }
-        for (hipEvent_t e : ev_time) (void)hipEventDestroy(e);
-        if (st) (void)hipStreamDestroy(st);
-    }
 };
 
 namespace {
@@ -590,22 +414,11 @@ int add_device(taxor_gpu_segments *c, const void *who, uint64_t n, const uint64_
     out->seconds_kernels = 0;
     out->lookups = 0;
     sl.h_seg_off[0] = 0;
-    if (c->ev_used[0] || c->ev_used[1]) {              // a call that failed half-way: its copies out of the page-locked pieces end first
-        SG_TRY(hipStreamSynchronize(c->st));
-        c->ev_used[0] = c->ev_used[1] = false;
-    }
+    if (int rc = c->stage.recover()) return rc;
     if (n == 0) return TAXOR_OK;
-
-    size_t n_ev = 0;
-    auto stamp = [&]() -> int {                        // an event on the stream: launches are timed between pairs of them
-        if (c->ev_time.size() <= n_ev) {
-            hipEvent_t e = nullptr;
-            SG_TRY(hipEventCreate(&e));
-            c->ev_time.push_back(e);
-        }
-        SG_TRY(hipEventRecord(c->ev_time[n_ev++], c->st));
-        return TAXOR_OK;
-    };
+    const uint64_t n_bins = c->leaf.n_bins;
+    c->timer.begin();
+    auto stamp = [&]() { return c->timer.stamp(c->st); };
 
     // the words of a read that is not examined are 0
     SG_TRY(hipMemsetAsync(sl.d_nseg.p, 0, n * sizeof(uint32_t), c->st));
@@ -617,16 +430,16 @@ int add_device(taxor_gpu_segments *c, const void *who, uint64_t n, const uint64_
     SG_TRY(hipMemsetAsync(sl.d_value.p, 0, n * sizeof(long long), c->st));
     SG_TRY(hipMemsetAsync(c->d_lookups.p, 0, 8, c->st));
     if (int rc = stamp()) return rc;
-    k_sg_count<<<grid_for(n, SWV, S_GRID_CAP), SB, 0, c->st>>>(d_off, d_ub, d_cnt, t0, d_nh, n, c->n_bins, sl.d_n_cand.p, c->d_err.p);
+    k_cand_count<uint32_t><<<grid_for(n, SWV, S_GRID_CAP), SB, 0, c->st>>>(d_off, d_ub, d_cnt, t0, d_nh, n, n_bins, sl.d_n_cand.p, c->d_err.p);
     SG_TRY(hipGetLastError());
     if (int rc = stamp()) return rc;
     uint32_t err = 0;
     SG_TRY(hipMemcpyAsync(h_m, sl.d_n_cand.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
     SG_TRY(hipMemcpyAsync(&err, c->d_err.p, 4, hipMemcpyDeviceToHost, c->st));
     SG_TRY(hipStreamSynchronize(c->st));
-    if (err & SG_BAD_BIN) {
-        SG_TRY(hipMemset(c->d_err.p, 0, 4));
-        return fail(TAXOR_E_INTERNAL, "segments_add: user_bin: a tuple names a user bin outside the index's %llu", (unsigned long long)c->n_bins);
+    if (err & CAND_BAD_BIN) {
+        if (int rc = c->clear_err()) return rc;
+        return fail(TAXOR_E_INTERNAL, "segments_add: user_bin: a tuple names a user bin outside the index's %llu", (unsigned long long)n_bins);
     }
     // who is examined; the candidates' offsets; groups of reads whose masks stay within the budget, a read that exceeds it by itself
     // alone; where a read's masks (and switch words) and its a lie within its group's scratch
@@ -681,67 +494,47 @@ int add_device(taxor_gpu_segments *c, const void *who, uint64_t n, const uint64_
         SG_TRY(sl.d_cand_ub.reserve(n_cand, n_cand + n_cand / 2));
         SG_TRY(hipMemcpyAsync(sl.d_off3.p, sl.h_off3, (3 * n + 1) * 8, hipMemcpyHostToDevice, c->st));
         if (int rc = stamp()) return rc;
-        k_sg_fill<<<grid_for(n, SWV, S_GRID_CAP), SB, 0, c->st>>>(d_off, d_ub, d_cnt, t0, n, c->n_bins, sl.d_off3.p, sl.d_cand_tuple.p, sl.d_cand_ub.p, c->d_err.p);
+        k_cand_fill<false><<<grid_for(n, SWV, S_GRID_CAP), SB, 0, c->st>>>(d_off, d_ub, d_cnt, t0, n, n_bins, nullptr, sl.d_off3.p, sl.d_cand_tuple.p, sl.d_cand_ub.p, nullptr,
+                                                                           c->d_err.p);
         SG_TRY(hipGetLastError());
         if (int rc = stamp()) return rc;
 
-        ProbeArgs a{};
-        a.ixf = c->d_ixf;
-        a.leaf_off = c->d_leaf_off.p;
-        a.leaf = c->d_leaf.p;
-        a.l = Layout{sl.d_off3.p, sl.d_cand_tuple.p, sl.d_cand_ub.p, sl.d_off3.p + n + 1, sl.d_off3.p + 2 * n + 1, d_nh, c->d_mask.p, c->d_sw.p, c->d_a.p, sl.d_state.p};
-        a.lookups = c->d_lookups.p;
-        // Pieces are staged and launched in bounded sets (breakpoint.hip's scheme): at most STAGE_PIECES pieces whose hashes lie within
-        // STAGE_HASHES consecutive entries of the dense host array, copied as one range.  A group's sets come first, then its Viterbi
-        // pass and the first trace; the host sums the group's K, and the second trace and the segments' hits follow before the next
-        // group writes the same scratch behind them on the stream
-        int buf = 0;
-        uint32_t n_p = 0;
-        uint64_t g0 = 0, g1 = 0;            // the set's hashes: [g0, g1) of hashes
-        auto flush = [&]() -> int {
-            if (n_p == 0) return TAXOR_OK;
-            SG_TRY(hipMemcpyAsync(c->d_hashes[buf].p, hashes + g0, (g1 - g0) * 8, hipMemcpyHostToDevice, c->st));
-            SG_TRY(hipMemcpyAsync(c->d_pieces[buf].p, c->h_pieces[buf], (uint64_t)n_p * sizeof(Piece), hipMemcpyHostToDevice, c->st));
-            SG_TRY(hipEventRecord(c->ev_free[buf], c->st));
-            c->ev_used[buf] = true;
-            a.pieces = c->d_pieces[buf].p;
-            a.hashes = c->d_hashes[buf].p;
+        Layout l{};
+        l.cand_off = sl.d_off3.p;
+        l.cand_ub = sl.d_cand_ub.p;
+        l.mask_off = sl.d_off3.p + n + 1;
+        l.nh = d_nh;
+        l.mask = c->d_mask.p;
+        l.cand_tuple = sl.d_cand_tuple.p;
+        l.a_off = sl.d_off3.p + 2 * n + 1;
+        l.sw = c->d_sw.p;
+        l.a = c->d_a.p;
+        l.state = sl.d_state.p;
+        MaskProbeArgs a{c->leaf.d_ixf, c->leaf.d_off.p, c->leaf.d_leaf.p, l, nullptr, nullptr, 0, c->d_lookups.p};
+        c->stage.begin(hashes, [&](const Piece *pieces, const uint64_t *staged, uint32_t n_p) {
+            a.pieces = pieces;
+            a.hashes = staged;
             a.n_pieces = n_p;
-            if (int rc = stamp()) return rc;
-            k_sg_probe<<<grid_for(n_p, SWV, S_GRID_CAP), SB, 0, c->st>>>(a);
-            SG_TRY(hipGetLastError());
-            if (int rc = stamp()) return rc;
-            buf ^= 1;
-            n_p = 0;
-            if (c->ev_used[buf]) SG_TRY(hipEventSynchronize(c->ev_free[buf]));     // the page-locked pieces of two sets ago have been copied
-            return TAXOR_OK;
-        };
+            k_probe_mask<true><<<grid_for(n_p, SWV, S_GRID_CAP), SB, 0, c->st>>>(a);
+        });
+        // A group's sets come first, then its Viterbi pass and the first trace; the host sums the group's K, and the second trace and
+        // the segments' hits follow before the next group writes the same scratch behind them on the stream
         uint64_t r_done = 0;                // seg_off[0 .. r_done] is final
         for (const Group &g : c->groups) {
-            for (uint64_t r = g.r0; r < g.r1; ++r) {
-                if (!sl.h_examined[r]) continue;
-                const uint64_t h0 = hash_off[r], nh = h_nh[r];
-                for (uint64_t done = 0; done < nh;) {
-                    const uint32_t take = (uint32_t)std::min<uint64_t>(SG_SPLIT, nh - done);
-                    if (n_p && (n_p == STAGE_PIECES || h0 + done + take - g0 > STAGE_HASHES))
-                        if (int rc = flush()) return rc;
-                    if (n_p == 0) g0 = h0 + done;
-                    c->h_pieces[buf][n_p++] = Piece{(uint32_t)r, (uint32_t)(h0 + done - g0), take, (uint32_t)done};
-                    done += take;
-                    g1 = h0 + done;
-                }
-            }
-            if (int rc = flush()) return rc;
+            for (uint64_t r = g.r0; r < g.r1; ++r)
+                if (sl.h_examined[r])
+                    if (int rc = c->stage.add(r, hash_off[r], h_nh[r])) return rc;
+            if (int rc = c->stage.flush()) return rc;
             const uint64_t gn = g.r1 - g.r0;
             if (int rc = stamp()) return rc;
-            k_sg_single<<<grid_for(gn, SWV, S_GRID_CAP), SB, 0, c->st>>>(a.l, g.r0, g.r1, sl.d_single.p, sl.d_best.p, sl.d_tuple_best.p, sl.d_bin_best.p);
-            k_sg_viterbi<<<grid_for(gn, SWV, S_GRID_CAP), SB, 0, c->st>>>(a.l, g.r0, g.r1, (uint64_t)c->switch_cost, sl.d_e.p, sl.d_value.p);
-            k_sg_trace_count<<<grid_for(gn, SB, S_GRID_CAP), SB, 0, c->st>>>(a.l, g.r0, g.r1, sl.d_e.p, sl.d_nseg.p, c->d_err.p);
+            k_sg_single<<<grid_for(gn, SWV, S_GRID_CAP), SB, 0, c->st>>>(l, g.r0, g.r1, sl.d_single.p, sl.d_best.p, sl.d_tuple_best.p, sl.d_bin_best.p);
+            k_sg_viterbi<<<grid_for(gn, SWV, S_GRID_CAP), SB, 0, c->st>>>(l, g.r0, g.r1, (uint64_t)c->switch_cost, sl.d_e.p, sl.d_value.p);
+            k_sg_trace_count<<<grid_for(gn, SB, S_GRID_CAP), SB, 0, c->st>>>(l, g.r0, g.r1, sl.d_e.p, sl.d_nseg.p, c->d_err.p);
             SG_TRY(hipGetLastError());
             if (int rc = stamp()) return rc;
             SG_TRY(hipMemcpyAsync(h_nseg + g.r0, sl.d_nseg.p + g.r0, gn * sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
             SG_TRY(hipStreamSynchronize(c->st));
-            c->ev_used[0] = c->ev_used[1] = false;
+            c->stage.synced();
             // K summed over the reported reads, like M above
             for (uint64_t r = r_done; r < g.r1; ++r) {
                 sl.h_seg_off[r] = seg_total;
@@ -764,8 +557,8 @@ int add_device(taxor_gpu_segments *c, const void *who, uint64_t n, const uint64_
             SG_TRY(hipMemcpyAsync(sl.d_seg_off.p + g.r0, sl.h_seg_off + g.r0, (gn + 1) * 8, hipMemcpyHostToDevice, c->st));
             const SegOut so{sl.d_seg_off.p, sl.d_seg_start.p, sl.d_seg_end.p, sl.d_seg_cand.p, sl.d_seg_tuple.p, sl.d_seg_bin.p};
             if (int rc = stamp()) return rc;
-            k_sg_trace_fill<<<grid_for(gn, SB, S_GRID_CAP), SB, 0, c->st>>>(a.l, g.r0, g.r1, sl.d_e.p, sl.d_nseg.p, so, c->d_err.p);
-            k_sg_hits<<<grid_for(gn, SWV, S_GRID_CAP), SB, 0, c->st>>>(a.l, g.r0, g.r1, sl.d_best.p, so, sl.d_seg_hits.p, sl.d_seg_best.p);
+            k_sg_trace_fill<<<grid_for(gn, SB, S_GRID_CAP), SB, 0, c->st>>>(l, g.r0, g.r1, sl.d_e.p, sl.d_nseg.p, so, c->d_err.p);
+            k_sg_hits<<<grid_for(gn, SWV, S_GRID_CAP), SB, 0, c->st>>>(l, g.r0, g.r1, sl.d_best.p, so, sl.d_seg_hits.p, sl.d_seg_best.p);
             SG_TRY(hipGetLastError());
             if (int rc = stamp()) return rc;
         }
@@ -803,15 +596,11 @@ int add_device(taxor_gpu_segments *c, const void *who, uint64_t n, const uint64_
     SG_TRY(hipMemcpyAsync(&lookups, c->d_lookups.p, 8, hipMemcpyDeviceToHost, c->st));
     SG_TRY(hipMemcpyAsync(&err, c->d_err.p, 4, hipMemcpyDeviceToHost, c->st));
     SG_TRY(hipStreamSynchronize(c->st));               // the searcher's buffers and the hash lists are the caller's again
-    c->ev_used[0] = c->ev_used[1] = false;
-    for (size_t i = 0; i + 1 < n_ev; i += 2) {
-        float ms = 0;
-        SG_TRY(hipEventElapsedTime(&ms, c->ev_time[i], c->ev_time[i + 1]));
-        out->seconds_kernels += (double)ms * 1e-3;
-    }
+    c->stage.end();
+    if (int rc = c->timer.add_to(&out->seconds_kernels)) return rc;
     out->lookups = lookups;
     if (err) {                                         // the CSR changed under the call, or a trace left the read's candidates
-        SG_TRY(hipMemset(c->d_err.p, 0, 4));
+        if (int rc = c->clear_err()) return rc;
         return fail(TAXOR_E_INTERNAL, "segments_add: candidates: a second walk disagrees with the first (the candidates' or the trace's; flags %u)", err);
     }
     // value = (hits - L * switches) * 2^32 - switches, and switches = K - 1
@@ -840,68 +629,19 @@ extern "C" int taxor_gpu_segments_create(taxor_gpu_index *idx, const taxor_hixf_
     if (switch_cost < 1 || switch_cost > SEGMENTS_MAX_SWITCH_COST)
         return fail(TAXOR_E_ARG, "segments_create: switch_cost: %u is outside [1, %u] (a switch that costs nothing is taken at every hash; above 2^20 the cost leaves the value's 63 bits)",
                     switch_cost, SEGMENTS_MAX_SWITCH_COST);
-    const IxfDesc *d_ixf = nullptr, *h_ixf = nullptr;
-    uint64_t n_ixf = 0, n_bins = 0;
-    uint32_t n_passes = 0;
-    int device = 0;
-    if (taxor_index_descs(idx, &d_ixf, &h_ixf, &n_ixf, &n_bins, &n_passes, &device)) return fail(TAXOR_E_ARG, "segments_create: null index");
-    if (n_passes)
-        return fail(TAXOR_E_ARG, "segments_create: a paged index (%u resident pass%s) is refused: its leaf bins are not all resident at once and a read's final tuples exist only after the last pass's merge; segmenting pass by pass is not built",
-                    n_passes, n_passes == 1 ? "" : "es");
-    if (view->n_ixf != n_ixf || view->n_user_bins != n_bins || (n_ixf && !view->ixf))
-        return fail(TAXOR_E_ARG, "segments_create: the view (%llu IXFs, %llu user bins) is not the index's (%llu IXFs, %llu user bins)", (unsigned long long)view->n_ixf,
-                    (unsigned long long)view->n_user_bins, (unsigned long long)n_ixf, (unsigned long long)n_bins);
-    if (n_bins >= (1ull << 32) || n_ixf >= (1ull << 32)) return fail(TAXOR_E_ARG, "segments_create: user bins and IXFs are numbered in 32 bits");
-    // the inverse of fname_idx: every leaf technical bin of a user bin, root included, as one CSR in index order (breakpoint.hip's table,
-    // restated: that file, and its object, stay as they are)
-    std::vector<uint64_t> leaf_off(n_bins + 1, 0);
-    for (uint64_t x = 0; x < n_ixf; ++x) {
-        const taxor_ixf_view &f = view->ixf[x];
-        if (f.bins != h_ixf[x].bins) return fail(TAXOR_E_ARG, "segments_create: IXF %llu has %llu bins in the view, %u in the index", (unsigned long long)x, (unsigned long long)f.bins, h_ixf[x].bins);
-        if (!f.fname_idx) return fail(TAXOR_E_ARG, "segments_create: IXF %llu of the view has no fname_idx", (unsigned long long)x);
-        for (uint64_t j = 0; j < f.bins; ++j) {
-            const int64_t b = f.fname_idx[j];
-            if (b < 0) continue;
-            if ((uint64_t)b >= n_bins) return fail(TAXOR_E_ARG, "segments_create: bin %llu of IXF %llu names user bin %lld of %llu", (unsigned long long)j, (unsigned long long)x, (long long)b, (unsigned long long)n_bins);
-            ++leaf_off[(uint64_t)b + 1];
-        }
-    }
-    for (uint64_t b = 0; b < n_bins; ++b) leaf_off[b + 1] += leaf_off[b];
-    std::vector<uint2> leaf(leaf_off[n_bins]);
-    {
-        std::vector<uint64_t> at(leaf_off.begin(), leaf_off.end() - 1);
-        for (uint64_t x = 0; x < n_ixf; ++x)
-            for (uint64_t j = 0; j < view->ixf[x].bins; ++j) {
-                const int64_t b = view->ixf[x].fname_idx[j];
-                if (b >= 0) leaf[at[(uint64_t)b]++] = make_uint2((uint32_t)x, (uint32_t)j);
-            }
-    }
-    SG_TRY(hipSetDevice(device));
     auto c = std::make_unique<taxor_gpu_segments>();
-    c->idx = idx;
-    c->device = device;
+    if (int rc = c->leaf.build("segments_create", "its leaf bins are not all resident at once and a read's final tuples exist only after the last pass's merge; segmenting pass by pass is not built", idx, view))
+        return rc;
+    if (int rc = c->stage.configure("segments_create")) return rc;
     c->switch_cost = switch_cost;
-    c->n_bins = n_bins;
-    c->d_ixf = d_ixf;
     // a measurement knob (tuning.h): the mask words of one group of reads.  It moves the cut into groups, never a result
     if (const char *e = tune_env("TAXOR_SEGMENTS_BUDGET_WORDS")) {
         const long long v = atoll(e);
         if (v >= 1) c->budget_words = (uint64_t)v;
     }
-    SG_TRY(hipStreamCreate(&c->st));
-    SG_TRY(c->d_leaf_off.alloc(n_bins + 1));
-    SG_TRY(c->d_leaf.alloc(leaf.size() + 1));
-    SG_TRY(c->d_err.alloc(1));
+    SG_TRY(hipSetDevice(c->leaf.device));
+    if (int rc = c->open("segments")) return rc;
     SG_TRY(c->d_lookups.alloc(1));
-    for (int i = 0; i < 2; ++i) {
-        SG_TRY(c->d_hashes[i].alloc(STAGE_HASHES));
-        SG_TRY(c->d_pieces[i].alloc(STAGE_PIECES));
-        SG_TRY(hipHostMalloc((void **)&c->h_pieces[i], STAGE_PIECES * sizeof(Piece), hipHostMallocDefault));
-        SG_TRY(hipEventCreateWithFlags(&c->ev_free[i], hipEventDisableTiming));
-    }
-    SG_TRY(hipMemcpy(c->d_leaf_off.p, leaf_off.data(), (n_bins + 1) * 8, hipMemcpyHostToDevice));
-    if (!leaf.empty()) SG_TRY(hipMemcpy(c->d_leaf.p, leaf.data(), leaf.size() * 8, hipMemcpyHostToDevice));
-    SG_TRY(hipMemset(c->d_err.p, 0, 4));
     *out = c.release();
     return TAXOR_OK;
 }
@@ -909,66 +649,27 @@ extern "C" int taxor_gpu_segments_create(taxor_gpu_index *idx, const taxor_hixf_
 extern "C" void taxor_gpu_segments_destroy(taxor_gpu_segments *c)
 {
     if (!c) return;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->leaf.device);
     delete c;
 }
 
 extern "C" int taxor_gpu_segments_add_batch(taxor_gpu_segments *c, taxor_gpu_searcher *s, const taxor_gpu_saved *saved, taxor_segments_batch *out)
 {
     if (!c || !s || !out) return fail(TAXOR_E_ARG, "segments_add_batch: null argument");
-    if (!saved) return fail(TAXOR_E_ARG, "segments_add_batch: saved: no saved batch (the batch ran with capture off, or its lists were not taken)");
-    if (taxor_searcher_index(s) != c->idx) return fail(TAXOR_E_ARG, "segments_add_batch: index: the searcher works on another index than the segments object");
-    const std::string unsound = saved_validate(*saved);
-    if (!unsound.empty()) return fail(TAXOR_E_ARG, "segments_add_batch: " + unsound);
-    const uint64_t *d_off = nullptr;
-    const int64_t *d_ub = nullptr;
-    const uint32_t *d_cnt = nullptr, *d_nh = nullptr;
-    uint64_t n = 0, nt = 0;
-    int dev = 0;
-    if (int rc = taxor_searcher_device_results(s, &d_off, &d_ub, &d_cnt, &d_nh, &n, &nt, &dev)) return rc;
-    if (saved->n_reads != n)
-        return fail(TAXOR_E_ARG, "segments_add_batch: n_reads: the saved batch holds %llu reads, the searcher's last batch %llu", (unsigned long long)saved->n_reads, (unsigned long long)n);
-    if (n >= MAX_READS) return fail(TAXOR_E_ARG, "segments_add_batch: n_reads: a batch of 2^31 reads or more");
-    std::lock_guard<std::mutex> lk(c->mu);
-    SG_TRY(hipSetDevice(c->device));
-    c->h_nh.resize(n);
-    if (n) SG_TRY(hipMemcpy(c->h_nh.data(), d_nh, n * 4, hipMemcpyDeviceToHost));
-    for (uint64_t r = 0; r < n; ++r)
-        if (c->h_nh[r] != saved->n_hashes[r])
-            return fail(TAXOR_E_ARG, "segments_add_batch: n_hashes: read %llu has %u hashes in the saved batch, %u in the searcher's last batch", (unsigned long long)r, saved->n_hashes[r], c->h_nh[r]);
-    return add_device(c, s, n, d_off, d_ub, d_cnt, d_nh, 0, saved->hash_off.data(), saved->hashes, c->h_nh.data(), out);
+    std::unique_lock<std::mutex> lk;
+    SearcherBatch b;
+    if (int rc = begin_batch("segments_add_batch", "segments", "the segments object", *c, s, saved, lk, &b)) return rc;
+    return add_device(c, s, b.n, b.d_off, b.d_ub, b.d_cnt, b.d_nh, 0, saved->hash_off.data(), saved->hashes, c->h_nh.data(), out);
 }
 
 extern "C" int taxor_gpu_segments_add_csr(taxor_gpu_segments *c, uint64_t n_reads, const uint64_t *read_off, const int64_t *user_bin, const uint32_t *count,
                                           const uint64_t *hash_off, const uint64_t *hashes, taxor_segments_batch *out)
 {
     if (!c || !read_off || !hash_off || !out) return fail(TAXOR_E_ARG, "segments_add_csr: null argument");
-    if (n_reads >= MAX_READS) return fail(TAXOR_E_ARG, "segments_add_csr: n_reads: 2^31 reads or more");
-    for (uint64_t r = 0; r < n_reads; ++r) {
-        if (read_off[r + 1] < read_off[r] || read_off[r + 1] - read_off[r] >= (1ull << 32))
-            return fail(TAXOR_E_ARG, "segments_add_csr: read_off: the tuples of read %llu are malformed", (unsigned long long)r);
-        if (hash_off[r + 1] < hash_off[r] || hash_off[r + 1] - hash_off[r] >= (1ull << 32))
-            return fail(TAXOR_E_ARG, "segments_add_csr: hash_off: the list of read %llu is malformed", (unsigned long long)r);
-    }
-    const uint64_t t0 = read_off[0], nt = read_off[n_reads] - t0;
-    if (nt && (!user_bin || !count)) return fail(TAXOR_E_ARG, "segments_add_csr: user_bin / count: null array");
-    if (hash_off[n_reads] > hash_off[0] && !hashes) return fail(TAXOR_E_ARG, "segments_add_csr: hashes: null array");
-    for (uint64_t i = t0; i < t0 + nt; ++i)
-        if (user_bin[i] < 0 || (uint64_t)user_bin[i] >= c->n_bins)
-            return fail(TAXOR_E_ARG, "segments_add_csr: user_bin: tuple %llu names user bin %lld, the index has %llu", (unsigned long long)i, (long long)user_bin[i], (unsigned long long)c->n_bins);
+    CsrUpload &u = c->csr;
     std::lock_guard<std::mutex> lk(c->mu);
-    SG_TRY(hipSetDevice(c->device));
-    c->h_nh.resize(n_reads);
-    for (uint64_t r = 0; r < n_reads; ++r) c->h_nh[r] = (uint32_t)(hash_off[r + 1] - hash_off[r]);
-    SG_TRY(c->c_off.reserve(n_reads + 1, n_reads + 1 + n_reads / 2));
-    SG_TRY(c->c_nh.reserve(n_reads + 1, n_reads + 1 + n_reads / 2));
-    SG_TRY(c->c_ub.reserve(nt + 1, nt + 1 + nt / 2));
-    SG_TRY(c->c_cnt.reserve(nt + 1, nt + 1 + nt / 2));
-    SG_TRY(hipMemcpy(c->c_off.p, read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice));
-    if (nt) {
-        SG_TRY(hipMemcpy(c->c_ub.p, user_bin + t0, nt * 8, hipMemcpyHostToDevice));
-        SG_TRY(hipMemcpy(c->c_cnt.p, count + t0, nt * 4, hipMemcpyHostToDevice));
-    }
-    if (n_reads) SG_TRY(hipMemcpy(c->c_nh.p, c->h_nh.data(), n_reads * 4, hipMemcpyHostToDevice));
-    return add_device(c, nullptr, n_reads, c->c_off.p, c->c_ub.p, c->c_cnt.p, c->c_nh.p, t0, hash_off, hashes, c->h_nh.data(), out);
+    if (int rc = u.check("segments_add_csr", "index", c->leaf.n_bins, n_reads, read_off, user_bin, count, hash_off, hashes)) return rc;
+    SG_TRY(hipSetDevice(c->leaf.device));
+    if (int rc = u.upload("segments", n_reads, read_off, user_bin, count, hash_off, nullptr, &c->h_nh)) return rc;
+    return add_device(c, nullptr, n_reads, u.off.p, u.ub.p, u.cnt.p, u.nh.p, u.t0, hash_off, hashes, c->h_nh.data(), out);
 }

@@ -47,6 +47,23 @@ class Expect:
             m |= (d[rows[:, 0], j] ^ d[rows[:, 1], j] ^ d[rows[:, 2], j]) == fp
         return m
 
+    def lookups(self, b, hashes, stop_at_first):
+        """leaf-bin lookups the device makes for `hashes` against user bin b (read_probe.h's leaf_lookup): per hash the number of b's
+        leaf bins, or with stop_at_first the index of the first matching leaf bin plus one (all of them when none matches)"""
+        leaves = self.leaves.get(b, [])
+        n = len(hashes)
+        if not stop_at_first or n == 0:
+            return n * len(leaves)
+        made = np.full(n, len(leaves), np.int64)
+        open_ = np.ones(n, bool)
+        for at, (x, j) in enumerate(leaves):
+            rows, fp = self._probes(x, hashes)
+            d = self.data[x]
+            hit = open_ & ((d[rows[:, 0], j] ^ d[rows[:, 1], j] ^ d[rows[:, 2], j]) == fp)
+            made[hit] = at + 1
+            open_ &= ~hit
+        return int(made.sum())
+
     def add_read(self, hashes, user_bin, count, times=1):
         """one read: its hash list and its tuples before the 0.8 * max filter.  Returns the surviving (user bin, count) pairs"""
         if len(count) == 0:
@@ -99,3 +116,33 @@ def same(table, exp, p=12):
     assert np.array_equal(table.hash_matches, exp.hash_matches)
     want = exp.registers(p)
     assert np.array_equal(table.registers, want), np.argwhere(table.registers != want)[:8]
+
+
+def candidate_lookups(cov, reads, min_candidates):
+    """the leaf-bin lookups breakpoint.hip, segments.hip and exclusive.hip count for hand-made (what, tuples, hashes) reads: a read is
+    examined when it has a hash and at least min_candidates candidates (tuples with count > 0); every candidate of an examined read is
+    looked up for every hash of the read, and a lookup stops at the candidate's first matching leaf bin"""
+    total, memo = 0, {}
+    for _, tuples, hashes in reads:
+        cand = [int(b) for b, c in tuples if c > 0]
+        if len(hashes) == 0 or len(cand) < min_candidates:
+            continue
+        h = np.asarray(hashes, np.uint64)
+        for b in cand:
+            key = (b, h.tobytes())
+            if key not in memo:
+                memo[key] = cov.lookups(b, h, True)
+            total += memo[key]
+    return total
+
+
+STAGE_CUT = {"TAXOR_TUNING": "1", "TAXOR_STAGE_HASHES": "4096", "TAXOR_STAGE_PIECES": "3"}
+
+
+def same_results(a, b):
+    """two result objects of one class hold equal arrays and equal counters; the seconds are left out"""
+    for k, v in vars(a).items():
+        if isinstance(v, np.ndarray):
+            assert np.array_equal(v, getattr(b, k)), k
+        elif not k.startswith("seconds"):
+            assert v == getattr(b, k), k

@@ -7,6 +7,7 @@ from oracle import oracle as orc
 from taxor_amd import GpuIndex, Searcher, _lib, synth
 from taxor_amd.search import Breakpoints
 from tests import breakpoint_expect as be
+from tests.coverage_expect import STAGE_CUT, candidate_lookups, same_results
 from tests.coverage_expect import Expect as CovExpect
 from tests.test_gpu_coverage import _cat
 from tests.test_gpu_hitmap import COUNTS, _run, world  # noqa: F401  (the hit map tests' world, reused)
@@ -103,6 +104,7 @@ def test_hand_made_reads_equal_the_expectation(world, hand, G):
     assert not rep["one dominates"] and not rep["no hash"] and rep["gain 5"] and rep["break at 2048"]
     assert rep["gain 4"] == (G == 1) and rep["gain 1"] == (G == 1)                           # the boundary G - 1 / G
     assert got.lookups > 0 and got.seconds_kernels > 0
+    assert got.lookups == candidate_lookups(w["expect"].cov, hand["reads"], 2)               # every candidate of an examined read, every hash
     assert (got.tuple_a[got.gain > 0] != got.tuple_b[got.gain > 0]).all()                    # A != B wherever the split gains
 
 
@@ -119,6 +121,19 @@ def test_two_adds_and_small_scratch_equal_one(world, hand, monkeypatch):
     monkeypatch.setenv("TAXOR_BREAKPOINT_BUDGET_WORDS", "64")
     with Breakpoints(w["idx"], w["host"]) as bp:
         be.same(bp.add_csr(off, ub, cnt, hoff, hashes), e)
+
+
+def test_the_stage_cut_does_not_matter(world, hand, monkeypatch):
+    """staging buffers of 4096 hashes and 3 pieces: the pieces of the reads of 2047, 2048 and 2049 + 40 hashes fall into different sets"""
+    w, e = world, hand["e"]
+    with Breakpoints(w["idx"], w["host"]) as bp:
+        plain = bp.add_csr(*csr(hand["reads"]))
+    for k, v in STAGE_CUT.items():
+        monkeypatch.setenv(k, v)
+    with Breakpoints(w["idx"], w["host"]) as bp:
+        cut = bp.add_csr(*csr(hand["reads"]))
+    be.same(cut, e)
+    same_results(cut, plain)
 
 
 @pytest.fixture(scope="module")

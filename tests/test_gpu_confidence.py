@@ -8,6 +8,7 @@ from taxor_amd import GpuIndex, Searcher, _lib, synth
 from taxor_amd.search import Confidence, Lca, Lineage
 from tests import confidence_expect as ce
 from tests import lca_expect as le
+from tests.coverage_expect import STAGE_CUT, same_results
 from tests.coverage_expect import Expect as CovExpect
 from tests.test_gpu_coverage import _cat, _layout
 from tests.test_gpu_lca import species
@@ -323,3 +324,21 @@ def test_refusals_come_before_any_launch(world):
         assert got.node.size == 10 and (got.node != _lib.LCA_UNCLASSIFIED).any()
         sv10.close()
     sr.close()
+
+
+def test_the_stage_cut_does_not_matter(world, monkeypatch):
+    """staging buffers of 4096 hashes and 3 pieces: the pieces of the reads of 2048, 2049 and 5245 hashes fall into different sets.  The
+    three counters are printed: the skip schedule is not derived, they are compared between versions of the library"""
+    w = world
+    e = w["expect"][0.5]
+    with Confidence(w["idx"], w["host"], w["glin"], 0.5) as cf:
+        plain, plain_t = cf.add_csr(*csr(w["hand"])), cf.results()
+    for k, v in STAGE_CUT.items():
+        monkeypatch.setenv(k, v)
+    with Confidence(w["idx"], w["host"], w["glin"], 0.5) as cf:
+        cut, cut_t = cf.add_csr(*csr(w["hand"])), cf.results()
+    print("confidence counters (probes, tuple_steps, tuple_steps_full):", plain.probes, plain.tuple_steps, plain.tuple_steps_full)
+    ce.same(cut, e)
+    ce.same_tallies(cut_t, e)
+    same_results(cut, plain)
+    same_results(cut_t, plain_t)

@@ -8,7 +8,7 @@ import pytest
 from oracle import oracle as orc
 from taxor_amd import GpuIndex, Searcher, _lib, synth
 from taxor_amd.search import Coverage
-from tests.coverage_expect import Expect, same
+from tests.coverage_expect import STAGE_CUT, Expect, same, same_results
 
 pytestmark = pytest.mark.gpu
 
@@ -138,6 +138,8 @@ def test_one_batch_equals_the_expectation(world, expect_all):
     both = [s for s in surv if {ub[1], ub["1 again"]} <= {b for b, _ in s}]
     assert both
     assert t.probes > 0 and t.seconds_kernels > 0
+    # every surviving tuple of every read, every hash of the read, every leaf bin of the tuple's user bin
+    assert t.probes == sum(e.lookups(b, range(nh[r]), False) for r, s in enumerate(surv) for b, _ in s)
     # genome 3's bin (the long read's ~5000 hashes among them): the estimate stands within four standard errors of the exact count
     d = t.distinct(ub[3])
     n = len(e.matched[ub[3]])
@@ -301,3 +303,19 @@ def test_index_from_the_gpu_builder(world):
     sr.close()
     cap.close()
     idx.close()
+
+
+def test_the_stage_cut_does_not_matter(world, expect_all, monkeypatch):
+    """staging buffers of 4096 hashes and 3 pieces: the pieces of the long read fall into different sets"""
+    w = world
+    e, _ = expect_all
+    with Coverage(w["idx"], w["host"]) as cov:
+        _run(w, cov, w["reads"])
+        plain = cov.results()
+    for k, v in STAGE_CUT.items():
+        monkeypatch.setenv(k, v)
+    with Coverage(w["idx"], w["host"]) as cov:
+        _run(w, cov, w["reads"])
+        cut = cov.results()
+    same(cut, e)
+    same_results(cut, plain)

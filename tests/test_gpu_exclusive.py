@@ -8,6 +8,7 @@ from oracle import oracle as orc
 from taxor_amd import GpuIndex, Searcher, _lib, synth
 from taxor_amd.search import Exclusive
 from tests import exclusive_expect as xe
+from tests.coverage_expect import STAGE_CUT, candidate_lookups, same_results
 from tests.coverage_expect import Expect as CovExpect
 from tests.test_gpu_coverage import _cat
 from tests.test_gpu_hitmap import COUNTS, _run, world  # noqa: F401  (the hit map tests' world, reused)
@@ -126,6 +127,7 @@ def test_hand_made_reads_equal_the_expectation(world, hand, P):
     xe.same(got, e)
     xe.same_table(table, e, P)
     assert got.probes > 0 and got.seconds_kernels > 0 and table.probes == got.probes
+    assert got.probes == candidate_lookups(w["expect"].cov, hand["reads"], 1)                # every candidate of an examined read, every hash
     b = hand["b"]
     assert table.exclusive_hits[b] > 150 and table.exclusive_reads[b] >= 10 and table.registers[b].any()
     est = table.distinct(b)                               # 200 distinct keys of genome 3 were ever exclusive to it, and a few collisions
@@ -308,3 +310,18 @@ def test_refusals_come_before_any_launch(world):
         assert empty.examined.size == 0 and [int(v) for v in empty.cand_off] == [0]
         sv10.close()
     sr.close()
+
+
+def test_the_stage_cut_does_not_matter(world, hand, monkeypatch):
+    """staging buffers of 4096 hashes and 3 pieces: the pieces of the reads of 2047, 2048 and 2049 hashes fall into different sets"""
+    w, e = world, hand["e"]
+    with Exclusive(w["idx"], w["host"]) as ex:
+        plain, plain_table = ex.add_csr(*csr(hand["reads"])), ex.results()
+    for k, v in STAGE_CUT.items():
+        monkeypatch.setenv(k, v)
+    with Exclusive(w["idx"], w["host"]) as ex:
+        cut, cut_table = ex.add_csr(*csr(hand["reads"])), ex.results()
+    xe.same(cut, e)
+    xe.same_table(cut_table, e)
+    same_results(cut, plain)
+    same_results(cut_table, plain_table)

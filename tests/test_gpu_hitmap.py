@@ -6,6 +6,7 @@ import pytest
 from oracle import oracle as orc
 from taxor_amd import GpuIndex, Searcher, _lib, synth
 from taxor_amd.search import Hitmap
+from tests.coverage_expect import STAGE_CUT, same_results
 from tests.hitmap_expect import HitExpect, same, seg, size
 from tests.test_gpu_coverage import _cat, _layout
 
@@ -214,6 +215,8 @@ def test_the_filter_boundary_through_lists_made_by_hand(world):
     assert got.map_off[3] == got.map_off[2]               # no tuple
     t2 = [t for t in range(int(got.map_off[0]), int(got.map_off[1])) if got.user_bin[t] == ub[2]][0]
     assert got.hits[t2].tolist() == [3, 1]                # five hashes: ranks 0, 1, 2 | 3, 4; genome 2 holds the first four
+    # every mapped tuple, every hash of its read, every leaf bin of its user bin
+    assert got.probes == sum(e.cov.lookups(int(got.user_bin[t]), lists[r], False) for r in range(4) for t in range(int(got.map_off[r]), int(got.map_off[r + 1])))
     sv.close()
     sr.close()
 
@@ -330,3 +333,35 @@ def test_refusals_come_before_any_launch(world):
         assert got.map_off.size == 11 and got.count.size > 0
         sv10.close()
     sr.close()
+
+
+def test_the_stage_cut_does_not_matter(world, monkeypatch):
+    """staging buffers of 4096 hashes and 3 pieces: the pieces of the reads of 2048, 2049 and 5245 hashes fall into different sets, for
+    the lists made by hand as for the reads; a buffer that cannot hold one piece is refused"""
+    w = world
+    k0 = w["planted"][0]
+    lists = [k0[:5], k0[10:15], k0[20:25]]
+    sr, sv, _ = _replay(w["idx"], _prefix_with(w["G"][4][1000:], 5), lists, [1, 1, 5])
+    by_hand = HitExpect(w["host"])
+    for h, t in zip(lists, [1, 1, 5]):
+        by_hand.add_hash_list(h, t)
+    with Hitmap(w["idx"], w["host"], segments=2) as hm:
+        plain_hand = hm.add_batch(sr, sv)
+    with Hitmap(w["idx"], w["host"]) as hm:
+        plain, _, _, _ = _run(w, hm, w["reads"])
+    for k, v in STAGE_CUT.items():
+        monkeypatch.setenv(k, v)
+    with Hitmap(w["idx"], w["host"], segments=2) as hm:
+        cut_hand = hm.add_batch(sr, sv)
+    with Hitmap(w["idx"], w["host"]) as hm:
+        cut, _, _, _ = _run(w, hm, w["reads"])
+    sv.close()
+    sr.close()
+    same(cut_hand, by_hand, 2)
+    same(cut, w["expect"], 16)
+    same_results(cut_hand, plain_hand)
+    same_results(cut, plain)
+    monkeypatch.setenv("TAXOR_STAGE_HASHES", "2047")
+    with pytest.raises(_lib.TaxorError) as ei:
+        Hitmap(w["idx"], w["host"])
+    assert ei.value.code == -1 and "TAXOR_STAGE_HASHES" in str(ei.value)

@@ -7,6 +7,7 @@ from oracle import oracle as orc
 from taxor_amd import GpuIndex, Searcher, _lib, synth
 from taxor_amd.search import Segments
 from tests import segments_expect as se
+from tests.coverage_expect import candidate_lookups
 from tests.coverage_expect import Expect as CovExpect
 from tests.test_gpu_coverage import _cat
 from tests.test_gpu_hitmap import COUNTS, _run, world  # noqa: F401  (the hit map tests' world, reused)
@@ -136,6 +137,7 @@ def test_hand_made_reads_equal_the_expectation(world, hand, L):
         got = sg.add_csr(*csr(hand["reads"]))
     se.same(got, e)
     assert got.lookups > 0 and got.seconds_kernels > 0
+    assert got.lookups == candidate_lookups(w["expect"].cov, hand["reads"], 2)               # every candidate of an examined read, every hash
     if L == 2**20:
         assert got.n_reported == 0 and got.seg_off[-1] == 0
 
