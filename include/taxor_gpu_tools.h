@@ -320,6 +320,26 @@ int taxor_gpu_search_take_saved(taxor_gpu_searcher *s, taxor_gpu_saved **saved);
 int taxor_gpu_saved_view_get(const taxor_gpu_saved *saved, taxor_gpu_saved_view *view);
 uint64_t taxor_gpu_saved_bytes(const taxor_gpu_saved *saved);
 void taxor_gpu_saved_free(taxor_gpu_saved *saved);
+/* ---- where along its read each saved hash lies.  Syncmer indexes only.  For read r of L bases, k-mer size k
+ * and its list hashes[hash_off[r] .. hash_off[r+1]):
+ *     pos[i] = min { p in [0, L-k] : wyhash_u64(min(f_p, revcomp(f_p))) == hashes[i] }
+ * with f_p the 2-bit k-mer at base p of the packed read (after the dna4 mapping): the first base at which the read shows this k-mer, on
+ * either strand.  It is defined by CONTENT: it equals the start of the window that first emitted the hash except where the reference's
+ * stateful tie rule leaves a k-mer's first occurrence unselected and selects a later one -- pos is then the earlier occurrence, and
+ * positions need not increase with i.  The same for FracMinHash-scaled lists (a subset).
+ * on != 0, while capture is on: every batch from now on runs one more kernel per sub-batch behind the gather, on its stream
+ * (k_hash_positions: the list in pieces of 2048 hashes in an LDS table, the read's k-mers swept once per piece), and its saved batch
+ * carries a position store beside the hashes, 4 bytes per hash, copied out through a second bounded page-locked pair.  TAXOR_E_ARG, by
+ * name: capture is off; a batch is in flight; the searcher does not hash syncmers (minimiser and k-mer lists are not deduplicated and
+ * their values are not wyhash(k-mer)).  taxor_gpu_search_capture(s, 0) turns positions off as well.  A hash no k-mer of its read gives
+ * is TAXOR_E_INTERNAL, naming the read; it is never a result.  A replay (taxor_gpu_search_saved_begin) ignores positions. */
+int taxor_gpu_search_capture_positions(taxor_gpu_searcher *s, int on);
+/* *pos: [total_hashes] parallel to the view's hashes, valid until the saved batch is freed; NULL when it was captured without
+ * positions.  taxor_gpu_saved_bytes counts the store; taxor_gpu_saved_view is unchanged. */
+int taxor_gpu_saved_positions(const taxor_gpu_saved *saved, const uint32_t **pos);
+/* seconds between the event pairs around the batch's position kernels, one pair per sub-batch (0 without positions).  A sub-batch's
+ * kernel runs beside the query of the sub-batch before it: this is the time it held its stream, not its time alone on the device. */
+double taxor_gpu_saved_positions_seconds(const taxor_gpu_saved *saved);
 /* The batch again, from its saved lists: they are staged sub-batch by sub-batch (same plan, same double buffering, same queue sizing as
  * the run from bases) and queried from level 0; nothing is packed or hashed.  taxor_gpu_search_batch_end follows, and afterwards the
  * searcher is where a batch from bases leaves it: taxor_gpu_batch_fetch, _batch_export_device, taxor_gpu_results_keys,

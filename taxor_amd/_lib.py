@@ -287,6 +287,9 @@ SIGNATURES = {
     "taxor_gpu_saved_view_get": (C.c_int, [_P, C.POINTER(SavedView)]),
     "taxor_gpu_saved_bytes": (C.c_uint64, [_P]),
     "taxor_gpu_saved_free": (None, [_P]),
+    "taxor_gpu_search_capture_positions": (C.c_int, [_P, C.c_int]),
+    "taxor_gpu_saved_positions": (C.c_int, [_P, C.POINTER(C.POINTER(C.c_uint32))]),
+    "taxor_gpu_saved_positions_seconds": (C.c_double, [_P]),
     "taxor_gpu_search_saved_begin": (C.c_int, [_P, _P]),
     "taxor_saved_bytes_bound": (C.c_uint64, [C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]),
     "taxor_saved_store_fits": (C.c_int, [C.c_uint64, C.c_uint64]),

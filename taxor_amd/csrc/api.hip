@@ -132,6 +132,15 @@ struct SubBatch {
     uint64_t a_begin, a_end; // ASCII byte range of its reads within the batch
 };
 
+// taxor_gpu_search_capture_positions: every gathered hash's position in its read (positions.hip), beside the hashes all the way.
+// The object exists only while the switch is on; a searcher that never turned it on holds a null pointer and nothing else
+struct CapturePositions {
+    DeviceBuf<uint32_t> d_pos[2];                  // parallel to d_cap_dense
+    uint32_t *h_pin[2] = {nullptr, nullptr};       // parallel to h_cap_pin: kCapChunk entries each
+    std::vector<hipEvent_t> ev;                    // an event pair around every sub-batch's k_hash_positions: the kernel's own seconds of a batch
+    size_t ev_used = 0;
+};
+
 struct taxor_gpu_searcher {
     taxor_gpu_index *idx = nullptr;
     taxor_gpu_search_params prm{};
@@ -250,6 +259,7 @@ struct taxor_gpu_searcher {
     uint64_t *h_cap_total = nullptr;        // page-locked words: the hash count of sub-batch i at [i & 1]
     hipEvent_t ev_cap[2] = {nullptr, nullptr}, ev_cap_gather[2] = {nullptr, nullptr};
     hipStream_t st_cap = nullptr;           // the dense hashes' way to the host, nothing else
+    CapturePositions *cap_pos = nullptr;    // taxor_gpu_search_capture_positions is on: made there, gone when it (or capture) is turned off
     const taxor_gpu_saved *replay = nullptr;      // the batch in flight runs from these saved lists (until it is synchronised)
     bool from_saved = false;                // the last batch did: the searcher holds no packed bases to run again
 
@@ -1192,8 +1202,23 @@ static int searcher_create_impl(taxor_gpu_index *idx, const taxor_gpu_search_par
 }
 
 // the capture's buffers and an untaken saved batch go (capture off, or the searcher's end)
+static void capture_positions_release(taxor_gpu_searcher *s)
+{
+    CapturePositions *cp = s->cap_pos;
+    if (!cp) return;
+    if (s->st_cap) (void)hipStreamSynchronize(s->st_cap);
+    for (int i = 0; i < 2; ++i) {
+        cp->d_pos[i].release();
+        if (cp->h_pin[i]) (void)hipHostFree(cp->h_pin[i]);
+    }
+    for (hipEvent_t e : cp->ev) (void)hipEventDestroy(e);
+    delete cp;
+    s->cap_pos = nullptr;
+}
+
 static void capture_release(taxor_gpu_searcher *s)
 {
+    capture_positions_release(s);
     delete s->cap_cur;
     s->cap_cur = nullptr;
     s->cap_done = false;
@@ -1930,6 +1955,14 @@ int capture_begin(taxor_gpu_searcher *s)
         slots += sb.slots;
     }
     if (!b->reserve(slots)) return fail(TAXOR_E_NOMEM, "capture: no address space for %llu hashes", (unsigned long long)slots);
+    if (s->cap_pos) {
+        s->cap_pos->ev_used = 0;
+        for (int i = 0; i < 2; ++i) {
+            if (!s->cap_pos->h_pin[i]) HIP_TRY(hipHostMalloc((void **)&s->cap_pos->h_pin[i], kCapChunk * 4, hipHostMallocDefault));
+            if (reserve(s->cap_pos->d_pos[i], s->max_slots + 64)) return TAXOR_E_HIP;
+        }
+        if (!b->reserve_positions()) return fail(TAXOR_E_NOMEM, "capture: no address space for %llu positions", (unsigned long long)slots);
+    }
     return 0;
 }
 
@@ -1940,6 +1973,17 @@ int capture_launch(taxor_gpu_searcher *s, const SubBatch &sb, size_t i, int buf,
     launch_hash_offsets(s->d_nh.p + sb.first, s->d_cap_off.p, sb.n, ss);       // (d_cap_off is read by the gather behind it on the same stream only)
     launch_gather_hashes(s->d_hashes[buf].p, s->d_hoff.p + sb.first, s->d_hcap.p + sb.first, s->d_nh.p + sb.first, s->d_cap_off.p, s->d_cap_dense[c].p,
                          s->d_cap_dense[c].cap, sb.n, ss);
+    if (s->cap_pos) {          // the sub-batch's packed reads are still resident: every gathered hash gets its position (positions.hip)
+        while (s->cap_pos->ev.size() < s->cap_pos->ev_used + 2) {
+            hipEvent_t e = nullptr;
+            HIP_TRY(hipEventCreate(&e));
+            s->cap_pos->ev.push_back(e);
+        }
+        HIP_TRY(hipEventRecord(s->cap_pos->ev[s->cap_pos->ev_used++], ss));
+        launch_hash_positions(s->d_packed.p, s->d_poff.p + sb.first, s->d_rlen.p + sb.first, s->d_cap_off.p, s->d_cap_dense[c].p, s->cap_pos->d_pos[c].p,
+                              std::min(s->d_cap_dense[c].cap, s->cap_pos->d_pos[c].cap), sb.n, s->idx->k, ss);
+        HIP_TRY(hipEventRecord(s->cap_pos->ev[s->cap_pos->ev_used++], ss));
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(s->h_cap_total + c, s->d_cap_off.p + sb.n, 8, hipMemcpyDeviceToHost, ss));
     HIP_TRY(hipEventRecord(s->ev_cap_gather[c], ss));
@@ -1954,21 +1998,31 @@ int capture_drain(taxor_gpu_searcher *s, const SubBatch &sb, size_t i)
     const uint64_t total = s->h_cap_total[d];
     if (total > sb.slots || total > s->d_cap_dense[d].cap)
         return fail(TAXOR_E_INTERNAL, "capture: a sub-batch of %llu slots holds %llu hashes", (unsigned long long)sb.slots, (unsigned long long)total);
+    const bool with_pos = s->cap_pos && s->cap_cur->pos;
+    if (with_pos && total > s->cap_pos->d_pos[d].cap)
+        return fail(TAXOR_E_INTERNAL, "capture: a sub-batch holds %llu hashes, its positions have room for %llu", (unsigned long long)total, (unsigned long long)s->cap_pos->d_pos[d].cap);
+    // a chunk's hashes and, where they are captured, its positions behind them: one event covers both
+    auto append = [&](int pin, uint64_t n) -> int {
+        if (!s->cap_cur->append(s->h_cap_pin[pin], n)) return fail(TAXOR_E_INTERNAL, "capture: the batch holds more hashes than slots");
+        if (with_pos && !s->cap_cur->append_positions(s->cap_pos->h_pin[pin], n)) return fail(TAXOR_E_INTERNAL, "capture: the batch holds more positions than slots");
+        return 0;
+    };
     uint64_t prev_n = 0;
     int c = 0;
     for (uint64_t at = 0; at < total; at += kCapChunk, ++c) {
         const uint64_t n = std::min(kCapChunk, total - at);
         HIP_TRY(hipMemcpyAsync(s->h_cap_pin[c & 1], s->d_cap_dense[d].p + at, n * 8, hipMemcpyDeviceToHost, s->st_cap));
+        if (with_pos) HIP_TRY(hipMemcpyAsync(s->cap_pos->h_pin[c & 1], s->cap_pos->d_pos[d].p + at, n * 4, hipMemcpyDeviceToHost, s->st_cap));
         HIP_TRY(hipEventRecord(s->ev_cap[c & 1], s->st_cap));
         if (c) {
             HIP_TRY(hipEventSynchronize(s->ev_cap[(c - 1) & 1]));
-            if (!s->cap_cur->append(s->h_cap_pin[(c - 1) & 1], prev_n)) return fail(TAXOR_E_INTERNAL, "capture: the batch holds more hashes than slots");
+            if (int rc = append((c - 1) & 1, prev_n)) return rc;
         }
         prev_n = n;
     }
     if (c) {
         HIP_TRY(hipEventSynchronize(s->ev_cap[(c - 1) & 1]));
-        if (!s->cap_cur->append(s->h_cap_pin[(c - 1) & 1], prev_n)) return fail(TAXOR_E_INTERNAL, "capture: the batch holds more hashes than slots");
+        if (int rc = append((c - 1) & 1, prev_n)) return rc;
     }
     return 0;
 }
@@ -1988,6 +2042,21 @@ int capture_finish(taxor_gpu_searcher *s)
     for (uint64_t r = 0; r < n; ++r) b.hash_off[r + 1] = b.hash_off[r] + b.n_hashes[r];
     if (b.hash_off[n] != b.total_hashes)
         return fail(TAXOR_E_INTERNAL, "capture: the counts sum to %llu hashes, %llu were gathered", (unsigned long long)b.hash_off[n], (unsigned long long)b.total_hashes);
+    if (b.pos) {
+        for (size_t i = 0; s->cap_pos && i + 1 < s->cap_pos->ev_used; i += 2) {      // every gather has ended, so has every kernel in front of one
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, s->cap_pos->ev[i], s->cap_pos->ev[i + 1]));
+            b.pos_seconds += (double)ms * 1e-3;
+        }
+        if (b.pos_count != b.total_hashes)
+            return fail(TAXOR_E_INTERNAL, "capture: %llu hashes were gathered, %llu positions", (unsigned long long)b.total_hashes, (unsigned long long)b.pos_count);
+        // every saved hash was emitted from a k-mer of its read: a hash no k-mer gave is never a result
+        for (uint64_t r = 0; r < n; ++r)
+            for (uint64_t i = b.hash_off[r]; i < b.hash_off[r + 1]; ++i)
+                if (b.pos[i] == 0xFFFFFFFFu || (uint64_t)b.pos[i] + b.kmer_size > b.read_len[r])
+                    return fail(TAXOR_E_INTERNAL, "capture: no k-mer of read %llu (%u bases) hashes to entry %llu of its list (0x%016llx)", (unsigned long long)r, b.read_len[r],
+                                (unsigned long long)(i - b.hash_off[r]), (unsigned long long)b.hashes[i]);
+    }
     b.finish();
     s->cap_done = true;
     return 0;
@@ -3204,6 +3273,29 @@ extern "C" int taxor_gpu_saved_view_get(const taxor_gpu_saved *saved, taxor_gpu_
     saved->view(view);
     return TAXOR_OK;
 }
+
+extern "C" int taxor_gpu_search_capture_positions(taxor_gpu_searcher *s, int on)
+{
+    if (!s) return fail(TAXOR_E_ARG, "search_capture_positions: null searcher");
+    if (!s->capture) return fail(TAXOR_E_ARG, "search_capture_positions: capture is off (taxor_gpu_search_capture); positions ride beside the captured hashes");
+    if (s->ran && !s->synced) return fail(TAXOR_E_ARG, "search_capture_positions: a batch is in flight; end it first");
+    if (on && s->idx->w_min != 0)
+        return fail(TAXOR_E_ARG, "search_capture_positions: the searcher does not hash syncmers (a minimiser or k-mer index, window %d): its lists are neither deduplicated nor "
+                                 "wyhash(k-mer), a position by content is not defined", s->idx->w_min);
+    HIP_TRY(hipSetDevice(s->idx->device));
+    if (on && !s->cap_pos) s->cap_pos = new CapturePositions();
+    if (!on) capture_positions_release(s);
+    return TAXOR_OK;
+}
+
+extern "C" int taxor_gpu_saved_positions(const taxor_gpu_saved *saved, const uint32_t **pos)
+{
+    if (!saved || !pos) return fail(TAXOR_E_ARG, "saved_positions: null argument");
+    *pos = saved->pos;
+    return TAXOR_OK;
+}
+
+extern "C" double taxor_gpu_saved_positions_seconds(const taxor_gpu_saved *saved) { return saved ? saved->pos_seconds : 0.0; }
 
 extern "C" uint64_t taxor_gpu_saved_bytes(const taxor_gpu_saved *saved) { return saved ? saved->bytes() : 0; }
 extern "C" void taxor_gpu_saved_free(taxor_gpu_saved *saved) { delete saved; }

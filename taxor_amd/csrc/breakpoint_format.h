@@ -63,4 +63,27 @@ inline void breakpoint_line(std::string &out, const char *id, uint64_t id_len, u
     out += '\n';
 }
 
+// ---- `--base-positions`: the same header and the same line, with two columns appended.  left_end_base =
+// pos[break_hash - 1] + k, the base behind the last k-mer in front of the break; break_base = pos[break_hash], the first base of the
+// k-mer the break stands in front of -- real bases, from the positions captured with the hash lists
+inline std::string breakpoint_header_positions()
+{
+    std::string h = breakpoint_header();
+    h.pop_back();
+    return h + "\tLEFT_END_BASE\tBREAK_BASE\n";
+}
+
+inline void breakpoint_line_positions(std::string &out, const char *id, uint64_t id_len, uint64_t query_len, uint32_t n_hashes, uint32_t candidates, breakpoint_ref best,
+                                      uint32_t single, uint32_t break_hash, breakpoint_ref left, uint32_t pre_a, uint32_t pre_b, breakpoint_ref right, uint32_t suf_b,
+                                      uint32_t suf_a, uint32_t gain, uint64_t left_end_base, uint64_t break_base)
+{
+    breakpoint_line(out, id, id_len, query_len, n_hashes, candidates, best, single, break_hash, left, pre_a, pre_b, right, suf_b, suf_a, gain);
+    out.pop_back();                                    // the line's '\n'
+    out += '\t';
+    breakpoint_put_u64(out, left_end_base);
+    out += '\t';
+    breakpoint_put_u64(out, break_base);
+    out += '\n';
+}
+
 }   // namespace taxor

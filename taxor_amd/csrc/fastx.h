@@ -159,6 +159,7 @@ struct Batch {
     struct BreakRow {
         uint32_t read, gain, break_hash, pre_a, suf_b, pre_b, suf_a, single, n_cand;
         int64_t bin_a, bin_b, bin_best;
+        uint64_t left_end_base = 0, break_base = 0;     // --base-positions: pos[break_hash - 1] + k and pos[break_hash]
     };
     std::vector<BreakRow> bp_rows;
     bool bp_set = false;
@@ -173,6 +174,7 @@ struct Batch {
     struct Seg {
         uint32_t start, end, hits, best_hits;
         int64_t bin;
+        uint64_t base_start = 0, base_end = 0;          // --base-positions: pos[start] and pos[end - 1] + k
     };
     std::vector<SegRow> sg_rows;
     std::vector<Seg> sg_segs;

@@ -262,4 +262,10 @@ void launch_hash_offsets(const uint32_t *nh, uint64_t *off, uint32_t n_reads, hi
 void launch_gather_hashes(const uint64_t *hashes, const uint64_t *hoff, const uint32_t *hcap, const uint32_t *nh, const uint64_t *off,
                           uint64_t *dense, uint64_t dense_cap, uint32_t n_reads, hipStream_t st);
 
+// positions of a sub-batch's gathered hashes (positions.hip, taxor_gpu_search_capture_positions; syncmer lists only): pos[off[r] + i] =
+// the first base of read r at which a k-mer's wyhash(canonical form) equals dense[off[r] + i], 0xFFFFFFFF where none does.  packed,
+// poff, rlen: the sub-batch's packed reads; every entry of every list inside dense_cap is written
+void launch_hash_positions(const uint32_t *packed, const uint64_t *poff, const uint32_t *rlen, const uint64_t *off, const uint64_t *dense,
+                           uint32_t *pos, uint64_t dense_cap, uint32_t n_reads, int k, hipStream_t st);
+
 } // namespace taxor

@@ -22,6 +22,11 @@ struct taxor_gpu_saved {
     std::vector<uint64_t> threshold, hash_off;                    // hash_off: n_reads + 1 entries
     uint64_t *hashes = nullptr;
     uint64_t hash_cap = 0;                                        // entries the mapping holds
+    // where along its read each hash lies (taxor_gpu_search_capture_positions): a second mapping managed like
+    // `hashes`, 4 bytes per hash, parallel to it.  nullptr when the batch was captured without positions
+    uint32_t *pos = nullptr;
+    uint64_t pos_cap = 0, pos_count = 0;                          // entries the mapping holds / entries appended
+    double pos_seconds = 0;                                       // seconds between the event pairs around the batch's position kernels
     uint32_t use_syncmer = 0, kmer_size = 0, syncmer_size = 0, t_syncmer = 0, scaling = 1, model = 0;
     uint64_t window_size = 0;
     double error_rate = 0, ratio = 0;
@@ -50,6 +55,25 @@ struct taxor_gpu_saved {
         total_hashes += n;
         return true;
     }
+    // the position store beside the hashes: the same capacity in entries, reserved after reserve()
+    bool reserve_positions()
+    {
+        release_positions();
+        pos_cap = hash_cap ? hash_cap : 1;
+        void *p = mmap(nullptr, pos_cap * 4, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+        if (p == MAP_FAILED) { pos_cap = 0; return false; }
+        (void)madvise(p, pos_cap * 4, MADV_HUGEPAGE);
+        pos = static_cast<uint32_t *>(p);
+        return true;
+    }
+    // the positions of the next n hashes, appended in step with append()
+    bool append_positions(const uint32_t *src, uint64_t n)
+    {
+        if (!pos || n > pos_cap - pos_count) return false;
+        if (n) memcpy(pos + pos_count, src, n * 4);
+        pos_count += n;
+        return true;
+    }
     // the mapping shrinks to the pages that hold hashes
     void finish()
     {
@@ -58,9 +82,21 @@ struct taxor_gpu_saved {
             munmap(reinterpret_cast<char *>(hashes) + keep, hash_cap * 8 - keep);
             hash_cap = keep / 8;
         }
+        const uint64_t pkeep = ((pos_count ? pos_count : 1) * 4 + page - 1) / page * page;
+        if (pos && pkeep < pos_cap * 4) {
+            munmap(reinterpret_cast<char *>(pos) + pkeep, pos_cap * 4 - pkeep);
+            pos_cap = pkeep / 4;
+        }
+    }
+    void release_positions()
+    {
+        if (pos) munmap(pos, pos_cap * 4);
+        pos = nullptr;
+        pos_cap = pos_count = 0;
     }
     void release()
     {
+        release_positions();
         if (hashes) munmap(hashes, hash_cap * 8);
         hashes = nullptr;
         hash_cap = total_hashes = 0;
@@ -68,7 +104,8 @@ struct taxor_gpu_saved {
     // host bytes the object holds
     uint64_t bytes() const
     {
-        return total_hashes * 8 + (read_len.size() + n_hashes.size() + order.size() + sub_first.size()) * 4 + (threshold.size() + hash_off.size()) * 8;
+        return total_hashes * 8 + (pos ? pos_count * 4 : 0) + (read_len.size() + n_hashes.size() + order.size() + sub_first.size()) * 4 +
+               (threshold.size() + hash_off.size()) * 8;
     }
     void view(taxor_gpu_saved_view *v) const
     {
@@ -107,6 +144,8 @@ inline std::string saved_validate(const taxor_gpu_saved &b)
     if (b.read_len.size() != n || b.n_hashes.size() != n || b.threshold.size() != n || b.order.size() != n || b.hash_off.size() != n + 1)
         return "n_reads: the per-read arrays do not hold " + u(n) + " entries";
     if (b.total_hashes > b.hash_cap || (b.total_hashes && !b.hashes)) return "total_hashes: " + u(b.total_hashes) + " hashes, the array holds " + u(b.hash_cap);
+    if (b.pos && (b.pos_count != b.total_hashes || b.pos_count > b.pos_cap))
+        return "positions: the store holds " + u(b.pos_count) + " positions (room for " + u(b.pos_cap) + "), the batch " + u(b.total_hashes) + " hashes";
     if (b.hash_off[0] != 0) return "hash_off: the first offset is " + u(b.hash_off[0]) + ", not 0";
     for (uint64_t r = 0; r < n; ++r) {          // the offsets first, all of them: a count is judged against sound offsets
         if (b.hash_off[r + 1] < b.hash_off[r]) return "hash_off: offsets do not ascend at read " + u(r);

@@ -31,6 +31,7 @@ struct Config : ReaderOptions {              // taxor_search_configuration.hpp:8
     uint32_t breakpoint_min_gain = 0;  // --breakpoint-min-gain: hits the split must explain beyond the best single reference, >= 1 (0: not given, 1)
     std::string segments_file;         // --segments-file: one line per segment of a read whose best path among its references switches (segments.hip)
     uint32_t segments_switch_cost = 0; // --segments-switch-cost: hits a switch of reference costs, in [1,2^20] (0: not given, 16)
+    bool base_positions = false;       // --base-positions: every hash's position in its read is captured (positions.hip); the two files above gain base columns
     std::string exclusive_file;        // --exclusive-file: per user bin the hashes that no other reference on a read's list holds, over the whole run (exclusive.hip)
     std::string exclusive_reads_file;  // --exclusive-reads-file: the same per line of the TSV, for reads with two candidates or more
     uint32_t exclusive_precision = 0;  // hidden --exclusive-precision: registers per sketch = 2^this, in [4,16] (0: the library's 12)
@@ -93,7 +94,12 @@ void usage()
             "                           mosaic (a chimeric read, a prophage or IS element inside a chromosome read, a concatemer); ONE index file,\n"
             "                           ONE device; --output-file is then optional\n"
             "  --segments-switch-cost <n> with --segments-file: the hits a switch of reference must pay for, in [1,1048576] (default 16)\n"
-            "  --exclusive-file <f>     per reference that was a candidate of any read: its hits, and how many of them are hashes that NO other\n"
+            "  --base-positions         with --breakpoint-file and/or --segments-file, syncmer indexes only: every hash's position in its read is\n"
+            "                           recorded on the device (the first base at which the read shows the hashed k-mer, on either strand), and\n"
+            "                           the files gain real base columns at the end of each line: LEFT_END_BASE, BREAK_BASE / BASE_START, BASE_END\n"
+            "                           (where the reference's tie rule skips a k-mer's first occurrence the position is that earlier occurrence;\n"
+            "                           a read of more than 2048 hashes is swept once per 2048)\n"
+            "  --exclusive-file <f>    per reference that was a candidate of any read: its hits, and how many of them are hashes that NO other\n"
             "                           reference the same read reported holds (which of several near-identical strains a read supports); ONE\n"
             "                           index file, ONE device; --output-file is then optional\n"
             "  --exclusive-reads-file <f> the same per line of --output-file, for reads with two candidates or more; alone or beside --exclusive-file\n"
@@ -222,6 +228,20 @@ void advanced_help()
                     "                           k = 22, s = 12 about one base in 11 starts a syncmer, so 16 hits are roughly 180 bases of exact match, and\n"
                     "                           an inner segment, which pays twice, has to beat its flank by some 350 bases' worth of hits -- less than the\n"
                     "                           mobile elements people look for.\n"
+                    "  --base-positions         with --breakpoint-file and/or --segments-file; refused without either, and for a minimiser or k-mer index\n"
+                    "                           (their lists are not deduplicated and their values are not wyhash(k-mer)).  For a read of L bases, k-mer\n"
+                    "                           size k and its ordered hash list, pos[i] = min { p in [0, L-k] : wyhash(min(f_p, revcomp(f_p))) == hash i },\n"
+                    "                           f_p the k-mer at base p after the dna4 mapping: the first base at which the read shows this k-mer, on either\n"
+                    "                           strand.  It is computed on the device while the batch's packed reads are resident, one more kernel per\n"
+                    "                           sub-batch, and kept beside the saved hash lists, 4 bytes per hash.  Existing columns stay as they are; appended\n"
+                    "                           at the end of the header and of every line: --breakpoint-file LEFT_END_BASE = pos[BREAK_HASH - 1] + k and\n"
+                    "                           BREAK_BASE = pos[BREAK_HASH]; --segments-file BASE_START = pos[HASH_START] and BASE_END = pos[HASH_END - 1] + k\n"
+                    "                           (exclusive, at most QUERY_LEN).  The position is defined by CONTENT.  It is the start of the window that first\n"
+                    "                           emitted the hash except where the reference's stateful tie rule leaves a k-mer's first occurrence unselected\n"
+                    "                           and selects a later one (homopolymers, short tandem repeats): pos is then the earlier occurrence, and positions\n"
+                    "                           need not increase along the list.  Cost: the read's list is taken in pieces of 2048 hashes, and every k-mer of\n"
+                    "                           the read is hashed once per piece: a read with P pieces is swept P times (a 1-Mbp read: some 90,000 hashes, 45\n"
+                    "                           sweeps).\n"
                     "  --exclusive-file <f>     columns ACCESSION, TAXID, CANDIDATE_READS, HITS, EXCLUSIVE_HITS, EXCLUSIVE_READS, DISTINCT_EXCLUSIVE,\n"
                     "                           EXCLUSIVE_FRACTION; one line per reference that was a candidate of an examined read, in the coverage file's\n"
                     "                           order.  Candidates and the lookup are --breakpoint-file's (every tuple of the read with a match, not only the\n"
@@ -530,6 +550,8 @@ struct SearchRun {
     FILE *segments_out = nullptr;             // --segments-file; written by the sequencer as well
     std::vector<uint32_t> segments_species;   // user bin -> the species the TSV names for it
     double t_segments = 0, t_segments_kernels = 0;       // seconds inside taxor_gpu_segments_add_batch and in its kernels, summed over workers
+    double t_positions_kernels = 0;           // --base-positions: seconds between the event pairs around k_hash_positions, summed over batches and workers
+    uint64_t positions_hashes = 0;            // ... and the hashes that got a position
     uint64_t segments_lookups = 0, segments_lines = 0, segments_reported = 0, segments_examined = 0, segments_reads = 0, segments_groups = 0;
     taxor_gpu_exclusive *exclusive = nullptr; // --exclusive-file / --exclusive-reads-file: the object beside the resident index, for the whole run (exclusive.hip)
     FILE *exclusive_reads_out = nullptr;      // --exclusive-reads-file; written by the sequencer as well
@@ -655,6 +677,7 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             if (n < 1 || n > (double)taxor::SEGMENTS_MAX_SWITCH_COST) die("Validation failed for option --segments-switch-cost: Value not in range [1,1048576].");
             cfg.segments_switch_cost = (uint32_t)n;
         }
+        else if (k == "--base-positions") cfg.base_positions = true;
         else if (k == "--exclusive-file") {
             cfg.exclusive_file = val();
             if (cfg.exclusive_file.empty()) die("Validation failed for option --exclusive-file: the file name is empty.");
@@ -780,6 +803,8 @@ bool parse_search_args(const std::vector<std::string> &args, SearchRun &run)
             die("Validation failed for option --gather: --segments-file runs on ONE device, where nothing is gathered; leave --gather out.");
         if (!cfg.expect_file.empty() && cfg.report_file.empty()) die("Option --expect compares the TSV: it needs --output-file.");
     }
+    if (cfg.base_positions && cfg.breakpoint_file.empty() && cfg.segments_file.empty())   // before any HIP call
+        die("Option --base-positions adds base columns to --breakpoint-file and --segments-file: it needs one of them.");
     if (cfg.exclusive_precision && cfg.exclusive_file.empty()) die("Option --exclusive-precision sizes the sketches of --exclusive-file: it needs that option.");
     if (cfg.exclusive_mode()) {   // before any HIP call
         const std::string opt = !cfg.exclusive_file.empty() ? "--exclusive-file" : "--exclusive-reads-file";
@@ -1354,8 +1379,13 @@ struct ReportWriter {
         breakpoint_text.clear();
         for (const Batch::BreakRow &x : bt.bp_rows) {
             if (x.read >= n) die("internal: a break names a read outside its chunk");
-            taxor::breakpoint_line(breakpoint_text, bt.ids.ptr(x.read), bt.ids.len(x.read), bt.offsets[x.read + 1] - bt.offsets[x.read], bt.n_hashes[x.read], x.n_cand,
-                                   ref(x.bin_best), x.single, x.break_hash, ref(x.bin_a), x.pre_a, x.pre_b, ref(x.bin_b), x.suf_b, x.suf_a, x.gain);
+            if (run.cfg.base_positions)
+                taxor::breakpoint_line_positions(breakpoint_text, bt.ids.ptr(x.read), bt.ids.len(x.read), bt.offsets[x.read + 1] - bt.offsets[x.read], bt.n_hashes[x.read],
+                                                 x.n_cand, ref(x.bin_best), x.single, x.break_hash, ref(x.bin_a), x.pre_a, x.pre_b, ref(x.bin_b), x.suf_b, x.suf_a, x.gain,
+                                                 x.left_end_base, x.break_base);
+            else
+                taxor::breakpoint_line(breakpoint_text, bt.ids.ptr(x.read), bt.ids.len(x.read), bt.offsets[x.read + 1] - bt.offsets[x.read], bt.n_hashes[x.read], x.n_cand,
+                                       ref(x.bin_best), x.single, x.break_hash, ref(x.bin_a), x.pre_a, x.pre_b, ref(x.bin_b), x.suf_b, x.suf_a, x.gain);
         }
         run.breakpoint_lines += bt.bp_rows.size();
         if (!breakpoint_text.empty() && fwrite(breakpoint_text.data(), 1, breakpoint_text.size(), run.breakpoint_out) != breakpoint_text.size())
@@ -1383,8 +1413,13 @@ struct ReportWriter {
             const char *shape = taxor::segments_shape(x.n_seg, segments_bins.data());
             for (uint32_t j = 0; j < x.n_seg; ++j) {
                 const Batch::Seg &sg = bt.sg_segs[x.first + j];
-                taxor::segments_line(segments_text, bt.ids.ptr(x.read), bt.ids.len(x.read), bt.offsets[x.read + 1] - bt.offsets[x.read], bt.n_hashes[x.read], x.n_cand,
-                                     x.n_seg, shape, x.path_hits, x.single, j, sg.start, sg.end, ref(sg.bin), sg.hits, ref(x.bin_best), sg.best_hits);
+                if (run.cfg.base_positions)
+                    taxor::segments_line_positions(segments_text, bt.ids.ptr(x.read), bt.ids.len(x.read), bt.offsets[x.read + 1] - bt.offsets[x.read], bt.n_hashes[x.read],
+                                                   x.n_cand, x.n_seg, shape, x.path_hits, x.single, j, sg.start, sg.end, ref(sg.bin), sg.hits, ref(x.bin_best), sg.best_hits,
+                                                   sg.base_start, sg.base_end);
+                else
+                    taxor::segments_line(segments_text, bt.ids.ptr(x.read), bt.ids.len(x.read), bt.offsets[x.read + 1] - bt.offsets[x.read], bt.n_hashes[x.read], x.n_cand,
+                                         x.n_seg, shape, x.path_hits, x.single, j, sg.start, sg.end, ref(sg.bin), sg.hits, ref(x.bin_best), sg.best_hits);
             }
             run.segments_lines += x.n_seg;
         }
@@ -1812,6 +1847,9 @@ struct GpuStage {
         }
         for (auto *s : sr)
             if (taxor_gpu_search_capture(s, 1) != TAXOR_OK) die(taxor_gpu_last_error());
+        if (cfg.base_positions)      // --base-positions: the saved batches carry every hash's position in its read (positions.hip)
+            for (auto *s : sr)
+                if (taxor_gpu_search_capture_positions(s, 1) != TAXOR_OK) die(taxor_gpu_last_error());
     }
     // after a batch's end: its saved lists are taken ONCE, used by the consumers that are on and freed -- none is kept across batches,
     // so host memory stays bounded by the batches in flight.  The hit map's share goes to each chunk of the batch
@@ -1865,6 +1903,18 @@ struct GpuStage {
             }
         }
         const double c3b = now();
+        // --base-positions: the batch's positions, parallel to its hashes; the base columns are host lookups at the indices the analyses return
+        const uint32_t *hpos = nullptr;
+        taxor_gpu_saved_view svv{};
+        if (rc == TAXOR_OK && run.cfg.base_positions) {
+            if (taxor_gpu_saved_positions(sv, &hpos) != TAXOR_OK || taxor_gpu_saved_view_get(sv, &svv) != TAXOR_OK) die(taxor_gpu_last_error());
+            if (!hpos && svv.total_hashes) die("internal: a batch was saved without the positions --base-positions asked for");
+        }
+        // the position of hash i of read r of the batch
+        auto pos_of = [&](uint64_t r, uint64_t i) -> uint64_t {
+            if (r >= svv.n_reads || i >= svv.hash_off[r + 1] - svv.hash_off[r]) die("internal: a base position is asked for a hash outside its read's list");
+            return hpos[svv.hash_off[r] + i];
+        };
         // --breakpoint-file: the reported reads of the batch go to the chunks that hold them
         taxor_breakpoint_batch bb{};
         if (rc == TAXOR_OK && run.breakpoint) rc = taxor_gpu_breakpoint_add_batch(run.breakpoint, s, sv, &bb);
@@ -1881,6 +1931,12 @@ struct GpuStage {
                     if (bb.examined[r] && bb.gain[r] >= bb.min_gain)
                         bt->bp_rows.push_back(Batch::BreakRow{(uint32_t)i, bb.gain[r], bb.break_hash[r], bb.pre_a[r], bb.suf_b[r], bb.pre_b[r], bb.suf_a[r], bb.single[r],
                                                               bb.n_candidates[r], bb.bin_a[r], bb.bin_b[r], bb.bin_best[r]});
+                    if (hpos && !bt->bp_rows.empty() && bt->bp_rows.back().read == (uint32_t)i) {
+                        Batch::BreakRow &x = bt->bp_rows.back();
+                        if (x.break_hash == 0) die("internal: a reported break stands in front of the read's first hash");
+                        x.left_end_base = pos_of(r, x.break_hash - 1) + svv.kmer_size;
+                        x.break_base = pos_of(r, x.break_hash);
+                    }
                 }
                 bt->bp_set = true;
                 if (!run.write_tsv) bt->n_hashes.assign(bb.n_hashes + r0, bb.n_hashes + r0 + n);
@@ -1904,8 +1960,15 @@ struct GpuStage {
                     const uint64_t r = r0 + i, k = gb.seg_off[r + 1] - gb.seg_off[r];
                     if (k == 0) continue;
                     bt->sg_rows.push_back(Batch::SegRow{(uint32_t)i, gb.n_candidates[r], (uint32_t)k, gb.path_hits[r], gb.single[r], gb.bin_best[r], bt->sg_segs.size()});
-                    for (uint64_t j = gb.seg_off[r]; j < gb.seg_off[r + 1]; ++j)
+                    for (uint64_t j = gb.seg_off[r]; j < gb.seg_off[r + 1]; ++j) {
                         bt->sg_segs.push_back(Batch::Seg{gb.seg_start[j], gb.seg_end[j], gb.seg_hits[j], gb.seg_best_hits[j], gb.seg_bin[j]});
+                        if (hpos) {
+                            Batch::Seg &g = bt->sg_segs.back();
+                            if (g.end <= g.start) die("internal: a reported segment holds no hash");
+                            g.base_start = pos_of(r, g.start);
+                            g.base_end = pos_of(r, g.end - 1) + svv.kmer_size;
+                        }
+                    }
                 }
                 bt->sg_set = true;
                 if (!run.write_tsv) bt->n_hashes.assign(gb.n_hashes + r0, gb.n_hashes + r0 + n);
@@ -1942,10 +2005,15 @@ struct GpuStage {
             }
         }
         const double c3e = now();
+        const double pos_seconds = run.cfg.base_positions ? taxor_gpu_saved_positions_seconds(sv) : 0.0;
         taxor_gpu_saved_free(sv);
         if (rc != TAXOR_OK) die(taxor_gpu_last_error());
         const double c4 = now(), shared = (c1 - c0) + (c4 - c3e);       // taking and freeing the lists: the first consumer's
         std::lock_guard<std::mutex> lk(run.stat_mu);
+        if (run.cfg.base_positions) {
+            run.t_positions_kernels += pos_seconds;
+            run.positions_hashes += svv.total_hashes;
+        }
         if (run.exclusive) {
             run.t_exclusive += c3e - c3d + (run.coverage || run.hitmap || run.confidence || run.breakpoint || run.segments ? 0.0 : shared);
             run.t_exclusive_kernels += eb.seconds_kernels;
@@ -2344,6 +2412,9 @@ void search_resident(SearchRun &run, taxor_hixf *h, const taxor_hixf_view *view,
         finish_hitmap(run);
         trace("hit maps written");
     }
+    if (run.cfg.base_positions && tune_env("TAXOR_CLI_TRACE"))
+        fprintf(stderr, "[trace] positions: %llu hashes placed, %.6f s in k_hash_positions (event pairs, one per sub-batch, summed over workers)\n",
+                (unsigned long long)run.positions_hashes, run.t_positions_kernels);
     if (run.breakpoint) {
         finish_breakpoint(run);
         trace("breaks written");
@@ -2468,6 +2539,9 @@ void search_files(SearchRun &run, const std::string &hixf_file, const std::vecto
             die("Validation failed for option --segments-file: the index would be searched in resident passes (" + std::string(why) + "; it holds " +
                 std::to_string(whole.index_bytes >> 20) + " MiB), and its leaf bins are then never resident together; segmenting pass by pass is not built.");
     }
+    if (cfg.base_positions && !view->use_syncmer)
+        die("Validation failed for option --base-positions: the index does not hash syncmers (a minimiser or k-mer index); its hash lists are not deduplicated and their "
+            "values are not wyhash(k-mer), so a position by content is not defined.");
     if (cfg.exclusive_mode()) {
         // as for --breakpoint-file
         if (budget && cfg.index_budget_mib && whole.index_bytes <= budget) budget = 0;

@@ -127,12 +127,12 @@ int main(int argc, char **argv)
     if (!cfg.breakpoint_file.empty()) {
         run.breakpoint_out = fopen(cfg.breakpoint_file.c_str(), "wb");
         if (!run.breakpoint_out) die("cannot open breakpoint file " + cfg.breakpoint_file);
-        fputs(taxor::breakpoint_header(), run.breakpoint_out);
+        fputs(cfg.base_positions ? taxor::breakpoint_header_positions().c_str() : taxor::breakpoint_header(), run.breakpoint_out);
     }
     if (!cfg.segments_file.empty()) {
         run.segments_out = fopen(cfg.segments_file.c_str(), "wb");
         if (!run.segments_out) die("cannot open segments file " + cfg.segments_file);
-        fputs(taxor::segments_header(), run.segments_out);
+        fputs(cfg.base_positions ? taxor::segments_header_positions().c_str() : taxor::segments_header(), run.segments_out);
     }
     if (!cfg.exclusive_reads_file.empty()) {     // --exclusive-file is written once, at the run's end
         run.exclusive_reads_out = fopen(cfg.exclusive_reads_file.c_str(), "wb");

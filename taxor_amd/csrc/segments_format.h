@@ -58,4 +58,26 @@ inline void segments_line(std::string &out, const char *id, uint64_t id_len, uin
     out += '\n';
 }
 
+// ---- `--base-positions`: the same header and the same line, with two columns appended.  base_start = pos of
+// the segment's first hash; base_end = pos of its last hash + k, exclusive and at most query_len -- real bases
+inline std::string segments_header_positions()
+{
+    std::string h = segments_header();
+    h.pop_back();
+    return h + "\tBASE_START\tBASE_END\n";
+}
+
+inline void segments_line_positions(std::string &out, const char *id, uint64_t id_len, uint64_t query_len, uint32_t n_hashes, uint32_t candidates, uint32_t n_segments,
+                                    const char *shape, uint32_t path_hits, uint32_t single, uint32_t segment, uint32_t start, uint32_t end, breakpoint_ref ref, uint32_t hits,
+                                    breakpoint_ref best, uint32_t best_hits, uint64_t base_start, uint64_t base_end)
+{
+    segments_line(out, id, id_len, query_len, n_hashes, candidates, n_segments, shape, path_hits, single, segment, start, end, ref, hits, best, best_hits);
+    out.pop_back();                                    // the line's '\n'
+    out += '\t';
+    breakpoint_put_u64(out, base_start);
+    out += '\t';
+    breakpoint_put_u64(out, base_end);
+    out += '\n';
+}
+
 }   // namespace taxor

@@ -531,6 +531,11 @@ class Searcher:
         """taxor_gpu_search_capture: while on, every batch also leaves its hash lists on the host (take_saved)"""
         check(_lib.lib().taxor_gpu_search_capture(self._h, 1 if on else 0))
 
+    def capture_positions(self, on=True):
+        """taxor_gpu_search_capture_positions: while on (capture must be on, a syncmer index), every saved batch also carries
+        SavedBatch.positions -- for each hash the first base at which its read shows the hashed k-mer, on either strand"""
+        check(_lib.lib().taxor_gpu_search_capture_positions(self._h, 1 if on else 0))
+
     def take_saved(self) -> "SavedBatch":
         """the saved batch of the last batch that ran with capture on (taxor_gpu_search_take_saved)"""
         h = C.c_void_p()
@@ -643,6 +648,11 @@ class SavedBatch:
         self.sub_first = np.ctypeslib.as_array(v.sub_first, shape=(ns + 1,))
         self.order = arr(v.order, n, np.uint32)
         self.params = {f: getattr(v, f) for f in self.PARAMS}
+        # taxor_gpu_saved_positions: every hash's position in its read, parallel to `hashes`; None when captured without positions
+        pp = C.POINTER(C.c_uint32)()
+        check(_lib.lib().taxor_gpu_saved_positions(h, C.byref(pp)))
+        self.positions = arr(pp, t, np.uint32) if pp else None
+        self.positions_seconds = float(_lib.lib().taxor_gpu_saved_positions_seconds(h))
 
     @property
     def nbytes(self):
@@ -650,7 +660,7 @@ class SavedBatch:
 
     def close(self):
         if getattr(self, "_h", None):
-            for f in ("read_len", "n_hashes", "threshold", "hash_off", "hashes", "sub_first", "order"):
+            for f in ("read_len", "n_hashes", "threshold", "hash_off", "hashes", "sub_first", "order", "positions"):
                 setattr(self, f, None)
             _lib.lib().taxor_gpu_saved_free(self._h)
             self._h = None
